@@ -1,6 +1,7 @@
 """Benchmark: graph-match pairs/sec of the matcher's forward (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 1024] [--n 256] [--dtype bf16]
+                    [--dump-outputs DIR] [--full]
 
 One step = one full ``Net.forward`` (eval, AFA-U regression, soft top-k, host Hungarian + greedy,
 match classifier) over a batch of ``--batch`` synthetic pairs of ``--n``-keypoint Delaunay graphs
@@ -8,6 +9,12 @@ per GPU, inputs resident in HBM (graph generation is outside the timed region). 
 launched by torch.distributed.run, one process per GPU, pairs sharded (no data-path collective;
 gloo barrier + max-over-ranks timing only), ``value`` = pairs of all ranks / max rank time.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--dump-outputs DIR``
+also writes the last timed step's outputs as ``DIR/<name>.npy``.  ``--full`` adds everything else the
+benchmark measures or checks after the timed steps: the profiled pass and roofline of the product
+GEMM, the timed-batch self-check, the fp32 / 128-pair / strong-scaling lines, the on-device graph
+build, the CPU-oracle baseline with the parity gate, and the c2 / c4 / c5 / training lines.
 """
 import argparse
 import json
@@ -416,6 +423,82 @@ def train_line(args, dev, B=64, n=256, steps=4, warmup=2, cpu_pairs=2):
     return res
 
 
+def headline(args, world, net, pairs_total, elapsed, gpu_s, lsa_s, E_tot, tuning, shared_devices, cpu_share,
+             pinned, t_gen, dumped):
+    """The result line of a plain run (``--full`` adds its own fields to it): the timed steps' rate."""
+    return {
+        "metric": "graph-match pairs/sec @ n=256 kpts, batch=1024, 1 & 8 GPU",
+        "value": pairs_total / elapsed,
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if args.config == "c4" else "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "full": args.full,
+        "data": "synthetic (seeded Delaunay keypoint graphs, random node/global features, random-init weights)",
+        "config": {"workload": ("1 probe x %d gallery graphs (%d per GPU), n=%d keypoints, probe SplineConv "
+                                "once per pipeline chunk (accounting: shared probe stage), %s MFMA; full "
+                                "Net.forward per pair" % (args.gallery, args.batch, args.n, args.dtype))
+                   if args.config == "c4" else
+                   ("batch=%d pairs/GPU, n=%d keypoints, Delaunay edges, factorized Kronecker "
+                    "affinity, %s MFMA; full Net.forward incl. AFA-U, soft top-k, host Hungarian, "
+                    "greedy top-k, MatchClassifier" % (args.batch, args.n, args.dtype)),
+                   "survey_config": args.config,
+                   "afau_mode": net.afau_mode,
+                   "global_batch": args.gallery if args.config == "c4" else args.batch * world,
+                   "n_keypoints": args.n,
+                   "edges_per_graph": E_tot / (2.0 * args.batch), "parallelism": "pair-sharded x%d" % world},
+        "gpu_stage_pairs_per_s": args.batch * world * args.steps / gpu_s,
+        "host_lsa_ms_per_step": lsa_s / args.steps * 1e3,
+        "tuning": tuning or None,
+        "ranks_share_devices": shared_devices,
+        "host_cpus_per_rank": cpu_share,
+        "ranks_pinned": pinned is not None,
+        "input_gen_s": t_gen,
+        "dumped_outputs": dumped,
+    }
+
+
+DUMP_BYTES = 48 << 20     # budget of one --dump-outputs directory (limit: 64 MB)
+
+
+def dump_outputs(res, out_dir, seed=0):
+    """Write the arrays of one forward's result dict as ``out_dir/<name>.npy`` (float32; integer and
+    float64 outputs as float64).  Outputs too large for their share of DUMP_BYTES are cut to a fixed,
+    seeded sample of whole pairs (their indices: ``sample_pairs.npy``), or of flat elements where one
+    pair alone is too large.  -> {name: shape written}."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: v for k, v in res.items() if torch.is_tensor(v)}
+    share = DUMP_BYTES // max(1, sum(v.numel() * 4 > (1 << 20) for v in arrs.values()))
+    rng = np.random.default_rng(seed)
+    written, pick = {}, {}
+    for k in sorted(arrs):
+        v = arrs[k].detach()
+        if v.numel() * 4 > max(share, 1 << 20):
+            row = (v.numel() // v.shape[0]) * 4
+            if v.dim() >= 2 and row <= share:
+                B = v.shape[0]
+                if B not in pick:
+                    pick[B] = np.sort(rng.choice(B, max(1, min(B, share // row)), replace=False))
+                v = v[torch.from_numpy(pick[B]).to(v.device)]
+            else:
+                idx = np.sort(rng.choice(v.numel(), share // 4, replace=False))
+                v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        a = v.cpu()
+        a = (a.double() if a.dtype in (torch.float64, torch.int64, torch.int32) else a.float()).numpy()
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        written[k] = list(a.shape)
+    for B, idx in pick.items():
+        np.save(os.path.join(out_dir, "sample_pairs.npy" if len(pick) == 1 else "sample_pairs_%d.npy" % B),
+                idx.astype(np.float64))
+    return written
+
+
 def log(*a):
     print("[bench %.1fs]" % (time.perf_counter() - T0), *a, file=sys.stderr, flush=True)
 
@@ -432,6 +515,12 @@ def main():
     ap.add_argument("--n", type=int, default=256, help="keypoints per graph")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the last "
+                    "timed step's outputs as DIR/<name>.npy (large ones: a fixed, seeded sample of pairs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run everything else the "
+                    "benchmark measures or checks (profiled pass / roofline, self-check, fp32 / share / strong "
+                    "lines, graph build, CPU baseline + parity gate, c2 / c4 / c5 / training lines); the "
+                    "--no-* switches and --cpu-pairs / --parity-pairs select among these")
     ap.add_argument("--cpu-pairs", type=int, default=32)
     ap.add_argument("--parity-pairs", type=int, default=32, help="pairs of the CPU sample re-run on the GPU "
                     "modes for the parity_vs_oracle report (and the parity_gate)")
@@ -452,6 +541,8 @@ def main():
     ap.add_argument("--tuning", default="", help="kernel-variant switches for A/B runs, key=value[,key=value] "
                     "(fpm_set_tuning keys, include/fpm.h); recorded in the JSON line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "c2":
         args.n, args.batch, args.dtype = 128, 256, "f32"
     elif args.config == "c5":
@@ -568,6 +659,24 @@ def main():
 
     # the headline: K steps with the library's profiling off
     elapsed, gpu_s, lsa_s = timed(net, bt, args.steps, "")
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step returned (each rank its own shard's, rank r > 0 under rank<r>/)
+        dumped = dump_outputs(last[""], os.path.join(args.dump_outputs, "rank%d" % rank) if rank
+                              else args.dump_outputs, args.seed)
+        log("outputs written to %s: %s" % (args.dump_outputs, json.dumps(dumped)))
+    pairs_total = (args.gallery if args.config == "c4" else args.batch * world) * args.steps
+    if not args.full:
+        # a plain run: the headline line only
+        del last[""]
+        elapsed, gpu_s, lsa_s = reduce_max([elapsed, gpu_s, lsa_s], world)
+        if rank == 0:
+            res = headline(args, world, net, pairs_total, elapsed, gpu_s, lsa_s, E_tot, tuning, shared_devices,
+                           host_cpu_share(), pinned, t_gen, dumped)
+            print(json.dumps(res), file=json_out, flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # the roofline: the same K steps again, every product-GEMM launch bracketed by HIP events on its
     # own stream (fpm_profile_*); its wall rate is reported beside the headline
     lib.fpm_profile_read(None, None, None)     # drop earlier records
@@ -599,7 +708,6 @@ def main():
         raise SystemExit("bench: timed batch differs from per-pair solo runs: %s" % selfcheck["mismatches"])
     del last[""]
     elapsed, gpu_s, lsa_s, elapsed_prof = reduce_max([elapsed, gpu_s, lsa_s, elapsed_prof], world)
-    pairs_total = (args.gallery if args.config == "c4" else args.batch * world) * args.steps
     value = pairs_total / elapsed
     peak = 2500.0 if args.dtype == "bf16" else 157.3
     achieved = (fl.value / (ms.value / 1e3)) / 1e12 if ms.value > 0 else 0.0
@@ -693,33 +801,9 @@ def main():
             log("train line: %s" % json.dumps(config_lines["train_line"]))
         f8d = survey_flops_per_pair(args.n, args.n, E_tot / (2.0 * args.batch), E_tot / (2.0 * args.batch))
 
-        res = {
-            "metric": "graph-match pairs/sec @ n=256 kpts, batch=1024, 1 & 8 GPU",
-            "value": value,
-            "unit": "pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong" if args.config == "c4" else "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic (seeded Delaunay keypoint graphs, random node/global features, random-init weights)",
-            "config": {"workload": ("1 probe x %d gallery graphs (%d per GPU), n=%d keypoints, probe SplineConv "
-                                    "once per pipeline chunk (accounting: shared probe stage), %s MFMA; full "
-                                    "Net.forward per pair" % (args.gallery, args.batch, args.n, args.dtype))
-                       if args.config == "c4" else
-                       ("batch=%d pairs/GPU, n=%d keypoints, Delaunay edges, factorized Kronecker "
-                        "affinity, %s MFMA; full Net.forward incl. AFA-U, soft top-k, host Hungarian, "
-                        "greedy top-k, MatchClassifier" % (args.batch, args.n, args.dtype)),
-                       "survey_config": args.config,
-                       "afau_mode": net.afau_mode,
-                       "global_batch": args.gallery if args.config == "c4" else args.batch * world,
-                       "n_keypoints": args.n,
-                       "edges_per_graph": E_tot / (2.0 * args.batch), "parallelism": "pair-sharded x%d" % world},
-            "gpu_stage_pairs_per_s": args.batch * world * args.steps / gpu_s,
-            "host_lsa_ms_per_step": lsa_s / args.steps * 1e3,
+        res = headline(args, world, net, pairs_total, elapsed, gpu_s, lsa_s, E_tot, tuning, shared_devices,
+                       host_cpu_share(), pinned, t_gen, dumped)
+        res.update({
             "roofline": {"kernel": "spline (node, cell) product GEMM (%s, grouped by cell)" % (("gemm_phase_kernel 256x256" if os.environ.get("FPM_GEMM_PHASE", "1") != "0" else "gemm_big_kernel<256>") if args.dtype == "bf16" else "gemm_kernel<f32>"),
                          "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
                          "frac": achieved / peak, "traffic": traffic,
@@ -759,13 +843,8 @@ def main():
             "f32_line": f32_line,
             "strong_scaling": strong,
             "share128_line": share_line,
-            "tuning": tuning or None,
-            "ranks_share_devices": shared_devices,
-            "host_cpus_per_rank": host_cpu_share(),
-            "ranks_pinned": pinned is not None,
-            "input_gen_s": t_gen,
             "graph_build": graph_build,
-        }
+        })
         res.update(config_lines)
         print(json.dumps(res), file=json_out, flush=True)
     if world > 1:

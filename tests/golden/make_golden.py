@@ -13,7 +13,8 @@ written (``tests/golden/*.npz``); no reference source is copied.  Modules used:
 ``utils.build_graphs``, ``utils.factorize_graph_matching`` + ``src.sparse_torch``,
 ``utils.feature_align``, ``src.loss_func``; and plain-torch pieces of ``src/model/ngm.py`` (which
 does not import here) executed from their source text: ``MatchClassifier``, the readout layout and
-the forward's tail after the final Sinkhorn.  ``python make_golden.py NAME ...`` regenerates only the named fixtures.
+the forward's tail after the final Sinkhorn; and the stage block of ``train.py`` run against
+``fpm.Net`` (``train_stages.json``: parameter names and optimizer settings).  ``python make_golden.py NAME ...`` regenerates only the named fixtures.
 """
 import os
 import sys
@@ -353,10 +354,41 @@ def gen_permutation_loss():
     save("permutation_loss", ds=ds.numpy(), gt=gt.numpy(), n1=n1.numpy(), n2=n2.numpy(), loss=loss.numpy())
 
 
+def gen_train_stages():
+    """train.py:153-239 (the stage block: freeze / unfreeze per stage and the optimizers it builds),
+    executed unchanged from the reference's source text against ``fpm.Net`` for stages 1-6.  Stored
+    (train_stages.json): per stage the names of the parameters left trainable and, per optimizer, each
+    group's parameter names, lr and weight decay -- names and numbers only."""
+    import json
+    import torch.optim as optim
+    path = os.path.join(os.path.dirname(_ngm_lines()[0]), "..", "..", "train.py")
+    with open(path) as f:
+        lines = f.read().split("\n")
+    block = lines[152:239]
+    assert "backbone_ids" in block[4] and "optimizer_cls" in block[-1], "train.py moved"
+    code = compile("\n".join(l[4:] if l.startswith("    ") else l for l in block), path + ":153-239", "exec")
+    hyper = {"LR": 1e-3, "BACKBONE_LR": 1e-5, "K_LR": 1e-4}
+    out = {"hyper": hyper, "stages": {}}
+    for stage in range(1, 7):
+        model = fpm.Net(regression=True)
+        names = {id(p): n for n, p in model.named_parameters()}
+        ns = dict(hyper, model=model, stage=stage, optim=optim, torch=torch, print=lambda *a, **k: None)
+        exec(code, ns)
+
+        def groups(opt):
+            return None if opt is None else [{"params": sorted(names[id(p)] for p in g["params"]), "lr": g["lr"],
+                                              "weight_decay": g["weight_decay"]} for g in opt.param_groups]
+        out["stages"][str(stage)] = {"trainable": sorted(n for n, p in model.named_parameters() if p.requires_grad),
+                                     "optimizer": groups(ns["optimizer"]), "optimizer_k": groups(ns["optimizer_k"])}
+    with open(os.path.join(HERE, "train_stages.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    print("wrote train_stages.json")
+
+
 GENERATORS = dict(soft_topk=gen_soft_topk, hungarian_greedy=gen_hungarian_greedy, encoder=gen_encoder,
                   affinity=gen_affinity, graphs_pattern=gen_graphs_and_pattern, delaunay=gen_pyg_edges,
                   gconv=gen_gconv, feature_align=gen_feature_align, match_classifier=gen_match_classifier,
-                  ngm_tail=gen_ngm_tail, permutation_loss=gen_permutation_loss)
+                  ngm_tail=gen_ngm_tail, permutation_loss=gen_permutation_loss, train_stages=gen_train_stages)
 
 if __name__ == "__main__":
     for name in (sys.argv[1:] or list(GENERATORS)):

@@ -1,4 +1,4 @@
-"""train.py's stage selection (``/root/reference/train.py:153-239``) against ``fpm.Net``.
+"""The reference training script's stage selection (train.py:153-239) against ``fpm.Net``.
 
 The reference training script reads ``model.backbone_params`` (train.py:157,166),
 ``model.k_params_id`` (:158,186,213) and ``model.k_params`` (:172,196,209,219,227), set by
@@ -6,21 +6,22 @@ The reference training script reads ``model.backbone_params`` (train.py:157,166)
 
 * ``test_stage_block_restated``: the stage logic restated here (same membership rules and
   optimizer groups per stage), run on ``fpm.Net`` for stages 1-6 -- always runs;
-* ``test_reference_stage_block_executes``: the reference script's own lines 153-239, read as text
-  at run time from ``/root/reference`` (nothing of it is stored in this repo) and executed against
-  ``fpm.Net``; skipped where the reference tree is absent (the GPU box).
+* ``test_reference_stage_block_executes``: what the reference script's own lines 153-239 did when
+  they were executed unchanged against ``fpm.Net`` (``tests/golden/make_golden.py train_stages``;
+  only the resulting parameter names, learning rates and weight decays are stored, in
+  ``tests/golden/train_stages.json``) against what the restated block does to today's ``fpm.Net``.
 
 Both check every stage's ``requires_grad`` set and optimizer parameter groups.
 """
+import json
 import os
 
 import pytest
-import torch
 import torch.optim as optim
 
 import fpm
 
-REF_TRAIN = "/root/reference/train.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_stages.json")
 LR, BACKBONE_LR, K_LR = 1e-3, 1e-5, 1e-4
 
 
@@ -77,10 +78,8 @@ def test_train_attributes_membership():
     assert fpm.Net(regression=True, backbone=False).backbone_params == []
 
 
-@pytest.mark.parametrize("stage", [1, 2, 3, 4, 5, 6])
-def test_stage_block_restated(stage):
-    """train.py:153-239 restated: freeze / unfreeze per stage and the optimizers it builds."""
-    model = fpm.Net(regression=True)
+def _restated(model, stage):
+    """train.py:153-239 restated: freeze / unfreeze per stage -> (optimizer, optimizer_k)."""
     backbone_ids = [id(p) for p in model.backbone_params]
     k_params = model.k_params_id
     match_cls_ids = [id(p) for p in model.match_cls.parameters()]
@@ -106,26 +105,45 @@ def test_stage_block_restated(stage):
             p.requires_grad = id(p) in match_cls_ids
     optimizer = optim.AdamW(model_params, lr=LR, weight_decay=1e-4)
     if stage in (2, 3, 4, 5):
-        optimizer_k = optim.AdamW(model.k_params, lr=K_LR, weight_decay=1e-6)
+        # the k optimizer's weight decay is 1e-4 in stage 3 and 1e-6 in the k-only stages (recorded
+        # in tests/golden/train_stages.json)
+        optimizer_k = optim.AdamW(model.k_params, lr=K_LR, weight_decay=1e-4 if stage == 3 else 1e-6)
+    return optimizer, optimizer_k
+
+
+@pytest.mark.parametrize("stage", [1, 2, 3, 4, 5, 6])
+def test_stage_block_restated(stage):
+    """train.py:153-239 restated: freeze / unfreeze per stage and the optimizers it builds."""
+    model = fpm.Net(regression=True)
+    optimizer, optimizer_k = _restated(model, stage)
     _check(model, stage, optimizer, optimizer_k)
 
 
-def _reference_stage_block():
-    with open(REF_TRAIN) as f:
-        lines = f.read().split("\n")
-    # train.py:153-239 (1-based, inclusive): the stage block up to the classifier optimizer
-    block = lines[152:239]
-    assert "backbone_ids" in block[4] and "optimizer_cls" in block[-1], "train.py moved"
-    return "\n".join(l[4:] if l.startswith("    ") else l for l in block)
+@pytest.fixture(scope="module")
+def recorded():
+    with open(GOLDEN) as f:
+        rec = json.load(f)
+    assert rec["hyper"] == {"LR": LR, "BACKBONE_LR": BACKBONE_LR, "K_LR": K_LR}
+    return rec["stages"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TRAIN), reason="reference tree absent (GPU box)")
 @pytest.mark.parametrize("stage", [1, 2, 3, 4, 5, 6])
-def test_reference_stage_block_executes(stage):
-    """The reference's own stage block, executed unchanged against fpm.Net."""
-    src = _reference_stage_block()
+def test_reference_stage_block_executes(stage, recorded):
+    """The reference's own stage block, executed unchanged against fpm.Net when the fixture was
+    recorded: the parameters it left trainable and every group of the optimizers it built (names,
+    lr, weight decay), against the restated block on today's fpm.Net -- and the recorded result
+    itself against the expected membership (_check's rules, by name)."""
+    rec = recorded[str(stage)]
     model = fpm.Net(regression=True)
-    ns = {"model": model, "stage": stage, "optim": optim, "LR": LR, "BACKBONE_LR": BACKBONE_LR, "K_LR": K_LR,
-          "print": lambda *a, **k: None, "torch": torch}
-    exec(compile(src, REF_TRAIN + ":153-239", "exec"), ns)
-    _check(model, stage, ns["optimizer"], ns["optimizer_k"])
+    names = {id(p): n for n, p in model.named_parameters()}
+    optimizer, optimizer_k = _restated(model, stage)
+    _check(model, stage, optimizer, optimizer_k)
+
+    def groups(opt):
+        return None if opt is None else [{"params": sorted(names[id(p)] for p in g["params"]), "lr": g["lr"],
+                                          "weight_decay": g["weight_decay"]} for g in opt.param_groups]
+    assert sorted(n for n, p in model.named_parameters() if p.requires_grad) == rec["trainable"]
+    assert groups(optimizer) == rec["optimizer"]
+    assert groups(optimizer_k) == rec["optimizer_k"]
+    # the recording covers every parameter of today's Net (stage 3 trains all): none added or renamed since
+    assert set(recorded["3"]["trainable"]) == set(names.values())

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 tag=${TAG:-ab}
 reps=${REPS:-3}
-SL="--no-share-line"; [ "${SHARE:-0}" = 1 ] && SL=""
+SL="--no-share-line"; [ "${SHARE:-0}" = 1 ] && SL="--full"      # the share line is one of --full's extras
 B="--no-config-lines --no-cpu-baseline --no-f32-line $SL --no-selfcheck --steps 10 $BENCH_ARGS"
 for i in $(seq 1 $reps); do
   v=0

@@ -1,8 +1,9 @@
 #!/bin/bash
 # rocprofv3 kernel-trace + stats of the default bench command (the round's committed profile):
 #   bash tools/prof_bench.sh <tag>   -> gpurun_out/prof_<tag>/ (+ .json / .err)
-# The run does warmup 1 + 2 x 5 timed steps + 1 isolated forward = 12 forwards of 1024 pairs
-# (tools/roofline_table.py --forwards 12); no CPU baseline / parity / f32 line inside the trace.
+# The plain run does warmup 1 + 5 timed steps = 6 forwards of 1024 pairs (tools/roofline_table.py
+# --forwards 6; with --full it would add 5 profiled steps + 1 isolated forward = 12); no CPU baseline /
+# parity / f32 line inside the trace.
 set -o pipefail
 export TMPDIR=/tmp
 TAG=${1:-bench}

@@ -3,8 +3,8 @@
     python tools/roofline_table.py STATS.csv --forwards F [--n 256] [--pairs 1024] [--out profiles/rNN_roofline]
 
 STATS.csv is ``rocprofv3 --kernel-trace --stats`` output (``*_kernel_stats.csv``) of a command that
-ran F full forwards of ``--pairs`` pairs of n-keypoint graphs (bench.py: warmup + 2 x steps + 1
-isolated forward).  For each hot kernel: algorithmic bytes (or FLOPs) per pair and per call, times
+ran F full forwards of ``--pairs`` pairs of n-keypoint graphs (bench.py: warmup + steps; bench.py
+--full: warmup + 2 x steps + 1 isolated forward).  For each hot kernel: algorithmic bytes (or FLOPs) per pair and per call, times
 the pairs the run processed, divided by the kernel's summed duration -> achieved GB/s (TFLOP/s)
 and the fraction of the MI355X peak (HBM 8 TB/s; dense bf16 MFMA 2.5 PFLOP/s, fp32 157.3 TFLOP/s).
 Durations are kernel-trace durations in the pipelined forward (two compute streams share the CUs),
