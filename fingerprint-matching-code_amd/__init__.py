@@ -22,4 +22,7 @@ def __getattr__(name):
     if name == "DeviceBatch":
         from .batch import DeviceBatch
         return DeviceBatch
+    if name == "GalleryIndex":
+        from .gallery import GalleryIndex
+        return GalleryIndex
     raise AttributeError(name)

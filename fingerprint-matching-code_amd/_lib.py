@@ -43,6 +43,8 @@ SIGNATURES = {
     "fpm_spline_conv_fwd_argmax": (I, [I, P, P, L, L, I, P, P, P, P, L, I, P, P, P, P, P, P]),
     "fpm_edge_diff": (I, [P, P, P, L, I, P, P]),
     "fpm_rows_bcast_scale": (I, [I, P, L, I, P, P, P, I, P]),
+    "fpm_rows_gather_scale": (I, [I, P, P, P, I, I, I, P, P, P, I, P]),
+    "fpm_rank_topk": (I, [P, L, I, I, I, P, P, P]),
     "fpm_edge_diff_padded": (I, [P, P, P, P, P, P, L, I, P, P]),
     "fpm_kron_gnn_layer_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fpm_kron_gnn_layer_fwd_ord": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),

@@ -1440,6 +1440,106 @@ extern "C" int fpm_rows_bcast_scale(int dtype, const float* y, long rows, int B,
     return fpm::check_launch("fpm_rows_bcast_scale");
 }
 
+// Enrolled gallery (1:N identification): the cached fp32 SplineConv output rows of G graphs
+// (concatenated, graph g at rows [row_off[g], row_off[g + 1])) gathered into the padded per-pair
+// layout of a batch: pair b takes graph idx[b]; rows past its n_g are zeros.  The values are those of
+// rows_bcast_scale_kernel (out_f = y, out_t = T(y o coef[b]), the same split patterns); the y * coef
+// product is pinned (__fmul_rn) so that z - hi cannot be contracted into an FMA with it.
+// An HBM-bound copy: a workgroup of 192 threads takes a band of GATHER_BAND rows of one pair, two rows
+// per step, each thread 8 channels (two 16-B loads; 16-B stores, bf16 packed 8 per store).
+namespace {
+constexpr int GATHER_BAND = 16;
+
+template <typename T> struct GatherStore;
+template <> struct GatherStore<float> {
+    static __device__ __forceinline__ void put(float* p, const float (&v)[8]) {
+        *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+        *(float4*)(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    }
+};
+template <> struct GatherStore<bf16_t> {
+    static __device__ __forceinline__ void put(bf16_t* p, const float (&v)[8]) {
+        *(uint4*)p = make_uint4(fpm::f2bf2(v[0], v[1]), fpm::f2bf2(v[2], v[3]), fpm::f2bf2(v[4], v[5]),
+                                fpm::f2bf2(v[6], v[7]));
+    }
+};
+
+template <typename T, int SPLIT>
+__global__ __launch_bounds__(192) void rows_gather_scale_kernel(const float* __restrict__ y,
+                                                                const long* __restrict__ row_off,
+                                                                const int* __restrict__ idx, int G, int nmax,
+                                                                const float* __restrict__ coef,
+                                                                float* __restrict__ out_f, T* __restrict__ out_t) {
+    const int b = blockIdx.y;
+    const int g = idx[b];
+    if (g < 0 || g >= G) return;                       // the wrapper checks the range; never read outside y
+    const long r0 = row_off[g];
+    const long ng_l = row_off[g + 1] - r0;
+    const int ng = ng_l < nmax ? (int)ng_l : nmax;
+    const int sub = threadIdx.x >= 96 ? 1 : 0;         // which of the step's two rows
+    const int c0 = 8 * (threadIdx.x - 96 * sub);       // this thread's 8 channels
+    float cs[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    if (coef && out_t) {
+        const float4 a = *(const float4*)(coef + (long)b * 768 + c0), c = *(const float4*)(coef + (long)b * 768 + c0 + 4);
+        cs[0] = a.x; cs[1] = a.y; cs[2] = a.z; cs[3] = a.w; cs[4] = c.x; cs[5] = c.y; cs[6] = c.z; cs[7] = c.w;
+    }
+    const int band0 = blockIdx.x * GATHER_BAND;
+    constexpr int ldt = SPLIT ? 2304 : 768;
+    for (int s = 0; s < GATHER_BAND; s += 2) {
+        const int r = band0 + s + sub;
+        if (r >= nmax) break;
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (r < ng) {
+            const float* src = y + (r0 + r) * 768 + c0;
+            const float4 a = *(const float4*)src, c = *(const float4*)(src + 4);
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
+        }
+        const long row = (long)b * nmax + r;
+        if (out_f) GatherStore<float>::put(out_f + row * 768 + c0, v);
+        if (!out_t) continue;
+        float z[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z[j] = (coef && r < ng) ? __fmul_rn(v[j], cs[j]) : v[j];   // padding: +0
+        T* o = out_t + row * ldt + c0;
+        if constexpr (SPLIT != 0) {
+            float hi[8], lo[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                hi[j] = fpm::to_f<T>(fpm::from_f<T>(z[j]));
+                lo[j] = z[j] - hi[j];
+            }
+            GatherStore<T>::put(o, hi);
+            GatherStore<T>::put(o + 768, SPLIT == 1 ? lo : hi);
+            GatherStore<T>::put(o + 1536, SPLIT == 1 ? hi : lo);
+        } else {
+            GatherStore<T>::put(o, z);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int fpm_rows_gather_scale(int dtype, const float* y, const long* row_off, const int* idx, int G, int B,
+                                     int nmax, const float* coef, float* out_f, void* out_t, int split,
+                                     void* stream) {
+    FPM_CHECK_ARG(dtype == 0 || dtype == 1, "rows_gather_scale: bad dtype");
+    FPM_CHECK_ARG(split >= 0 && split <= 2 && (split == 0 || dtype == 1), "rows_gather_scale: split needs bf16");
+    FPM_CHECK_ARG(G > 0 && B >= 0 && nmax >= 0 && B <= 65535, "rows_gather_scale: bad sizes (G %d, B %d, nmax %d)", G,
+                  B, nmax);
+    FPM_CHECK_ARG(y && row_off && idx, "rows_gather_scale: y, row_off and idx are required");
+    if (B == 0 || nmax == 0 || (!out_f && !out_t)) return 0;
+    dim3 grid((unsigned)((nmax + GATHER_BAND - 1) / GATHER_BAND), (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+#define FPM_GATHER(T_, S_)                                                                                     \
+    hipLaunchKernelGGL((rows_gather_scale_kernel<T_, S_>), grid, dim3(192), 0, st, y, row_off, idx, G, nmax, coef, \
+                       out_f, (T_*)out_t)
+    if (dtype == 0) FPM_GATHER(float, 0);
+    else if (split == 0) FPM_GATHER(bf16_t, 0);
+    else if (split == 1) FPM_GATHER(bf16_t, 1);
+    else FPM_GATHER(bf16_t, 2);
+#undef FPM_GATHER
+    return fpm::check_launch("fpm_rows_gather_scale");
+}
+
 extern "C" int fpm_profile_enable(int on) {
     g_prof_on = on != 0;
     return 0;

@@ -1,0 +1,315 @@
+"""Enrolled gallery for 1:N identification: templates enrolled once, probes searched many times.
+
+SplineConv is the matcher's per-graph stage: its output rows depend on the graph alone, not on the
+partner graph of a pair (``Net._probe_rows`` uses the same fact for the probe side).  ``Net.enroll``
+runs the two SplineConv layers over the gallery once and keeps the fp32 output rows in a
+``GalleryIndex``; ``Net.identify`` then runs the probe x gallery forward with side 1's operand rows
+gathered from the index (``fpm_rows_gather_scale``) instead of recomputed -- the same values, so
+every output equals ``net.run(DeviceBatch.from_probe_gallery(probe, gallery))`` bit for bit -- and
+ranks the pair scores on the device (``fpm_rank_topk``).
+
+Size of an index: 768 fp32 channels = 3 KB per keypoint (0.39 MB per template at n = 128, 0.4 GB per
+1024 such templates), plus the graph's edges (12 B each, ~6 per keypoint) and 2 KB of global feature.
+"""
+import hashlib
+
+import numpy as np
+import torch
+
+from . import config as C
+from . import ops
+from ._lib import FpmError
+from .batch import DeviceBatch, ORDER_MIN_NMAX, ORDER_ON, hilbert_order
+from .model import _CachedSide
+
+FORMAT = 1
+SCORES = ("cls_prob", "cls_logits", "k_prob")
+
+
+class GalleryIndex:
+    """Data of an enrolled gallery of G graphs (a container; ``Net.enroll`` fills it):
+
+      y         (sum n, 768) fp32   SplineConv output rows, graph g at [row_off[g], row_off[g + 1])
+      row_off   (G + 1,) int64      device; ``row_off_host`` its host copy
+      n         (G,) int32          keypoints per graph (host)
+      src, dst  (sum E,) int32      each graph's edges, graph-local node ids, concatenated (device)
+      pseudo    (sum E, 2) fp32     their pseudo-coordinates (device)
+      edge_off  (G + 1,) int64      edge offsets per graph (host)
+      w         (G, 512) fp32       global features (device)
+      P         (sum n, 2) fp32     keypoints, or None when the graphs carry none (device)
+      sc_mode   "f32" | "bf16"      the SplineConv arithmetic that produced y
+      _pack_gen, weights_id         the enrolling net's weight-pack generation and a digest of its
+                                    SplineConv weights (``Net.identify`` refuses other weights)
+    """
+
+    def __init__(self, y, row_off, n, src, dst, pseudo, edge_off, w, P, sc_mode, pack_gen, weights_id):
+        if sc_mode not in ("f32", "bf16"):
+            raise FpmError("GalleryIndex: sc_mode must be 'f32' or 'bf16'")
+        self.y, self.src, self.dst, self.pseudo, self.w, self.P = y, src, dst, pseudo, w, P
+        self.row_off = row_off
+        self.row_off_host = row_off.cpu()
+        self.n = torch.as_tensor(n, dtype=torch.int32).cpu()
+        self.edge_off = torch.as_tensor(edge_off, dtype=torch.int64).cpu()
+        self.sc_mode = sc_mode
+        self._pack_gen = int(pack_gen)
+        self.weights_id = str(weights_id)
+        self._sel = None            # the last selection's side-1 batch data (_selection)
+        G = self.G
+        if (row_off.dtype != torch.int64 or self.row_off_host.numel() != G + 1 or self.edge_off.numel() != G + 1
+                or int(self.row_off_host[-1]) != y.shape[0] or int(self.edge_off[-1]) != src.numel()
+                or not torch.equal(self.row_off_host[1:] - self.row_off_host[:-1], self.n.long())
+                or tuple(w.shape) != (G, C.GLOBAL_FEATURE_DIM) or y.dtype != torch.float32):
+            raise FpmError("GalleryIndex: inconsistent fields")
+
+    @property
+    def G(self):
+        return int(self.n.numel())
+
+    @property
+    def device(self):
+        return self.y.device
+
+    def nbytes(self):
+        """Device bytes held (3 KB per keypoint of rows, plus edges and global features)."""
+        ts = [self.y, self.row_off, self.src, self.dst, self.pseudo, self.w] + ([] if self.P is None else [self.P])
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def save(self, path):
+        """``torch.save`` of a dict of tensors and scalars (no pickled code objects)."""
+        d = dict(format=FORMAT, y=self.y.cpu(), row_off=self.row_off_host, n=self.n, src=self.src.cpu(),
+                 dst=self.dst.cpu(), pseudo=self.pseudo.cpu(), edge_off=self.edge_off, w=self.w.cpu(),
+                 sc_mode=self.sc_mode, pack_gen=self._pack_gen, weights_id=self.weights_id)
+        if self.P is not None:
+            d["P"] = self.P.cpu()
+        torch.save(d, path)
+
+    @staticmethod
+    def load(path, device):
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if d.get("format") != FORMAT:
+            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d" % (path, FORMAT))
+        mv = lambda k: d[k].to(device)
+        return GalleryIndex(mv("y"), mv("row_off"), d["n"], mv("src"), mv("dst"), mv("pseudo"), d["edge_off"], mv("w"),
+                            mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"])
+
+    def _selection(self, select):
+        """Side 1 of a probe x gallery batch over the entries ``select`` (None: all), in that order,
+        as DeviceBatch.from_pairs lays it out: (sel host int64, dict of batch fields).  Independent
+        of the probe, so the last selection's data is kept for the next query."""
+        G = self.G
+        if select is None:
+            sel = torch.arange(G, dtype=torch.int64)
+        else:
+            sel = torch.as_tensor(select, dtype=torch.int64).view(-1).cpu()
+            if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= G:
+                raise FpmError("identify: select must name entries in [0, %d)" % G)
+        if self._sel is not None and torch.equal(self._sel[0], sel):
+            return self._sel
+        dev = self.device
+        B = int(sel.numel())
+        n2 = self.n[sel]
+        nmax = int(n2.max())
+        cnt = self.edge_off[sel + 1] - self.edge_off[sel]
+        eo = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
+        E = int(eo[-1])
+        cnt_d = cnt.to(dev)
+        pair = torch.repeat_interleave(torch.arange(B, device=dev), cnt_d, output_size=E)
+        pos = torch.arange(E, device=dev) + (self.edge_off[sel] - eo[:-1]).to(dev)[pair]
+        shift = (pair * nmax).to(torch.int32)
+        sel_d = sel.to(dev)
+        f = dict(n=n2, nmax=nmax, edge_off=eo, src=(self.src[pos] + shift).contiguous(),
+                 dst=(self.dst[pos] + shift).contiguous(), pseudo=self.pseudo[pos].contiguous(),
+                 w=self.w[sel_d].contiguous(), idx=sel_d.to(torch.int32).contiguous(), idx_host=sel.to(torch.int32),
+                 ord2=None)
+        if ORDER_ON and nmax > ORDER_MIN_NMAX and self.P is not None:
+            rows = torch.repeat_interleave(torch.arange(B, device=dev), n2.to(dev).long(), output_size=int(n2.sum()))
+            first = torch.cat([torch.zeros(1, dtype=torch.int64), n2.long().cumsum(0)[:-1]]).to(dev)
+            loc = torch.arange(rows.numel(), device=dev) - first[rows]
+            P2 = torch.zeros(B, nmax, 2, device=dev, dtype=torch.float32)
+            P2[rows, loc] = self.P[loc + self.row_off[sel_d][rows]]
+            f["ord2"] = hilbert_order(P2, n2, nmax)
+        self._sel = (sel, f)
+        return self._sel
+
+
+class _GalleryBatch(DeviceBatch):
+    """A probe x gallery batch whose side 1 lives in a GalleryIndex: laid out like
+    ``DeviceBatch.from_probe_gallery`` (shared side 0), except that no node features are staged:
+    x[0] is the probe's rows once (every sub-batch sees the same rows), x[1] is empty, and ``cached``
+    (model._CachedSide) names the index rows of each pair.  ``sc_mode``: the index's SplineConv
+    arithmetic, which the forward follows (Net._sc_f32)."""
+
+    def split_range(self, b0, b1):
+        if not 0 <= b0 < b1 <= self.B:
+            raise ValueError("split_range: bad pair range [%d, %d) of %d" % (b0, b1, self.B))
+        ws, ss, ds, ps = [], [], [], []
+        for side in range(2):
+            nm = self.nmax[side]
+            e0, e1 = int(self.edge_off[side][b0]), int(self.edge_off[side][b1])
+            ws.append(self.w[side][b0:b1])
+            ss.append((self.src[side][e0:e1] - b0 * nm).contiguous())
+            ds.append((self.dst[side][e0:e1] - b0 * nm).contiguous())
+            ps.append(self.pseudo[side][e0:e1])
+        eo = [self.edge_off[side][b0:b1 + 1] - self.edge_off[side][b0] for side in range(2)]
+        sub = _GalleryBatch(b1 - b0, self.n_host[0][b0:b1], self.n_host[1][b0:b1], list(self.x), ws, ss, ds, ps,
+                            self.device, nmax=self.nmax, edge_off=eo, shared0=True)
+        sub.pair_range = (b0, b1)
+        sub.ord2 = None if self.ord2 is None else self.ord2[b0:b1]
+        sub.cached = self.cached.slice(b0, b1)
+        sub.sc_mode = self.sc_mode
+        return sub
+
+    def to(self, device, non_blocking=True):
+        if torch.device(device) != self.device:
+            raise FpmError("a gallery batch stays on its index's device")
+        return self
+
+
+def _graph_side(graphs, dev):
+    """One side's padded batch tensors of a list of graph dicts (as DeviceBatch.from_pairs stages
+    them) -> (n host int32, nmax, x, src, dst, pseudo, edge counts)."""
+    B = len(graphs)
+    n = np.array([g["n"] for g in graphs], dtype=np.int32)
+    nmax = int(n.max())
+    X = np.zeros((B, nmax, C.NODE_FEATURE_DIM), np.float32)
+    s_l, d_l, p_l = [], [], []
+    for b, g in enumerate(graphs):
+        X[b, :g["n"]] = g["x"]
+        ei = np.asarray(g["edge_index"])
+        s_l.append(ei[0] + b * nmax)
+        d_l.append(ei[1] + b * nmax)
+        p_l.append(np.asarray(g["pseudo"], dtype=np.float32).reshape(-1, 2))
+    cnt = np.array([len(s) for s in s_l], dtype=np.int64)
+    to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(dev)
+    return (torch.from_numpy(n), nmax, to(X.reshape(B * nmax, -1), np.float32), to(np.concatenate(s_l), np.int32),
+            to(np.concatenate(d_l), np.int32), to(np.concatenate(p_l), np.float32), cnt)
+
+
+def spline_weights_id(net):
+    """Digest of the SplineConv parameters (the weights an index's rows depend on); kept per weight
+    version, so a repeated query does not hash again."""
+    key = tuple(p._version for p in net.parameters())
+    cached = getattr(net, "_sc_weights_id", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    from . import params as P
+    h = hashlib.blake2b(digest_size=16)
+    sd = net.state_dict()
+    for name in sorted(k for k in sd if k.startswith(P.SPLINE_PREFIX + ".")):
+        h.update(name.encode())
+        h.update(sd[name].detach().to("cpu", torch.float32).contiguous().numpy().tobytes())
+    net._sc_weights_id = (key, h.hexdigest())
+    return net._sc_weights_id[1]
+
+
+def enroll(net, graphs, device, sc_mode=None, batch=256):
+    """``Net.enroll``: the two SplineConv layers over ``graphs`` (dicts as ``fpm.synth.make_graph``
+    returns: n, x, w, edge_index, pseudo, optionally P) in sub-batches of ``batch`` graphs -> GalleryIndex."""
+    if net.training:
+        raise FpmError("enroll: inference only (call net.eval())")
+    dev = torch.device(device)
+    sc_mode = sc_mode or ("f32" if net.dtype_mode == "f32" else "bf16")
+    if sc_mode not in ("f32", "bf16") or (sc_mode == "bf16" and net.dtype_mode != "bf16"):
+        raise FpmError("enroll: sc_mode must be 'f32', or 'bf16' on a dtype='bf16' net")
+    graphs = list(graphs)
+    if not graphs:
+        raise FpmError("enroll: empty gallery")
+    wp = net.packed(dev)
+    f32 = sc_mode == "f32"
+    W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
+    code = ops.F32 if f32 else ops.BF16
+    ys, srcs, dsts, pss, cnts = [], [], [], [], []
+    with torch.cuda.device(dev):
+        for g0 in range(0, len(graphs), max(1, int(batch))):
+            sub = graphs[g0:g0 + max(1, int(batch))]
+            n, nmax, x0, src, dst, ps, cnt = _graph_side(sub, dev)
+            Bs, nn_, E = len(sub), len(sub) * nmax, int(src.numel())
+            nv = n.to(dev)
+            plan = ops.spline_plan(src, dst, ps, nn_, nmax, int(cnt.max()))
+            x_op = x0 if f32 else ops.cast_bf16(x0)
+            yws = ops.spline_y_ws(code, E, nn_, dev)
+            h = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=x_op.dtype)
+            ops.spline_conv(x_op, plan, E, nn_, nmax, nv, W0, wp["bias0"], yws, 0, out_t=h)
+            y = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
+            ops.spline_conv(h, plan, E, nn_, nmax, nv, W1, wp["bias1"], yws, 1, xres=x0, out_f=y)
+            # padded -> ragged rows, edges back to graph-local ids (off the hot path: torch indexing)
+            keep = (torch.arange(nmax, device=dev)[None, :] < nv.view(-1, 1)).reshape(-1)
+            ys.append(y[keep])
+            shift = torch.repeat_interleave(torch.arange(Bs, device=dev) * nmax, torch.from_numpy(cnt).to(dev),
+                                            output_size=E).to(torch.int32)
+            srcs.append(src - shift)
+            dsts.append(dst - shift)
+            pss.append(ps)
+            cnts.append(cnt)
+    n_all = torch.tensor([int(g["n"]) for g in graphs], dtype=torch.int32)
+    row_off = torch.cat([torch.zeros(1, dtype=torch.int64), n_all.long().cumsum(0)])
+    edge_off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.from_numpy(np.concatenate(cnts)).cumsum(0)])
+    w = torch.from_numpy(np.stack([np.asarray(g["w"], dtype=np.float32) for g in graphs])).to(dev)
+    P = None
+    if all("P" in g for g in graphs):
+        P = torch.from_numpy(np.concatenate([np.asarray(g["P"], dtype=np.float32).reshape(-1, 2) for g in graphs])).to(dev)
+    return GalleryIndex(torch.cat(ys), row_off.to(dev), n_all, torch.cat(srcs), torch.cat(dsts), torch.cat(pss),
+                        edge_off, w, P, sc_mode, net._pack_gen, spline_weights_id(net))
+
+
+def probe_batch(probe, index, select=None):
+    """The probe x gallery batch of one probe graph over ``index`` -> (_GalleryBatch, sel host int64)."""
+    dev = index.device
+    sel, f = index._selection(select)
+    B, n0 = int(sel.numel()), int(probe["n"])
+    x0 = torch.from_numpy(np.ascontiguousarray(np.asarray(probe["x"], dtype=np.float32))).to(dev)
+    ei = torch.from_numpy(np.asarray(probe["edge_index"]).astype(np.int32)).to(dev)
+    ps = torch.from_numpy(np.asarray(probe["pseudo"], dtype=np.float32).reshape(-1, 2)).to(dev)
+    e0 = int(ei.shape[1])
+    shift = (torch.arange(B, device=dev, dtype=torch.int32) * n0).view(B, 1)
+    src0 = (ei[0].view(1, e0) + shift).reshape(-1).contiguous()
+    dst0 = (ei[1].view(1, e0) + shift).reshape(-1).contiguous()
+    ps0 = ps.view(1, e0, 2).expand(B, e0, 2).reshape(-1, 2).contiguous()
+    w0 = torch.from_numpy(np.asarray(probe["w"], dtype=np.float32)).to(dev).view(1, -1).expand(B, -1).contiguous()
+    eo0 = torch.arange(B + 1, dtype=torch.int64) * e0
+    bt = _GalleryBatch(B, np.full(B, n0, np.int32), f["n"], [x0, x0.new_empty(0, C.NODE_FEATURE_DIM)], [w0, f["w"]],
+                       [src0, f["src"]], [dst0, f["dst"]], [ps0, f["pseudo"]], dev, nmax=[n0, f["nmax"]],
+                       edge_off=[eo0, f["edge_off"]], shared0=True)
+    bt.cached = _CachedSide(index.y, index.row_off, index.row_off_host, f["idx"], f["idx_host"])
+    bt.sc_mode = index.sc_mode
+    bt.ord2 = f["ord2"]
+    return bt, sel
+
+
+def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None):
+    """``Net.identify``: see there."""
+    if net.training:
+        raise FpmError("identify: inference only (call net.eval()); training through an index is not supported")
+    if net.use_graphs:
+        raise FpmError("identify: cached-gallery forwards are eager; switch HIP-graph replay (use_graphs) off")
+    if score not in SCORES:
+        raise FpmError("identify: score must be one of %s" % (SCORES,))
+    if not isinstance(index, GalleryIndex):
+        raise FpmError("identify: index must be a GalleryIndex (Net.enroll)")
+    if index.sc_mode == "bf16" and net.dtype_mode != "bf16":
+        raise FpmError("identify: the index holds bf16-SplineConv rows, the net runs fp32")
+    net.packed(index.device)
+    if index.weights_id != spline_weights_id(net):
+        raise FpmError("identify: the index was enrolled with other SplineConv weights (pack generation %d, net's %d); "
+                       "enroll the gallery again" % (index._pack_gen, net._pack_gen))
+    single = isinstance(probes, dict)
+    plist = [probes] if single else list(probes)
+    outs, sel = [], None
+    keep = net.prologue_graph
+    net.prologue_graph = 0                  # eager prologue: no capture per query batch
+    try:
+        with torch.cuda.device(index.device):
+            for p in plist:
+                bt, sel = probe_batch(p, index, select)
+                outs.append(net.run(bt, chunks=chunks))
+            if outs:
+                k = max(1, min(int(topk), int(sel.numel()), 128))
+                sc = torch.stack([o[score].view(-1) for o in outs])
+                ti, ts = ops.rank_topk(sc, k)
+                sel_d = index._sel[1]["idx"]
+                ti = sel_d[ti.long()]
+                for i, o in enumerate(outs):
+                    o["top_idx"], o["top_score"] = ti[i], ts[i]
+    finally:
+        net.prologue_graph = keep
+    return outs[0] if single else outs

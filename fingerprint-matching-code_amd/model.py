@@ -93,6 +93,19 @@ class _SharedProbe:
         self.y = y
 
 
+class _CachedSide:
+    """Enrolled gallery (fpm.gallery): side 1's SplineConv output comes from an index's cached rows.
+    ``y`` / ``row_off``: the index's fp32 rows and graph row offsets (device; ``row_off_host`` its host
+    copy); ``idx`` (device int32) / ``idx_host``: the gallery entry of each pair of the (sub-)batch.
+    Handed to _spline_side as side 1's x_op; a pipeline chunk slices idx, never rows."""
+
+    def __init__(self, y, row_off, row_off_host, idx, idx_host):
+        self.y, self.row_off, self.row_off_host, self.idx, self.idx_host = y, row_off, row_off_host, idx, idx_host
+
+    def slice(self, b0, b1):
+        return _CachedSide(self.y, self.row_off, self.row_off_host, self.idx[b0:b1], self.idx_host[b0:b1])
+
+
 class _TailView:
     """Pairs [r0, r1) of a (sub-)batch ``part`` for the tail stages (AFA-U, soft top-k, Hungarian,
     selection, classifier): device views of the pair sizes, no copies; ``pair_range`` is its range in
@@ -411,6 +424,15 @@ class Net(nn.Module):
                                    bt.max_graph_edges(side))
         if side == 0 and bt.shared0 and bt.B > 1:
             return (plan,) + self._spline_shared(wp, bt, cscale, probe=x_op if isinstance(x_op, _SharedProbe) else None)
+        if isinstance(x_op, _CachedSide):
+            # enrolled gallery: no SplineConv here, the cached rows gathered into the padded box (the
+            # plan above still serves the GNN layers' dst CSR)
+            split = self._kp_split(side, bt)
+            out = torch.empty(nn_, 3 * C.NODE_FEATURE_DIM if split else C.NODE_FEATURE_DIM, device=dev, dtype=op)
+            outf = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32) if self._keep_feats else None
+            ops.rows_gather_scale(x_op.y, x_op.row_off, x_op.idx, bt.nmax[side], coef=cscale, out_f=outf, out_t=out,
+                                  split=split, idx_host=x_op.idx_host, row_off_host=x_op.row_off_host)
+            return plan, out, outf
         if isinstance(x_op, _SharedProbe):          # a one-pair chunk of a probe x gallery batch
             x_op = None
         x0 = bt.x[side]
@@ -430,7 +452,11 @@ class Net(nn.Module):
 
     def _sc_f32(self, bt):
         """SplineConv products (and the vertex affinity) in fp32 for this batch: the fp32 mode, and the
-        bf16 mode on batches whose padded box is at most ``sc_f32_nmax`` keypoints."""
+        bf16 mode on batches whose padded box is at most ``sc_f32_nmax`` keypoints.  A batch over an
+        enrolled gallery follows the arithmetic that produced the cached rows (``sc_mode``), so both
+        affinity operands share a dtype."""
+        if getattr(bt, "sc_mode", None) is not None:
+            return bt.sc_mode == "f32"
         return self.dtype_mode != "bf16" or max(bt.nmax) <= self.sc_f32_nmax
 
     def _k_f64(self, bt):
@@ -861,6 +887,8 @@ class Net(nn.Module):
         dev = part.device
         x_ops = tuple(None if t is None else t if isinstance(t, _SharedProbe) else t[b0 * part.nmax[s]:b1 * part.nmax[s]]
                       for s, t in enumerate(xop or (None, None)))
+        if getattr(part, "cached", None) is not None:
+            x_ops = (x_ops[0], part.cached)        # this chunk's slice of the gallery selection
         r = self.run_gpu_stage(part, keep_feats, s_out=o["s"][b0:b1], ss_out=o["ss"][b0:b1],
                                gc=(gc[0][b0:b1], gc[1][b0:b1]), x_ops=x_ops, plans=plans,
                                ss64_out=o["ss64"][b0:b1] if "ss64" in o else None)
@@ -996,7 +1024,8 @@ class Net(nn.Module):
         def side_work():
             xop_ = None
             if not self._sc_f32(bt) and cast:
-                xop_ = tuple(None if (s == 0 and bt.shared0) else ops.cast_bf16(bt.x[s]) for s in range(2))
+                xop_ = tuple(None if ((s == 0 and bt.shared0) or (s == 1 and getattr(bt, "cached", None) is not None))
+                             else ops.cast_bf16(bt.x[s]) for s in range(2))
                 if bt.shared0 and bt.B > 1:
                     # the probe's SplineConv once per forward, not once per chunk
                     xop_ = (_SharedProbe(self._probe_rows(self.packed(dev), bt)), xop_[1])
@@ -1428,6 +1457,30 @@ class Net(nn.Module):
                                 enqueue_s=t_enq - t0, enqueue_cpu_s=t_enqc - t0c, total_s=time.perf_counter() - t0,
                                 chunk_timeline_ms=timeline)
         return res
+
+    def enroll(self, graphs, device, sc_mode=None, batch=256):
+        """Enrol a gallery for 1:N identification (inference only): run the two SplineConv layers over
+        ``graphs`` (dicts as ``fpm.synth.make_graph`` returns) once, in sub-batches of ``batch``, and
+        keep their fp32 output rows -> ``fpm.gallery.GalleryIndex`` (3 KB per keypoint).  ``sc_mode``:
+        the SplineConv arithmetic, "f32" or "bf16"; default "f32" for dtype="f32" nets, "bf16"
+        otherwise.  A forward over the index uses the same arithmetic for the probe (``_sc_f32``), so
+        a bf16 net that is to match its own small-box forwards (fp32 SplineConv on boxes of at most
+        ``sc_f32_nmax`` keypoints) enrols with sc_mode="f32"."""
+        from . import gallery
+        return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch)
+
+    def identify(self, probes, index, topk=10, select=None, score="cls_prob", chunks=None):
+        """1:N identification against an enrolled gallery: for each probe graph (one dict, or a list)
+        the shared-probe forward over the gallery entries ``select`` (an index list; default all),
+        with side 1's operand rows gathered from ``index`` (no SplineConv for the gallery side) --
+        every output equals ``run(DeviceBatch.from_probe_gallery(probe, [gallery[i] for i in select]))``
+        bit for bit.  Returns per probe the output dict of ``run`` plus ``top_idx`` (int32, gallery
+        entry numbers) / ``top_score``: the ``topk`` best pairs by ``score`` ("cls_prob",
+        "cls_logits" or "k_prob"), ranked on the device (``ops.rank_topk``).  Raises FpmError when the
+        index was enrolled with other SplineConv weights, in training mode, or with HIP-graph replay
+        (``use_graphs``) on: forwards over an index are eager."""
+        from . import gallery
+        return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks)
 
     def image_features(self, images, Ps, ns, dev=None):
         """ngm.py:226-248 on the device: per side, node_layers/edge_layers (ResNet-18 convolutions

@@ -2,7 +2,8 @@
 
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
-no CPU fallback: a CPU tensor or a missing library raises.
+no CPU fallback: a CPU tensor or a missing library raises (``rank_topk`` alone keeps a plain-torch
+host path for CPU tensors, the statement of its ordering).
 """
 import ctypes
 
@@ -312,6 +313,105 @@ def rows_bcast_scale(y, B, coef=None, out_f=None, out_t=None, split=0):
     code = _code(out_t) if out_t is not None else F32
     _lib.call("fpm_rows_bcast_scale", code, _p(y), y.shape[0], int(B), _p(coef), _p(out_f), _p(out_t), int(split),
               _stream(y))
+
+
+def rows_gather_scale(y, row_off, idx, nmax, coef=None, out_f=None, out_t=None, split=0, idx_host=None,
+                      row_off_host=None):
+    """Cached SplineConv rows of an enrolled gallery -> a batch's padded operand rows
+    (fpm_rows_gather_scale): y (sum n_g, 768) fp32, graph g at rows [row_off[g], row_off[g + 1])
+    (row_off int64 [G + 1]); pair b takes graph idx[b] (int32 [B]) into rows [b * nmax, (b + 1) * nmax)
+    of out_f (fp32 copies) and out_t (scaled by coef[b]; ``split`` as rows_bcast_scale), zeros past n_g.
+
+    Checked on the host before anything is launched: dtype, contiguity and device of idx / row_off,
+    every idx value in [0, G), every selected n_g <= nmax.  ``idx_host`` / ``row_off_host``: host
+    copies of the two (a caller that built them on the host passes them, and the check needs no
+    device synchronisation; without them the device tensors are copied back)."""
+    for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise _lib.FpmError("rows_gather_scale: %s must be a %s tensor (got %s)"
+                                % (name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise _lib.FpmError("rows_gather_scale: %s must be a contiguous 1-d tensor" % name)
+        if t.device != y.device:
+            raise _lib.FpmError("rows_gather_scale: %s is on %s, y on %s" % (name, t.device, y.device))
+    if y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != 768 or not y.is_contiguous():
+        raise _lib.FpmError("rows_gather_scale: y must be contiguous fp32 rows of 768 channels")
+    G, B, nmax = int(row_off.numel()) - 1, int(idx.numel()), int(nmax)
+    if G < 1 or nmax < 0:
+        raise _lib.FpmError("rows_gather_scale: empty gallery or negative nmax")
+    ih = torch.as_tensor(idx_host if idx_host is not None else idx.cpu()).view(-1).long()
+    oh = torch.as_tensor(row_off_host if row_off_host is not None else row_off.cpu()).view(-1).long()
+    if ih.numel() != B or oh.numel() != G + 1:
+        raise _lib.FpmError("rows_gather_scale: host copies of idx / row_off do not match the device tensors")
+    if int(oh[0]) != 0 or int(oh[-1]) != y.shape[0] or bool((oh[1:] < oh[:-1]).any()):
+        raise _lib.FpmError("rows_gather_scale: row_off must rise from 0 to the %d rows of y" % y.shape[0])
+    if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
+        raise _lib.FpmError("rows_gather_scale: idx value outside [0, %d)" % G)
+    if B and int((oh[ih + 1] - oh[ih]).max()) > nmax:
+        raise _lib.FpmError("rows_gather_scale: a selected graph has n_g = %d > nmax = %d"
+                            % (int((oh[ih + 1] - oh[ih]).max()), nmax))
+    if split not in (0, 1, 2):
+        raise _lib.FpmError("rows_gather_scale: split must be 0, 1 or 2")
+    _shape(coef, (B, 768), "rows_gather_scale coef")
+    _shape(out_f, (B * nmax, 768), "rows_gather_scale out_f")
+    _shape(out_t, (B * nmax, 2304 if split else 768), "rows_gather_scale out_t")
+    for t in (coef, out_f):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.FpmError("rows_gather_scale: coef / out_f must be contiguous fp32")
+    if out_t is not None and not out_t.is_contiguous():
+        raise _lib.FpmError("rows_gather_scale: out_t must be contiguous")
+    _dev(y, row_off, idx, coef, out_f, out_t)
+    code = _code(out_t) if out_t is not None else F32
+    if split and code != BF16:
+        raise _lib.FpmError("rows_gather_scale: split rows need a bf16 out_t")
+    _lib.call("fpm_rows_gather_scale", code, _p(y), _p(row_off), _p(idx), G, B, nmax, _p(coef), _p(out_f), _p(out_t),
+              int(split), _stream(y))
+
+
+def rank_key(scores):
+    """The 64-bit ranking key of fpm_rank_topk for a (P, G) fp32 tensor, as int64 whose signed order
+    is the key's unsigned order shifted by 2^63: (order-preserving bits of the score) << 32 |
+    (0xFFFFFFFF - index); NaN maps below -inf, -0 below +0."""
+    s = scores.detach().to(torch.float32)
+    u = s.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    neg = u >= 0x80000000
+    bits = torch.where(neg, 0xFFFFFFFF - u, u + 0x80000000)
+    bits = torch.where(torch.isnan(s), torch.zeros_like(bits), bits)
+    i = torch.arange(s.shape[-1], device=s.device, dtype=torch.int64).expand_as(bits)
+    return ((bits - 0x80000000) << 32) | (0xFFFFFFFF - i)
+
+
+def rank_topk(scores, k, top_idx=None, top_score=None):
+    """Per-row top-k of scores (P, G) fp32 (any row stride) -> (top_idx (P, k) int32, top_score (P, k)
+    fp32): descending score, ties to the lower index, NaN after every number (NaNs by index).
+    Device tensors run fpm_rank_topk; CPU tensors take the host path below (a stable sort on the same
+    key), which states the semantics."""
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise _lib.FpmError("rank_topk: scores must be a (P, G) fp32 tensor")
+    P, G = int(scores.shape[0]), int(scores.shape[1])
+    k = int(k)
+    if not 1 <= k <= min(G, 128):
+        raise _lib.FpmError("rank_topk: k = %d outside [1, min(G, 128) = %d]" % (k, min(G, 128)))
+    if not scores.is_cuda:
+        order = torch.argsort(rank_key(scores), dim=1, descending=True, stable=True)[:, :k]
+        return order.to(torch.int32), torch.gather(scores, 1, order)
+    if G > 1 and scores.stride(1) != 1:
+        scores = scores.contiguous()
+    ld = int(scores.stride(0)) if P > 1 else G
+    if ld < G:
+        scores, ld = scores.contiguous(), G
+    if top_idx is None:
+        top_idx = torch.empty(P, k, device=scores.device, dtype=torch.int32)
+    if top_score is None:
+        top_score = torch.empty(P, k, device=scores.device, dtype=torch.float32)
+    _shape(top_idx, (P, k), "rank_topk top_idx")
+    _shape(top_score, (P, k), "rank_topk top_score")
+    if top_idx.dtype != torch.int32 or top_score.dtype != torch.float32 or not top_idx.is_contiguous() \
+            or not top_score.is_contiguous():
+        raise _lib.FpmError("rank_topk: top_idx must be contiguous int32, top_score contiguous fp32")
+    _dev(top_idx, top_score)
+    _lib.call("fpm_rank_topk", _p(scores), ld, P, G, k, _p(top_idx), _p(top_score), _stream(scores))
+    return top_idx, top_score
 
 
 def edge_diff(x, src, dst):

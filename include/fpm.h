@@ -230,6 +230,15 @@ int fpm_spline_conv_fwd_argmax(int dtype, const void* x_op, const void* plan_ws,
  * per-pair path's fused epilogue writes; split (bf16 only) as fpm_spline_conv_fwd's mode >> 1. */
 int fpm_rows_bcast_scale(int dtype, const float* y, long rows, int B, const float* coef, float* out_f, void* out_t,
                          int split, void* stream);
+/* enrolled gallery (1:N identification): gather cached fp32 SplineConv rows into a batch's padded
+ * layout.  y: rows of G graphs concatenated, graph g at rows [row_off[g], row_off[g+1]) (row_off:
+ * int64 [G+1]); idx: int32 [B], the graph of each pair (0 <= idx[b] < G, n_g <= nmax: the caller
+ * checks both).  For r < n_g: out_f[b*nmax + r] = y[row_off[g] + r], out_t[b*nmax + r] =
+ * dtype(y[row_off[g] + r] o coef[b]); rows n_g <= r < nmax are zeros.  coef (B x 768), out_f and
+ * out_t may be NULL; split as fpm_rows_bcast_scale, whose values it reproduces bit for bit when
+ * G = 1 and n_0 = nmax.  B <= 65535. */
+int fpm_rows_gather_scale(int dtype, const float* y, const long* row_off, const int* idx, int G, int B, int nmax,
+                          const float* coef, float* out_f, void* out_t, int split, void* stream);
 /* vertex_attr_to_edge_attr (spline_conv.py:73-81): out[e] = x[src[e]] - x[dst[e]] */
 int fpm_edge_diff(const float* x, const int* src, const int* dst, long E, int D, float* out, void* stream);
 /* same, written into a padded per-pair layout and scaled: out[row[e]] = (x[src]-x[dst]) o c[pair[e]]
@@ -484,6 +493,13 @@ int fpm_feature_align_bwd(const float* nodes, const long* node_shape, const long
                           float ori_w, float ori_h, const float* ws, const float* dX, long ldx, const float* dwglob,
                           float* dnodes, const long* dnode_stride, float* dedges, const long* dedge_stride,
                           void* stream);
+
+/* ---- ranking (1:N identification) ---------------------------------------------------------------
+ * For every row p of scores (P rows of G fp32 values, row stride ld elements) the k best entries,
+ * k <= min(G, 128): top_idx[p][0..k) (int32) and top_score[p][0..k) in descending score order; equal
+ * scores go to the lower index; NaN ranks after every number (NaNs among themselves by index); -0
+ * ranks below +0.  No reference counterpart (the reference scores one pair at a time). */
+int fpm_rank_topk(const float* scores, long ld, int P, int G, int k, int* top_idx, float* top_score, void* stream);
 
 /* ---- profiling hooks: HIP-event timing of the dominant kernel (edge-message GEMM) ------------ */
 int fpm_profile_enable(int on);

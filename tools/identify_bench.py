@@ -1,0 +1,166 @@
+"""1:N identification: the cached-gallery forward (``Net.identify`` over an enrolled
+``GalleryIndex``) against the uncached probe x gallery forward (``Net.run`` over
+``DeviceBatch.from_probe_gallery``) on the same graphs.  GPU.
+
+    python tools/identify_bench.py [--gallery 1024] [--n 128] [--reps 7] [--out profiles/identify_c4.json]
+
+Shape: config C4 (one probe, n = 128 keypoints, a gallery of 1024), both dtypes.  Per dtype, in a
+fresh child process under its own time limit: one warm-up, then ``--reps`` (>= 5) timed forwards of
+each path, HIP events around each forward (the forward ends with its host Hungarian, so the events
+bracket the whole forward); medians and the spread are reported.  ``identify`` is timed as a query
+is served -- it stages the probe, gathers, runs the forward and ranks; the uncached ``run`` is timed
+on a batch staged beforehand (``from_probe_gallery``'s staging is not timed).  Then, outside the timed
+runs: the per-stage marks of a one-chunk, one-stream forward of both paths (``Net._mark`` events) and
+the gather kernel alone (achieved GB/s).  The parent writes one JSON file; a failing child ends the
+run (nothing else is started on the GPU after it).
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def _timed(fn, reps):
+    """[(GPU ms between events around fn, wall ms)] of ``reps`` calls."""
+    import time
+    import torch
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t = time.perf_counter()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append((e0.elapsed_time(e1), (time.perf_counter() - t) * 1e3))
+    return out
+
+
+def _summary(samples, pairs):
+    ev = sorted(s[0] for s in samples)
+    med = statistics.median(ev)
+    return dict(event_ms=[round(x, 3) for x in ev], median_ms=round(med, 3), min_ms=round(ev[0], 3),
+                max_ms=round(ev[-1], 3), wall_median_ms=round(statistics.median(s[1] for s in samples), 3),
+                pairs_per_s=round(pairs / med * 1e3, 1))
+
+
+def _marks(net, fn, reps=3):
+    """Mean GPU ms between consecutive stage marks of a one-chunk, one-stream forward."""
+    import collections
+    keep = (net._stage_events, net.tail_streams, net.tail_groups)
+    net._stage_events, net.tail_streams, net.tail_groups = True, 1, 1
+    try:
+        fn()
+        net.stage_events()
+        acc = collections.OrderedDict()
+        for _ in range(reps):
+            fn()
+            for name, ms in net.stage_events():
+                acc[name] = acc.get(name, 0.0) + ms / reps
+    finally:
+        net._stage_events, net.tail_streams, net.tail_groups = keep
+        net._ev_marks = []
+    return {k: round(v, 3) for k, v in acc.items()}
+
+
+def child(args):
+    import time
+    import torch
+    import bench
+    import fpm
+    from fpm import ops, params, synth
+    from fpm.batch import DeviceBatch
+    dev = torch.device("cuda", 0)
+    G, n, dtype = args.gallery, args.n, args.child
+    probe = synth.make_graph(args.seed, 0, 0, n)
+    gallery = bench.make_gallery(args.seed, 1, G, n, args.gen_workers)
+    net = fpm.Net(regression=True, backbone=False, dtype=dtype)
+    net.load_state_dict(params.init_params(args.seed))
+    t = time.perf_counter()
+    index = net.enroll(gallery, dev)
+    torch.cuda.synchronize()
+    enroll_s = time.perf_counter() - t
+    bt = DeviceBatch.from_probe_gallery(probe, gallery, dev)
+    del gallery
+    res = dict(dtype=dtype, gallery=G, n=n, sc_mode=index.sc_mode, reps=args.reps, enroll_s=round(enroll_s, 3),
+               index_mb=round(index.nbytes() / 2 ** 20, 1), chunks=net.pipeline_chunks(G))
+    ref = net.run(bt)                                   # the warm-up of each path, compared
+    out = net.identify(probe, index, topk=10)
+    torch.cuda.synchronize()
+    res["identical"] = all(bool(torch.equal(out[k], ref[k])) for k in ("ss", "ds_mat", "perm_mat", "k_prob", "cls_prob"))
+    res["top_idx"] = out["top_idx"].tolist()
+    del ref, out
+    unc = _timed(lambda: net.run(bt), args.reps)
+    cac = _timed(lambda: net.identify(probe, index, topk=10), args.reps)
+    res["uncached"], res["cached"] = _summary(unc, G), _summary(cac, G)
+    res["speedup_median"] = round(res["uncached"]["median_ms"] / res["cached"]["median_ms"], 3)
+    # faster by more than the spread: the slowest cached forward beats the fastest uncached one
+    res["cached_faster_beyond_spread"] = res["cached"]["max_ms"] < res["uncached"]["min_ms"]
+    res["marks_uncached_ms"] = _marks(net, lambda: net.run(bt, chunks=1))
+    res["marks_cached_ms"] = _marks(net, lambda: net.identify(probe, index, topk=10, chunks=1))
+    # the gather kernel alone, in the shape of side 1 of this forward
+    split = net._kp_split(1, bt)
+    opdt = torch.float32 if index.sc_mode == "f32" else torch.bfloat16
+    cols = 2304 if split else 768
+    out_t = torch.empty(G * n, cols, device=dev, dtype=opdt)
+    idx = torch.arange(G, dtype=torch.int32, device=dev)
+    call = lambda: ops.rows_gather_scale(index.y, index.row_off, idx, n, out_t=out_t, split=split,
+                                         idx_host=idx.cpu(), row_off_host=index.row_off_host)
+    call()
+    ks = sorted(s[0] for s in _timed(call, 20))
+    nbytes = index.y.numel() * 4 + out_t.numel() * out_t.element_size()
+    res["gather"] = dict(split=split, out_dtype=str(opdt).replace("torch.", ""), bytes=nbytes,
+                         median_ms=round(statistics.median(ks), 4), min_ms=round(ks[0], 4),
+                         gb_per_s=round(nbytes / statistics.median(ks) / 1e6, 1),
+                         note="events around one launch: launch latency included")
+    print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gallery", type=int, default=1024)
+    ap.add_argument("--n", type=int, default=128)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--gen-workers", type=int, default=8)
+    ap.add_argument("--dtypes", default="bf16,f32")
+    ap.add_argument("--step-timeout", type=int, default=240, help="time limit of one dtype's child, seconds")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "identify_c4.json"))
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.reps < 5:
+        ap.error("--reps must be at least 5")
+    if args.child:
+        return child(args)
+    lines = []
+    for dtype in args.dtypes.split(","):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", dtype, "--gallery", str(args.gallery), "--n",
+               str(args.n), "--reps", str(args.reps), "--seed", str(args.seed), "--gen-workers", str(args.gen_workers)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
+        except subprocess.TimeoutExpired:
+            sys.exit("identify_bench: the %s step ran over its %d s limit; stopping" % (dtype, args.step_timeout))
+        got = [l for l in r.stdout.splitlines() if l.startswith("IDENTIFY_BENCH ")]
+        if r.returncode != 0 or not got:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            sys.exit("identify_bench: the %s step failed (exit %d); stopping" % (dtype, r.returncode))
+        lines.append(json.loads(got[-1][len("IDENTIFY_BENCH "):]))
+        print(json.dumps(lines[-1]), flush=True)
+    doc = dict(tool="tools/identify_bench.py", config="C4: 1 probe x gallery, n keypoints per graph",
+               method="1 warm-up, median of `reps` forwards, HIP events around each forward; fresh process per dtype",
+               results=lines)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print("wrote %s" % args.out)
+
+
+if __name__ == "__main__":
+    main()
