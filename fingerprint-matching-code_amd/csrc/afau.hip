@@ -477,7 +477,7 @@ __global__ __launch_bounds__(256) void afau_row_attn_v_kernel(const float* __res
 // input C0 + bias (onehot mode).  Writes out_f / out_t, or (gmax != null) only the max over
 // positions of the normalised values (MaxPool1d over the -inf padded 600 positions, ngm.py:402-405).
 // 1024 threads = 16 position groups x 64 channels; each thread keeps its <= NV values in registers,
-// so x is read once (mean, variance and output from registers).
+// so x is read once (mean, variance and output from registers; position 0 once more, as the shift).
 template <typename T, int NV>
 __global__ __launch_bounds__(1024) void instnorm_kernel(const float* __restrict__ in1, const float* __restrict__ in2,
                                                         int P, int Cn, const int* __restrict__ nvalid,
@@ -488,6 +488,19 @@ __global__ __launch_bounds__(1024) void instnorm_kernel(const float* __restrict_
     const int b = blockIdx.x, cl = threadIdx.x & 63, c = blockIdx.y * 64 + cl, g = threadIdx.x >> 6;
     const bool cv = c < Cn;
     const int nb = onehot_bias ? nvalid[b] : 0;
+    // The values are kept relative to the channel's first position x0 (the norm is shift-invariant):
+    // the mean of x - x0 rounds at the scale of the channel's spread, not of its offset.  A channel
+    // without spread -- every column-block channel c >= n2 is the constant combine bias -- would
+    // otherwise come out as rstd = 1 / sqrt(eps) = 316 times the rounding error of its fp32 mean.
+    float x0 = 0.f;
+    if (cv && P > 0) {
+        if (onehot_bias) {
+            x0 = ((c == 0 && nb > 0) ? 1.f : 0.f) + onehot_bias[c];
+        } else {
+            const long o = (long)b * P * Cn + c;
+            x0 = in2 ? in1[o] + in2[o] : in1[o];
+        }
+    }
     float v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -500,6 +513,7 @@ __global__ __launch_bounds__(1024) void instnorm_kernel(const float* __restrict_
                 const long o = ((long)b * P + p) * Cn + c;
                 x = in2 ? in1[o] + in2[o] : in1[o];
             }
+            x -= x0;
         }
         v[k] = x;
     }

@@ -462,6 +462,8 @@ def crossset_attn(cost, n2, Wv, mix1w, mix1b, mix2w, mix2b, out, split=False, st
     if split and out.dtype != torch.bfloat16:
         raise _lib.FpmError("crossset_attn: split rows are bf16")
     _shape(stats, (B * n1max, 16, 2), "crossset_attn stats")
+    if n2max > 1 and cost.stride(2) != 1:
+        raise _lib.FpmError("crossset_attn: cost rows must be contiguous (inner stride %d)" % cost.stride(2))
     _lib.call("fpm_crossset_attn_fwd", 2 if split else _code(out), _p(cost), cost.stride(0), cost.stride(1), B, n1max, n2max,
               _p(n2), _p(Wv), Wv.shape[1], _p(mix1w), _p(mix1b), _p(mix2w), _p(mix2b), _p(out), _p(stats),
               _stream(cost))

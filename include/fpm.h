@@ -278,7 +278,8 @@ int fpm_node_classifier(const float* X, int B, int n1max, int n2max, const float
  * crossset_attn: the row block's multi-head cross-set attention (afau.py:99-142) -> out rows of
  * 256 = 16 heads x 16; dtype 0 = fp32, 1 = bf16, 2 = split bf16 rows [hi | lo | hi] (768 wide, the
  * A operand of the near-fp32 combine product, see fpm_split_bf16x3).  stats (optional, training):
- * per (pair, row, head) the softmax's (max score, sum of exp(score - max)), float2[B][n1max][16]. */
+ * per (pair, row, head) the softmax's (max score, sum of exp(score - max)), float2[B][n1max][16].
+ * cost: element (b, i, j) at cost[b * c_sb + i * c_ld + j] (unit stride along j). */
 int fpm_crossset_attn_fwd(int dtype, const float* cost, long c_sb, long c_ld, int B, int n1max, int n2max,
                           const int* n2, const float* Wv, int emb, const float* mix1w, const float* mix1b,
                           const float* mix2w, const float* mix2b, void* out, float* stats, void* stream);

@@ -21,7 +21,7 @@ SPLINE = "message_pass_node_features.mp_network.convs"
 __all__ = [
     "spline_basis", "spline_conv", "siamese_sconv", "edge_diff", "global_weights", "affinity",
     "kron_pattern", "pattern_mean_explicit", "pattern_mean_factorized", "pygm_sinkhorn",
-    "gnn_layer", "afau_encoder", "afau_ks", "sinkhorn_m", "soft_topk", "hungarian",
+    "gnn_layer", "afau_attention", "afau_encoder", "afau_ks", "sinkhorn_m", "soft_topk", "hungarian",
     "greedy_perm", "match_classifier", "gconv", "forward", "readout", "forward_tail", "permutation_loss",
 ]
 
@@ -210,10 +210,16 @@ def gnn_layer(x, sd, l, agg_fn, n1max, n2max, n1b, n2b, tau=TAU, sk_iter=GNN_SK_
 # ----------------------------------------------------------------------------------------------
 def _instnorm(x, w, b, eps=1e-5):
     """AddAndInstanceNormalization (afau.py:154-176): InstanceNorm1d over positions."""
+    if x.shape[1] == 1:
+        # F.instance_norm refuses a single position; its statistics are mean = x and variance 0
+        return (x - x) / math.sqrt(eps) * w + b
     return F.instance_norm(x.transpose(1, 2), weight=w, bias=b, eps=eps).transpose(1, 2)
 
 
-def _encoding_block(a, bemb, cost, sd, p):
+def afau_attention(a, bemb, cost, sd, p):
+    """CrossSet mixed-score attention of one encoding block (afau.py:99-142, 201-300) in the dtype
+    of ``a``: the mixed scores (B, H, R, Cn) that enter the softmax over the Cn columns, and the
+    heads' output before ``multi_head_combine`` (B, R, 256)."""
     dt = a.dtype
     g = lambda k: sd[p + k].to(dt)
     B, R, _ = a.shape
@@ -232,6 +238,13 @@ def _encoding_block(a, bemb, cost, sd, p):
     mixed = ms2.transpose(1, 2).squeeze(4)                              # (B, H, R, Cn)
     w = torch.softmax(mixed, dim=3)
     out = torch.matmul(w, v).transpose(1, 2).reshape(B, R, H * D)
+    return mixed, out
+
+
+def _encoding_block(a, bemb, cost, sd, p):
+    dt = a.dtype
+    g = lambda k: sd[p + k].to(dt)
+    _, out = afau_attention(a, bemb, cost, sd, p)
     mh = F.linear(out, g(".multi_head_combine.weight"), g(".multi_head_combine.bias"))
     o1 = _instnorm(a + mh, g(".add_n_normalization_1.norm.weight"), g(".add_n_normalization_1.norm.bias"))
     ff = F.linear(F.relu(F.linear(o1, g(".feed_forward.W1.weight"), g(".feed_forward.W1.bias"))),
