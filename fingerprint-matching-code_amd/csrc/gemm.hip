@@ -2,13 +2,13 @@
 // Used by: SplineConv root term, global-weight coefficient (affinity_layer.py:13), vertex
 // affinity Kp (affinity_layer.py:15-18), AFA-U projections/FFN (afau.py:99-103,188-199).
 #include "gemm_phase.h"
-#include "gemm_pp.h"
 #include <cstdlib>
 #include <cstring>
 
 namespace fpm {
 int& gemm_bn256_min();
 }
+int& gemm_store_sc1_flag();
 
 extern "C" int fpm_gemm(int dtype, const void* A, long lda, long sA, const int* a_rows, const void* B, long ldb,
                         long sB, int M, int N, int K, int batch, int epi, const float* bias, float* Cf, void* Ct,
@@ -52,7 +52,14 @@ extern "C" int fpm_gemm(int dtype, const void* A, long lda, long sA, const int* 
             if (BN == 256) FPM_BIG(256, EPI_AFFINITY, true); else FPM_BIG(128, EPI_AFFINITY, true);
         } else if (BN == 256) {
             if (epi == EPI_RELU) { if (f32) FPM_BIG(256, EPI_RELU, true); else FPM_BIG(256, EPI_RELU, false); }
-            else { if (f32) FPM_BIG(256, EPI_STORE, true); else FPM_BIG(256, EPI_STORE, false); }
+            else if (f32) FPM_BIG(256, EPI_STORE, true);
+            else {
+                // bf16 plain store: the walk kernel (S row tiles per workgroup, forced or picked by the kernel)
+                const int S = phase ? gemm_walk_strip(p) : 0;
+                p.store_sc1 = gemm_store_sc1_flag();      // as the SplineConv launch of the same kernels
+                if (S != 0) gemm_walk_launch(p, S, batch, st);
+                else FPM_BIG(256, EPI_STORE, false);
+            }
         } else {
             if (epi == EPI_RELU) { if (f32) FPM_BIG(128, EPI_RELU, true); else FPM_BIG(128, EPI_RELU, false); }
             else { if (f32) FPM_BIG(128, EPI_STORE, true); else FPM_BIG(128, EPI_STORE, false); }
@@ -68,21 +75,32 @@ extern "C" int fpm_gemm(int dtype, const void* A, long lda, long sA, const int* 
 }
 
 namespace fpm {
-// FPM_GEMM_PP: the product GEMM on the two-workgroups-per-CU 256 x 128 kernel (gemm_pp.h)
-int& gemm_pp_flag() {
-    static int on = [] {
-        const char* e = getenv("FPM_GEMM_PP");
-        return e ? atoi(e) : 0;
-    }();
-    return on;
-}
-
 int& gemm_phase_flag() {
     static int on = [] {
         const char* e = getenv("FPM_GEMM_PHASE");
         return e ? atoi(e) : 1;
     }();
     return on;
+}
+
+// FPM_GEMM_WALK: row tiles per workgroup of the bf16 product GEMM (gemm_walk_kernel); GW_AUTO = the rule
+int& gemm_walk_flag() {
+    static int v = [] {
+        const char* e = getenv("FPM_GEMM_WALK");
+        return e ? atoi(e) : GW_AUTO;
+    }();
+    return v;
+}
+
+int gemm_cu_count() {
+    static int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    }();
+    return cus;
 }
 
 int& gemm_bn256_min() {
@@ -250,7 +268,8 @@ int& afau_head_split_flag();
 extern "C" int fpm_set_tuning(const char* key, int value) {
     int* f = nullptr;
     if (key && !strcmp(key, "gemm_phase")) f = &fpm::gemm_phase_flag();
-    else if (key && !strcmp(key, "gemm_pp")) f = &fpm::gemm_pp_flag();
+    else if (key && !strcmp(key, "gemm_walk")) f = &fpm::gemm_walk_flag();
+    else if (key && !strcmp(key, "gemm_bn256_min")) f = &fpm::gemm_bn256_min();
     else if (key && !strcmp(key, "plan_graph")) f = &plan_graph_flag();
     else if (key && !strcmp(key, "combine_npb")) f = &combine_npb_flag();
     else if (key && !strcmp(key, "sinkhorn_bwd_reg")) f = &sinkhorn_bwd_reg_flag();

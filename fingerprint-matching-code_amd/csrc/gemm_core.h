@@ -62,6 +62,10 @@ struct GemmParams {
     int store_sc1;           // bf16 output tiles of the phase kernel: sc1 stores (the lines leave
                              // the XCD's L2 instead of evicting the gathered A rows)
     int remap_cm;            // phase kernel: row tiles per XCD chunk of the tile order (0 = 4)
+    int walk;                // gemm_walk_kernel: 2 = strips of two row tiles per workgroup, 0 = the kernel
+                             // picks 1 or 2 from the real tile count (gemm_walk_rule)
+    const int* tile_count;   // grouped: number of real entries of tile_info (device; null = remap_mtiles)
+    int walk_cus;            // gemm_walk_kernel: CUs of the device, for the rule
 };
 
 // 1-D grid for the XCD-aware tile order: padded to whole rounds of 8 chunks so the remap is a

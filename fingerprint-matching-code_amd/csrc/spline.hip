@@ -14,7 +14,6 @@
 // per-edge GEMM, and the message tensor is never materialised.  The plan (dst CSR included) is
 // built on device once per side and shared by both layers and the GNN layers.
 #include "gemm_phase.h"
-#include "gemm_pp.h"
 
 #include <vector>
 
@@ -1293,9 +1292,11 @@ extern "C" int fpm_spline_conv_fwd_argmax(int dtype, const void* x_op, const voi
         p.store_sc1 = gemm_store_sc1_flag();
         p.remap_mtiles = (int)(dtype == 0 ? L.max_tiles : L.max_tiles2);
         if (dtype == 1) p.tile_info = (const int*)(w + L.tile_info2);
-        const bool pp = dtype == 1 && use_gemm_pp(D);
-        dim3 grid(dtype == 0 ? remap_grid(D, p.remap_mtiles) : pp ? pp_grid(D, p.remap_mtiles)
-                                                                  : remap_grid256(D, p.remap_mtiles), 1, 1);
+        // bf16: the walk kernel (gemm_phase.h; S row tiles per workgroup, forced or picked by the kernel
+        // from the plan's real tile count), 0 = the phase kernel
+        const int walk = dtype == 1 ? gemm_walk_strip(p) : 0;
+        p.tile_count = (const int*)(w + L.cell_off) + NCELL + 2;
+        dim3 grid(dtype == 0 ? remap_grid(D, p.remap_mtiles) : remap_grid256(D, p.remap_mtiles), 1, 1);
         ProfRec rec = {nullptr, nullptr, (int)g_prof.size()};
         if (g_prof_on && !g_prof_rows) (void)hipMalloc(&g_prof_rows, PROF_MAX * sizeof(int));
         if (g_prof_on && g_prof_rows && rec.slot < PROF_MAX) {
@@ -1306,7 +1307,7 @@ extern "C" int fpm_spline_conv_fwd_argmax(int dtype, const void* x_op, const voi
             (void)hipEventRecord(rec.a, st);
         }
         if (dtype == 0) hipLaunchKernelGGL((gemm_kernel<float, false>), grid, dim3(GTHREADS), 0, st, p);
-        else if (pp) hipLaunchKernelGGL((gemm_pp_kernel<EPI_STORE>), grid, dim3(PP_THREADS), 0, st, p);
+        else if (walk != 0) gemm_walk_launch(p, walk, 1, st);
         else if (use_gemm_phase(D)) hipLaunchKernelGGL((gemm_phase_kernel<EPI_STORE, false>), grid, dim3(G2_THREADS), 0, st, p);
         else hipLaunchKernelGGL((gemm_big_kernel<256, EPI_STORE, false>), grid, dim3(G2_THREADS), 0, st, p);
         if (g_prof_on && g_prof_rows && rec.slot < PROF_MAX) {

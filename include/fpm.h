@@ -153,6 +153,15 @@ int fpm_gemm_x3out(const void* A, long lda, const void* B, long ldb, int M, int 
  * previous value, or -1 (error channel set) for an unknown key.  No reference counterpart.
  *   "gemm_phase" (env FPM_GEMM_PHASE, default 1): 256x256 bf16 GEMM tiles on the phase-pipelined
  *                kernel (1) or the two-stage kernel (0)
+ *   "gemm_walk" (FPM_GEMM_WALK, default 8): the phase kernel's bf16 plain-store launches (the
+ *                SplineConv product GEMM) on the strip-walk kernel: 0 / 1 = off (the phase kernel,
+ *                one tile per workgroup), 2..7 = strips of two row tiles per workgroup, the LDS-DMA
+ *                stream carried across the tile boundary, 8 = strips of two where that still leaves
+ *                a workgroup for every CU, decided by the kernel from the real tile count (a launch
+ *                for which it decides on one tile still runs on the walk kernel, as strips of one);
+ *                bit-identical
+ *   "gemm_bn256_min" (FPM_GEMM_BN256_MIN, default 512): fpm_gemm takes 256-wide tiles once they
+ *                alone give this many workgroups
  *   "combine_npb" (FPM_COMBINE_NPB, default 4): destination nodes per SplineConv combine workgroup
  *   "plan_graph" (FPM_PLAN_GRAPH, default 1): per-graph spline plan kernels where they apply (1) or
  *                the global plan kernels (0)

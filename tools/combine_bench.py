@@ -21,7 +21,7 @@ def variants(argv):
 def parse(d, vs):
     f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
-    for name in ("combine_kernel", "gemm_phase_kernel"):
+    for name in ("combine_kernel", "gemm_walk_kernel"):
         ks = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows if name in r["Kernel_Name"]]
         ks = ks[len(ks) - len(vs) * (REPS + 1):]           # the last (REPS + 1) per variant
         for i, v in enumerate(vs):

@@ -51,7 +51,7 @@ def work(n, E, rows_per_node):
         ("combine_kernel", "bytes", 2 * (comb_l1 + comb_l2), 4, "2 sides x 2 layers: product rows + output (+ residual)"),
         ("topk_select_kernel", "bytes", 2 * f4, 1, "perm + lsa matrices out"),
         ("gemm_big_kernel<128, 3", "flops_bf16", 2.0 * N * 768, 1, "vertex affinity Kp (softplus epilogue)"),
-        ("gemm_phase_kernel<0", "flops_bf16", 2 * 2 * 2.0 * spline_rows * 768 * 768, 4, "SplineConv (node, cell) products"),
+        ("gemm_walk_kernel", "flops_bf16", 2 * 2 * 2.0 * spline_rows * 768 * 768, 4, "SplineConv (node, cell) products"),
     ]
 
 
