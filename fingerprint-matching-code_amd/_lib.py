@@ -45,6 +45,9 @@ SIGNATURES = {
     "fpm_rows_bcast_scale": (I, [I, P, L, I, P, P, P, I, P]),
     "fpm_rows_gather_scale": (I, [I, P, P, P, I, I, I, P, P, P, I, P]),
     "fpm_rank_topk": (I, [P, L, I, I, I, P, P, P]),
+    "fpm_rank_select_ws_bytes": (L, [I]),
+    "fpm_rank_select": (I, [P, L, I, I, I, P, P, P, L, P]),
+    "fpm_coarse_score": (I, [P, P, P, I, I, P, I, P, I, F, P, P]),
     "fpm_edge_diff_padded": (I, [P, P, P, P, P, P, L, I, P, P]),
     "fpm_kron_gnn_layer_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fpm_kron_gnn_layer_fwd_ord": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),

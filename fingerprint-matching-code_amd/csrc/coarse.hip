@@ -1,0 +1,307 @@
+// Coarse 1:N score of a probe against enrolled gallery entries (the first pass of a shortlisted
+// identification): per (probe, entry) pair one scalar,
+//
+//     score = sum_{i < n0, j < n_g} P_ij Kp_ij / min(n0, n_g),
+//     Kp = softplus(a b^T) - 0.5,  a = bf16(y_p o c),  b = bf16(y_g),
+//     P  = Sinkhorn(Kp; dummy rows, iters, tau)          (pygmtools' log-domain Sinkhorn),
+//
+// the entropy-relaxed assignment value of the vertex affinity per matched keypoint.
+//
+// One workgroup (256 threads, 4 waves in a 2 x 2 grid of 64 x 64 quadrants) per pair:
+//   1. a b^T on v_mfma_f32_16x16x32_bf16.  The fp32 rows come from global memory (the entry's rows
+//      once, the probe's from L2), are scaled (probe side: one fp32 multiply by coef[b]) and rounded
+//      to bf16 (RNE) on the way into LDS; K = 768 in 12 tiles of 64, the next tile's global loads in
+//      flight under the current tile's MFMAs.
+//   2. The epilogue leaves Kp in the accumulators (they stay there to the end) and writes
+//      L = Kp / tau, in log2 units (so each exp is one v_exp_f32), into a 128 x 128 fp32 matrix in
+//      LDS, in the Sinkhorn's own orientation (rows = the smaller side: the MFMA's A operand is that
+//      side), over the operand tiles' space.
+//   3. The Sinkhorn runs on L in place, as the reference does (L -= lse along rows / columns in
+//      turn): the dominant entries of log P sit near 0, where fp32 is fine-grained (a potential
+//      form, L = M - u - v, would cancel values of ~100 at every read).  Rows: 16 lanes per row, DPP
+//      trees.  Columns: two threads per column, the half column in registers between its one read
+//      and its one write.  The nd = C - R dummy rows are identical at every step, so one row (index
+//      128) with multiplicity nd stands for them.
+//   4. sum exp2(L) Kp over each thread's accumulator positions, wave sums (DPP), the four waves
+//      through LDS; 4 bytes out.
+// The n0 x n_g block never reaches HBM.  Every order of summation is fixed by the pair alone (K
+// order of the MFMA chain, 16-lane DPP trees, the two row halves of a column, the accumulator walk),
+// so an entry's score is bit-identical whatever else shares the launch.  No spinning, no exchange
+// between workgroups.  LDS: 68.6 KB per workgroup, two workgroups per CU.
+#include "fpm_common.h"
+#include "fpm.h"
+
+namespace {
+constexpr int CN = FPM_COARSE_NMAX;      // 128
+constexpr int CT = 256;                  // threads
+constexpr int CK = 768;                  // channels
+constexpr int CBK = 64;                  // K tile
+constexpr int CROW = 144;                // bytes per operand row in LDS: 64 bf16 + 16 B pad
+constexpr int CTILE = CN * CROW;         // one operand tile
+constexpr int SLD = CN + 1;              // fp32 row stride of L (odd: column walks spread over the banks)
+constexpr int S_FLOATS = (CN + 1) * SLD; // rows 0..127 and the dummy row 128
+constexpr int LDS_FLOATS = S_FLOATS + 4 * CN + 4;
+static_assert(2 * CTILE <= S_FLOATS * 4, "the operand tiles share L's space");
+
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float row16_max(float v) {
+    v = fmaxf(v, fpm::dpp_f<0xB1>(v));
+    v = fmaxf(v, fpm::dpp_f<0x4E>(v));
+    v = fmaxf(v, fpm::dpp_f<0x141>(v));
+    return fmaxf(v, fpm::dpp_f<0x140>(v));
+}
+
+// one side's K tile: this thread's 8 float4 (rows (tid >> 4) + 16 m, columns 4 (tid & 15) ..)
+__device__ __forceinline__ void tile_load(const float* __restrict__ base, int n, int k0, int tid, float4 (&r)[8]) {
+    const int row0 = tid >> 4, c = 4 * (tid & 15);
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const int row = row0 + 16 * m;
+        r[m] = row < n ? *(const float4*)(base + (long)row * CK + k0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+// scale (one fp32 multiply; the unscaled side multiplies by 1, exactly), round to bf16, into LDS
+__device__ __forceinline__ void tile_store(unsigned char* tile, int tid, const float4 (&r)[8], float4 s) {
+    const int row0 = tid >> 4, c = 4 * (tid & 15);
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        uint2 o;
+        o.x = fpm::f2bf2(__fmul_rn(r[m].x, s.x), __fmul_rn(r[m].y, s.y));
+        o.y = fpm::f2bf2(__fmul_rn(r[m].z, s.z), __fmul_rn(r[m].w, s.w));
+        *(uint2*)(tile + (row0 + 16 * m) * CROW + c * 2) = o;
+    }
+}
+
+// two workgroups per CU (LDS allows it): hold the registers to two waves per SIMD
+__global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void coarse_score_kernel(const float* __restrict__ y,
+                                                           const long* __restrict__ row_off,
+                                                           const int* __restrict__ idx, int G,
+                                                           const float* __restrict__ yp, int n0,
+                                                           const float* __restrict__ coef, int iters, float tau,
+                                                           float* __restrict__ score) {
+    extern __shared__ float lds[];
+    float* S = lds;
+    float* cm = lds + S_FLOATS;              // [2][128] column partial maxima
+    float* cs = cm + 2 * CN;                 // [2][128] column partial sums
+    float* red = cs + 2 * CN;                // [4] wave sums
+    unsigned char* At = (unsigned char*)lds; // operand tiles (before L exists)
+    unsigned char* Bt = At + CTILE;
+
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = idx[b];
+    long r0 = 0, ngl = 0;
+    if (g >= 0 && g < G) {
+        r0 = row_off[g];
+        ngl = row_off[g + 1] - r0;
+    }
+    // the wrapper checks both on the host; never read outside y, never index past the 128 x 128 box
+    if (ngl < 1 || ngl > CN || n0 < 1 || n0 > CN) {
+        if (tid == 0) score[b] = __uint_as_float(0x7FC00000u);
+        return;
+    }
+    const int ng = (int)ngl;
+    // the Sinkhorn works on the transpose when n0 > n_g: its rows are the smaller side
+    const bool tr = n0 > ng;
+    const int R = tr ? ng : n0, C = tr ? n0 : ng;
+    const float* xa = tr ? y + r0 * CK : yp;         // rows side (MFMA A)
+    const float* xb = tr ? yp : y + r0 * CK;         // columns side (MFMA B)
+    const float* cf = coef + (long)b * CK;
+    const int c4 = 4 * (tid & 15);
+    const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
+
+    const int wm = wave >> 1, wn = wave & 1;
+    f32x4_t acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+
+    float4 ra[8], rb[8], sc;
+    tile_load(xa, R, 0, tid, ra);
+    tile_load(xb, C, 0, tid, rb);
+    sc = *(const float4*)(cf + c4);
+    const int fr = lane & 15, fq = lane >> 4;
+    for (int kt = 0; kt < CK / CBK; ++kt) {
+        tile_store(At, tid, ra, tr ? one : sc);
+        tile_store(Bt, tid, rb, tr ? sc : one);
+        __syncthreads();
+        if (kt + 1 < CK / CBK) {
+            tile_load(xa, R, (kt + 1) * CBK, tid, ra);
+            tile_load(xb, C, (kt + 1) * CBK, tid, rb);
+            sc = *(const float4*)(cf + (kt + 1) * CBK + c4);
+        }
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            bf16x8_t a[4], bb[4];
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                a[f] = *(const bf16x8_t*)(At + (wm * 64 + f * 16 + fr) * CROW + (kk * 32 + fq * 8) * 2);
+                bb[f] = *(const bf16x8_t*)(Bt + (wn * 64 + f * 16 + fr) * CROW + (kk * 32 + fq * 8) * 2);
+            }
+#pragma unroll
+            for (int fm = 0; fm < 4; ++fm) {
+                if (wm * 64 + fm * 16 >= R) continue;        // fragments past the block: wave-uniform
+#pragma unroll
+                for (int fn = 0; fn < 4; ++fn) {
+                    if (wn * 64 + fn * 16 >= C) continue;
+                    acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[fm], bb[fn], acc[fm][fn], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // Kp stays in acc (0 outside the block); L = Kp / tau into LDS
+#pragma unroll
+    for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < 4; ++fn)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = wm * 64 + fm * 16 + 4 * fq + r, j = wn * 64 + fn * 16 + fr;
+                float kp = 0.f;
+                if (i < R && j < C) {
+                    kp = fpm::softplus_f(acc[fm][fn][r]) - 0.5f;
+                    S[i * SLD + j] = (kp / tau) * fpm::LOG2E_F;
+                }
+                acc[fm][fn][r] = kp;
+            }
+    const int nd = C - R;                    // dummy rows (dummy_row = True)
+    if (nd > 0 && tid < C) S[CN * SLD + tid] = -100.f * fpm::LOG2E_F;
+    __syncthreads();
+
+    const float fnd = (float)nd;
+    for (int it = 0; it < iters; ++it) {
+        if ((it & 1) == 0) {
+            // rows: 16 lanes per row, 8 columns per lane.  A wave's four rows lie 16 apart (row stride
+            // 129 words: 16 banks apart, no conflicts); pass 8 is the dummy row's
+            for (int u = 0; u < 9; ++u) {
+                const int p = u < 8 ? (u >> 2) * 64 + fq * 16 + wave * 4 + (u & 3) : (wave == 0 && fq == 0 ? CN : -1);
+                if (p < 0 || (p < CN ? p >= R : nd <= 0)) continue;
+                float* row = S + p * SLD;
+                float x[8];
+                float m = -INFINITY;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int c = fr + 16 * q;
+                    x[q] = c < C ? row[c] : -INFINITY;
+                    m = fmaxf(m, x[q]);
+                }
+                m = row16_max(m);
+                float s = 0.f;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) s += fpm::fast_exp2(x[q] - m);
+                s = fpm::row16_sum(s);
+                const float lse = m + fpm::fast_log2(s);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int c = fr + 16 * q;
+                    if (c < C) row[c] = x[q] - lse;
+                }
+            }
+        } else {
+            // columns: two threads per column, rows [0, 64) and [64, 128); the first also takes the
+            // nd dummy rows; the halves join through LDS in a fixed order
+            const int j = tid & (CN - 1), h = tid >> 7;
+            const int i0 = h * 64, i1 = R < i0 + 64 ? R : i0 + 64;
+            const bool dm = nd > 0 && h == 0;
+            // the half column in two chunks of 32 rows (32 independent loads in flight each); their
+            // (max, sum) pairs merge in a fixed order, then the dummy rows' term
+            float m = -INFINITY, s = 0.f, dj = 0.f;
+            const bool on = j < C;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int ib = i0 + 32 * c;
+                if (!on || ib >= i1) continue;
+                float x[32];
+                float mc = -INFINITY, sc2 = 0.f;
+#pragma unroll
+                for (int q = 0; q < 32; ++q) {
+                    x[q] = ib + q < i1 ? S[(ib + q) * SLD + j] : -INFINITY;
+                    mc = fmaxf(mc, x[q]);
+                }
+#pragma unroll
+                for (int q = 0; q < 32; ++q) sc2 += fpm::fast_exp2(x[q] - mc);
+                if (c == 0) {
+                    m = mc;
+                    s = sc2;
+                } else {
+                    const float mn = fmaxf(m, mc);
+                    s = s * fpm::fast_exp2(m - mn) + sc2 * fpm::fast_exp2(mc - mn);
+                    m = mn;
+                }
+            }
+            if (on) {
+                if (dm) {                                        // half 0: never empty (row 0)
+                    dj = S[CN * SLD + j];
+                    const float mn = fmaxf(m, dj);
+                    s = s * fpm::fast_exp2(m - mn) + fnd * fpm::fast_exp2(dj - mn);
+                    m = mn;
+                }
+                cm[h * CN + j] = m;                              // (-inf, 0): an empty half 1
+                cs[h * CN + j] = s;
+            }
+            __syncthreads();
+            if (on) {
+                const float m0 = cm[j], m1 = cm[CN + j];
+                const float mm = fmaxf(m0, m1);              // finite: half 0 holds row 0
+                const float t = cs[j] * fpm::fast_exp2(m0 - mm) + cs[CN + j] * fpm::fast_exp2(m1 - mm);
+                const float lse = mm + fpm::fast_log2(t);
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const int ib = i0 + 32 * c;
+                    if (ib >= i1) continue;
+                    float x[32];
+#pragma unroll
+                    for (int q = 0; q < 32; ++q) x[q] = ib + q < i1 ? S[(ib + q) * SLD + j] : 0.f;
+#pragma unroll
+                    for (int q = 0; q < 32; ++q)
+                        if (ib + q < i1) S[(ib + q) * SLD + j] = x[q] - lse;
+                }
+                if (dm) S[CN * SLD + j] = dj - lse;
+            }
+        }
+        __syncthreads();
+    }
+
+    // <P, Kp> over this thread's accumulator positions, then the wave, then the four waves
+    float part = 0.f;
+#pragma unroll
+    for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < 4; ++fn)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = wm * 64 + fm * 16 + 4 * fq + r, j = wn * 64 + fn * 16 + fr;
+                if (i < R && j < C) part += fpm::fast_exp2(S[i * SLD + j]) * acc[fm][fn][r];
+            }
+    part = fpm::wave_sum_dpp(part);
+    if (lane == 0) red[wave] = part;
+    __syncthreads();
+    if (tid == 0) score[b] = (((red[0] + red[1]) + red[2]) + red[3]) / (float)R;
+}
+}  // namespace
+
+extern "C" int fpm_coarse_score(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp,
+                                int n0, const float* coef, int iters, float tau, float* score, void* stream) {
+    FPM_CHECK_ARG(G > 0 && B >= 0, "coarse_score: bad sizes (G %d, B %d)", G, B);
+    FPM_CHECK_ARG(n0 >= 1 && n0 <= FPM_COARSE_NMAX, "coarse_score: probe of %d keypoints outside [1, COARSE_NMAX = %d]",
+                  n0, FPM_COARSE_NMAX);
+    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_score: iters >= 0 and tau > 0 required");
+    FPM_CHECK_ARG(y && row_off && idx && yp && coef && score,
+                  "coarse_score: y, row_off, idx, yp, coef and score are required");
+    if (B == 0) return 0;
+    constexpr int lds = LDS_FLOATS * (int)sizeof(float);
+    if (hipFuncSetAttribute((const void*)coarse_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
+        hipSuccess) {
+        (void)hipGetLastError();
+        fpm::set_error("coarse_score: %d bytes of LDS per workgroup refused", lds);
+        return 1;
+    }
+    hipLaunchKernelGGL(coarse_score_kernel, dim3((unsigned)B), dim3(CT), lds, (hipStream_t)stream, y, row_off, idx, G,
+                       yp, n0, coef, iters, tau, score);
+    return fpm::check_launch("fpm_coarse_score");
+}

@@ -1,0 +1,210 @@
+// Per-probe top-k for k up to 1024 (the shortlist of a 1:N identification): the ranking of
+// rank.hip (64-bit key = order-preserving score bits << 32 | (0xFFFFFFFF - index), unique per
+// element; descending, ties to the lower index, NaN after every number) without k passes over the row.
+//
+//   1. Radix search for the k-th largest key T: six digit passes over the key's 64 bits from the top
+//      (five of 11 bits, one of 9).  A pass is one launch of several workgroups per row; each builds
+//      the histogram of its slice's keys that match the prefix found so far (LDS, then integer
+//      atomics into the row's global histogram: the counts do not depend on arrival order).  The
+//      prefix of pass d is derived at the start of pass d from pass d - 1's finished histogram, by
+//      every workgroup for itself; workgroup 0 of the row records it for pass d + 1.  Launch order on
+//      the stream is the only synchronisation.
+//   2. Compaction: the keys >= T (exactly k, keys being unique) go to a k-slot list, slots handed
+//      out by an integer atomic (their order is arbitrary and does not matter:)
+//   3. one workgroup per row sorts the list in LDS (bitonic, 1024 slots) and writes indices and scores.
+#include "fpm_common.h"
+#include "fpm.h"
+
+namespace {
+constexpr int RS_THREADS = 256;
+constexpr int RS_KMAX = FPM_RANK_SELECT_KMAX;
+constexpr int RS_PASSES = 6;
+constexpr int RS_BINS = 2048;
+constexpr int RS_ITEMS = 16;                       // elements per thread and slice pass
+typedef unsigned long long u64;
+
+__device__ __host__ constexpr int rs_width(int d) { return d < 5 ? 11 : 9; }
+__device__ __host__ constexpr int rs_shift(int d) { return d < 5 ? 53 - 11 * d : 0; }
+
+// per-row scratch
+struct RsRow {
+    unsigned hist[RS_PASSES][RS_BINS];
+    u64 prefix[RS_PASSES + 1];     // prefix[d]: the key bits above pass d's digit; prefix[6] = T
+    unsigned krem[RS_PASSES + 1];  // rank still sought among the keys that match prefix[d]
+    unsigned count;                // compaction slots handed out
+    unsigned pad;
+    u64 cand[RS_KMAX];
+};
+
+// as rank.hip's rank_bits
+__device__ __forceinline__ uint32_t rs_bits(float f) {
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ u64 rs_key(float f, int i) {
+    return ((u64)rs_bits(f) << 32) | (0xFFFFFFFFu - (uint32_t)i);
+}
+
+// prefix / remaining rank of pass d (1 <= d <= 6) from pass d - 1's state and finished histogram;
+// every thread of the workgroup returns with the same pair.  sh: RS_THREADS + 2 words of LDS.
+__device__ void rs_derive(const RsRow* w, int d, unsigned k, unsigned* sh, u64& prefix, unsigned& krem) {
+    if (d == 0) {
+        prefix = 0;
+        krem = k;
+        return;
+    }
+    const u64 pp = d == 1 ? 0ull : w->prefix[d - 1];
+    const unsigned kr = d == 1 ? k : w->krem[d - 1];
+    const unsigned* h = w->hist[d - 1];
+    const int tid = threadIdx.x;
+    // thread t owns the 8 bins 2047 - 8t .. 2040 - 8t (descending walk)
+    unsigned c[8], ls = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        c[q] = h[RS_BINS - 1 - (8 * tid + q)];
+        ls += c[q];
+    }
+    sh[tid] = ls;
+    __syncthreads();
+    for (int o = 1; o < RS_THREADS; o <<= 1) {       // inclusive scan over the threads
+        const unsigned v = tid >= o ? sh[tid - o] : 0u;
+        __syncthreads();
+        sh[tid] += v;
+        __syncthreads();
+    }
+    unsigned above = sh[tid] - ls;                   // keys in bins above this thread's
+    if (above < kr && kr <= above + ls) {            // exactly one thread: the bin of rank kr
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            if (above < kr && kr <= above + c[q]) {
+                sh[RS_THREADS] = (unsigned)(RS_BINS - 1 - (8 * tid + q));
+                sh[RS_THREADS + 1] = kr - above;
+            }
+            above += c[q];
+        }
+    }
+    __syncthreads();
+    prefix = (pp << rs_width(d - 1)) | sh[RS_THREADS];
+    krem = sh[RS_THREADS + 1];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(RS_THREADS) void rank_select_hist_kernel(const float* __restrict__ scores, long ld, int G,
+                                                                      int k, int d, RsRow* __restrict__ ws) {
+    __shared__ unsigned lh[RS_BINS];
+    __shared__ unsigned sh[RS_THREADS + 2];
+    RsRow* w = ws + blockIdx.y;
+    const float* row = scores + (long)blockIdx.y * ld;
+    u64 prefix;
+    unsigned krem;
+    rs_derive(w, d, (unsigned)k, sh, prefix, krem);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && d > 0) {
+        w->prefix[d] = prefix;
+        w->krem[d] = krem;
+    }
+    for (int i = threadIdx.x; i < RS_BINS; i += RS_THREADS) lh[i] = 0u;
+    __syncthreads();
+    const int sh_d = rs_shift(d), wd = rs_width(d);
+    const long per = (long)RS_THREADS * RS_ITEMS;
+    for (long base = (long)blockIdx.x * per; base < G; base += (long)gridDim.x * per) {
+#pragma unroll 4
+        for (int q = 0; q < RS_ITEMS; ++q) {
+            const long i = base + q * RS_THREADS + threadIdx.x;
+            if (i < G) {
+                const u64 key = rs_key(row[i], (int)i);
+                if (d == 0 || (key >> (sh_d + wd)) == prefix)
+                    atomicAdd(&lh[(unsigned)(key >> sh_d) & ((1u << wd) - 1u)], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < RS_BINS; i += RS_THREADS)
+        if (lh[i]) atomicAdd(&w->hist[d][i], lh[i]);
+}
+
+__global__ __launch_bounds__(RS_THREADS) void rank_select_compact_kernel(const float* __restrict__ scores, long ld,
+                                                                         int G, int k, RsRow* __restrict__ ws) {
+    __shared__ unsigned sh[RS_THREADS + 2];
+    RsRow* w = ws + blockIdx.y;
+    const float* row = scores + (long)blockIdx.y * ld;
+    u64 T;
+    unsigned krem;
+    rs_derive(w, RS_PASSES, (unsigned)k, sh, T, krem);
+    const long per = (long)RS_THREADS * RS_ITEMS;
+    for (long base = (long)blockIdx.x * per; base < G; base += (long)gridDim.x * per) {
+        for (int q = 0; q < RS_ITEMS; ++q) {
+            const long i = base + q * RS_THREADS + threadIdx.x;
+            if (i < G) {
+                const u64 key = rs_key(row[i], (int)i);
+                if (key >= T) {
+                    const unsigned slot = atomicAdd(&w->count, 1u);
+                    if (slot < (unsigned)k) w->cand[slot] = key;     // exactly k keys pass; the guard bounds the write
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(RS_THREADS) void rank_select_sort_kernel(const float* __restrict__ scores, long ld, int G, int k,
+                                                                      const RsRow* __restrict__ ws,
+                                                                      int* __restrict__ top_idx,
+                                                                      float* __restrict__ top_score) {
+    __shared__ u64 key[RS_KMAX];
+    const RsRow* w = ws + blockIdx.x;
+    const float* row = scores + (long)blockIdx.x * ld;
+    int n = 2;
+    while (n < k) n <<= 1;                           // power of two >= k, at most 1024
+    for (int i = threadIdx.x; i < n; i += RS_THREADS) key[i] = i < k ? w->cand[i] : 0ull;   // 0 is below every key
+    __syncthreads();
+    for (int size = 2; size <= n; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < n / 2; t += RS_THREADS) {
+                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                const bool desc = (lo & size) == 0;
+                const u64 a = key[lo], b = key[hi];
+                if ((a < b) == desc) {
+                    key[lo] = b;
+                    key[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    for (int j = threadIdx.x; j < k; j += RS_THREADS) {
+        const uint32_t i = 0xFFFFFFFFu - (uint32_t)key[j];
+        const bool ok = i < (uint32_t)G;             // always, with k <= G keys in the list; never read outside the row
+        top_idx[(long)blockIdx.x * k + j] = ok ? (int)i : -1;
+        top_score[(long)blockIdx.x * k + j] = ok ? row[i] : __uint_as_float(0x7FC00000u);
+    }
+}
+}  // namespace
+
+extern "C" long fpm_rank_select_ws_bytes(int P) { return P > 0 ? (long)P * (long)sizeof(RsRow) : 0; }
+
+extern "C" int fpm_rank_select(const float* scores, long ld, int P, int G, int k, int* top_idx, float* top_score,
+                               void* ws, long ws_bytes, void* stream) {
+    FPM_CHECK_ARG(P >= 0 && G >= 1 && ld >= G, "rank_select: bad sizes (P %d, G %d, ld %ld)", P, G, ld);
+    FPM_CHECK_ARG(k >= 1 && k <= RS_KMAX && k <= G, "rank_select: k = %d outside [1, min(G, %d)]", k, RS_KMAX);
+    FPM_CHECK_ARG(scores && top_idx && top_score, "rank_select: scores, top_idx and top_score are required");
+    FPM_CHECK_ARG(P <= 65535, "rank_select: at most 65535 rows per call (P %d)", P);
+    if (P == 0) return 0;
+    const long need = fpm_rank_select_ws_bytes(P);
+    FPM_CHECK_ARG(ws && ws_bytes >= need, "rank_select: workspace of %ld bytes required (got %ld)", need, ws_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ws, 0, (size_t)need, st) != hipSuccess) {
+        (void)hipGetLastError();
+        fpm::set_error("rank_select: clearing the workspace failed");
+        return 1;
+    }
+    const long per = (long)RS_THREADS * RS_ITEMS;
+    long nb = (G + per - 1) / per;
+    nb = nb < 1 ? 1 : (nb > 256 ? 256 : nb);
+    RsRow* w = (RsRow*)ws;
+    const dim3 grid((unsigned)nb, (unsigned)P);
+    for (int d = 0; d < RS_PASSES; ++d)
+        hipLaunchKernelGGL(rank_select_hist_kernel, grid, dim3(RS_THREADS), 0, st, scores, ld, G, k, d, w);
+    hipLaunchKernelGGL(rank_select_compact_kernel, grid, dim3(RS_THREADS), 0, st, scores, ld, G, k, w);
+    hipLaunchKernelGGL(rank_select_sort_kernel, dim3((unsigned)P), dim3(RS_THREADS), 0, st, scores, ld, G, k,
+                       (const RsRow*)w, top_idx, top_score);
+    return fpm::check_launch("fpm_rank_select");
+}

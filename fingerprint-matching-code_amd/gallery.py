@@ -8,6 +8,10 @@ gathered from the index (``fpm_rows_gather_scale``) instead of recomputed -- the
 every output equals ``net.run(DeviceBatch.from_probe_gallery(probe, gallery))`` bit for bit -- and
 ranks the pair scores on the device (``fpm_rank_topk``).
 
+``identify(shortlist=M)`` puts a coarse pass in front: ``coarse_scores`` (one fused kernel per pair,
+``fpm_coarse_score``: bf16 vertex affinity, Sinkhorn and <P, Kp> without the block leaving the CU)
+over the selected entries, ``fpm_rank_select`` to the M best, and the forward above over those alone.
+
 Size of an index: 768 fp32 channels = 3 KB per keypoint (0.39 MB per template at n = 128, 0.4 GB per
 1024 such templates), plus the graph's edges (12 B each, ~6 per keypoint) and 2 KB of global feature.
 """
@@ -276,7 +280,89 @@ def probe_batch(probe, index, select=None):
     return bt, sel
 
 
-def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None):
+def _check_query(net, index, what):
+    """The refusals shared by ``identify`` and ``coarse_scores``."""
+    if net.training:
+        raise FpmError("%s: inference only (call net.eval()); training through an index is not supported" % what)
+    if not isinstance(index, GalleryIndex):
+        raise FpmError("%s: index must be a GalleryIndex (Net.enroll)" % what)
+    if index.sc_mode == "bf16" and net.dtype_mode != "bf16":
+        raise FpmError("%s: the index holds bf16-SplineConv rows, the net runs fp32" % what)
+    net.packed(index.device)
+    if index.weights_id != spline_weights_id(net):
+        raise FpmError("%s: the index was enrolled with other SplineConv weights (pack generation %d, net's %d); "
+                       "enroll the gallery again" % (what, index._pack_gen, net._pack_gen))
+
+
+COARSE_CHUNK = 4096          # entries per coarse launch: 12 MB of coefficient scratch, whatever the gallery
+
+
+class _ProbeSide:
+    """What ``Net._probe_rows`` reads of a batch, for a probe graph alone (no gallery side staged)."""
+
+    def __init__(self, probe, index):
+        dev = index.device
+        n0 = int(probe["n"])
+        ei = torch.from_numpy(np.asarray(probe["edge_index"]).astype(np.int32)).to(dev)
+        self.device, self.sc_mode = dev, index.sc_mode
+        self.nmax = [n0, n0]
+        self.x = [torch.from_numpy(np.ascontiguousarray(np.asarray(probe["x"], dtype=np.float32))).to(dev)]
+        self.src, self.dst = [ei[0].contiguous()], [ei[1].contiguous()]
+        self.pseudo = [torch.from_numpy(np.asarray(probe["pseudo"], dtype=np.float32).reshape(-1, 2)).to(dev)]
+        self.edge_off = [torch.tensor([0, int(ei.shape[1])], dtype=torch.int64)]
+        self.n = [torch.tensor([n0], dtype=torch.int32, device=dev)]
+        self.w0 = torch.from_numpy(np.asarray(probe["w"], dtype=np.float32)).to(dev).view(1, -1)
+
+
+def _select_host(index, select, what):
+    if select is None:
+        return torch.arange(index.G, dtype=torch.int64)
+    sel = torch.as_tensor(select, dtype=torch.int64).view(-1).cpu()
+    if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= index.G:
+        raise FpmError("%s: select must name entries in [0, %d)" % (what, index.G))
+    return sel
+
+
+def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk):
+    """One probe's coarse scores over the entries ``sel`` into ``out`` (len(sel),)."""
+    n0 = int(probe["n"])
+    ng = index.n[sel]
+    if n0 > ops.COARSE_NMAX or n0 < 1 or int(ng.max()) > ops.COARSE_NMAX:
+        raise FpmError("coarse_scores: a graph of %d keypoints; the coarse pass takes boxes up to COARSE_NMAX = %d "
+                       "(identify without a shortlist has no such bound)" % (max(n0, int(ng.max())), ops.COARSE_NMAX))
+    ps = _ProbeSide(probe, index)
+    yp = net._probe_rows(wp, ps)
+    sel32 = sel.to(torch.int32)
+    B = int(sel.numel())
+    step = max(1, int(chunk))
+    coef = torch.empty(min(B, step), C.NODE_FEATURE_DIM, device=index.device, dtype=torch.float32)
+    w0 = ps.w0.expand(min(B, step), -1).contiguous()
+    for b0 in range(0, B, step):
+        b1 = min(B, b0 + step)
+        gw = ops.global_weights(w0[:b1 - b0], index.w[sel_d[b0:b1].long()])
+        cf = coef[:b1 - b0]
+        ops.coef_tanh(gw, wp["aff_wT"], wp["aff_b"], cf)
+        ops.coarse_score(index.y, index.row_off, sel_d[b0:b1], yp, cf, iters=C.SK_ITER_NUM, tau=net.tau,
+                         out=out[b0:b1], idx_host=sel32[b0:b1], row_off_host=index.row_off_host)
+
+
+def coarse_scores(net, probes, index, select=None, chunk=COARSE_CHUNK):
+    """``Net.coarse_scores``: see there."""
+    _check_query(net, index, "coarse_scores")
+    sel = _select_host(index, select, "coarse_scores")
+    single = isinstance(probes, dict)
+    plist = [probes] if single else list(probes)
+    dev = index.device
+    wp = net.packed(dev)
+    out = torch.empty(len(plist), int(sel.numel()), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        sel_d = sel.to(dev).to(torch.int32).contiguous()
+        for i, p in enumerate(plist):
+            _coarse_one(net, wp, p, index, sel, sel_d, out[i], chunk)
+    return out
+
+
+def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None, shortlist=None):
     """``Net.identify``: see there."""
     if net.training:
         raise FpmError("identify: inference only (call net.eval()); training through an index is not supported")
@@ -284,14 +370,9 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
         raise FpmError("identify: cached-gallery forwards are eager; switch HIP-graph replay (use_graphs) off")
     if score not in SCORES:
         raise FpmError("identify: score must be one of %s" % (SCORES,))
-    if not isinstance(index, GalleryIndex):
-        raise FpmError("identify: index must be a GalleryIndex (Net.enroll)")
-    if index.sc_mode == "bf16" and net.dtype_mode != "bf16":
-        raise FpmError("identify: the index holds bf16-SplineConv rows, the net runs fp32")
-    net.packed(index.device)
-    if index.weights_id != spline_weights_id(net):
-        raise FpmError("identify: the index was enrolled with other SplineConv weights (pack generation %d, net's %d); "
-                       "enroll the gallery again" % (index._pack_gen, net._pack_gen))
+    _check_query(net, index, "identify")
+    if shortlist is not None:
+        return _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist)
     single = isinstance(probes, dict)
     plist = [probes] if single else list(probes)
     outs, sel = [], None
@@ -312,4 +393,29 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
                     o["top_idx"], o["top_score"] = ti[i], ts[i]
     finally:
         net.prologue_graph = keep
+    return outs[0] if single else outs
+
+
+def _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist):
+    """``identify(shortlist=M)``: per probe the coarse pass over ``select``, the M best entries
+    (``ops.rank_select``), and the plain ``identify`` over exactly those, in coarse-rank order."""
+    M = int(shortlist)
+    if not 1 <= M <= ops.RANK_SELECT_KMAX:
+        raise FpmError("identify: shortlist = %d outside [1, %d]" % (M, ops.RANK_SELECT_KMAX))
+    sel = _select_host(index, select, "identify")
+    M = min(M, int(sel.numel()))
+    single = isinstance(probes, dict)
+    plist = [probes] if single else list(probes)
+    outs = []
+    if not plist:
+        return outs
+    call = coarse_scores(net, plist, index, select=sel)
+    with torch.cuda.device(index.device):
+        pos, csc = ops.rank_select(call, M)
+        short = sel.to(index.device)[pos.long()].to(torch.int32)
+        short_host = short.cpu()                # the shortlist shapes the host-side batch: one copy per query
+    for i, p in enumerate(plist):
+        o = identify(net, p, index, topk=topk, select=short_host[i].long(), score=score, chunks=chunks)
+        o["short_idx"], o["coarse_score"], o["coarse_all"] = short[i], csc[i], call[i]
+        outs.append(o)
     return outs[0] if single else outs

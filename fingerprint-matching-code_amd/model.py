@@ -1469,7 +1469,20 @@ class Net(nn.Module):
         from . import gallery
         return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch)
 
-    def identify(self, probes, index, topk=10, select=None, score="cls_prob", chunks=None):
+    def coarse_scores(self, probes, index, select=None):
+        """The coarse first pass of a shortlisted identification: for each probe graph (one dict, or a
+        list) one cheap score per gallery entry of ``select`` (default all) -> (P, len(select)) fp32 on
+        the index's device.  Per pair: Kp = softplus(a b^T) - 0.5 on single-bf16 operands (the probe's
+        SplineConv rows under the index's sc_mode, scaled by the forward's coefficients; the entry's
+        cached rows), the forward's final Sinkhorn (10 steps, tau) on Kp itself, and
+        sum P o Kp / min(n0, n_g): the entropy-relaxed assignment value of the vertex affinity per
+        matched keypoint (``ops.coarse_score``; one fused kernel, the block never leaves the CU).
+        The gallery is walked in bounded chunks, so the scratch does not grow with it.  Boxes of at
+        most ``ops.COARSE_NMAX`` = 128 keypoints; the refusals of ``identify`` apply."""
+        from . import gallery
+        return gallery.coarse_scores(self, probes, index, select=select)
+
+    def identify(self, probes, index, topk=10, select=None, shortlist=None, score="cls_prob", chunks=None):
         """1:N identification against an enrolled gallery: for each probe graph (one dict, or a list)
         the shared-probe forward over the gallery entries ``select`` (an index list; default all),
         with side 1's operand rows gathered from ``index`` (no SplineConv for the gallery side) --
@@ -1478,9 +1491,17 @@ class Net(nn.Module):
         entry numbers) / ``top_score``: the ``topk`` best pairs by ``score`` ("cls_prob",
         "cls_logits" or "k_prob"), ranked on the device (``ops.rank_topk``).  Raises FpmError when the
         index was enrolled with other SplineConv weights, in training mode, or with HIP-graph replay
-        (``use_graphs``) on: forwards over an index are eager."""
+        (``use_graphs``) on: forwards over an index are eager.
+
+        ``shortlist=M`` (1 <= M <= 1024, clamped to the selected entries): per probe the coarse pass
+        over ``select`` (``coarse_scores``), the M best entries by it (``ops.rank_select``), and the
+        forward above over exactly those, in coarse-rank order -- every output equals
+        ``identify(probe, index, select=short_idx)`` bit for bit.  The dict then also carries
+        ``short_idx`` (M, int32 gallery entry numbers), ``coarse_score`` (M) and ``coarse_all``
+        (len(select))."""
         from . import gallery
-        return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks)
+        return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
+                                shortlist=shortlist)
 
     def image_features(self, images, Ps, ns, dev=None):
         """ngm.py:226-248 on the device: per side, node_layers/edge_layers (ResNet-18 convolutions

@@ -2,8 +2,9 @@
 
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
-no CPU fallback: a CPU tensor or a missing library raises (``rank_topk`` alone keeps a plain-torch
-host path for CPU tensors, the statement of its ordering).
+no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select`` and
+``coarse_score`` alone keep a plain-torch host path for CPU tensors: the statements of the ordering
+and of the coarse score, which the tests hold the kernels to).
 """
 import ctypes
 
@@ -412,6 +413,163 @@ def rank_topk(scores, k, top_idx=None, top_score=None):
     _dev(top_idx, top_score)
     _lib.call("fpm_rank_topk", _p(scores), ld, P, G, k, _p(top_idx), _p(top_score), _stream(scores))
     return top_idx, top_score
+
+
+RANK_SELECT_KMAX = 1024
+
+
+def rank_select(scores, k, top_idx=None, top_score=None):
+    """``rank_topk``'s ranking for 1 <= k <= min(G, 1024) (the shortlist of a 1:N identification):
+    scores (P, G) fp32 (any row stride) -> (top_idx (P, k) int32, top_score (P, k) fp32), descending,
+    ties to the lower index, NaN after every number.  Device tensors run fpm_rank_select (a radix
+    search for the k-th largest key over several workgroups per row, a compaction, a sort of the k in
+    LDS); CPU tensors take the same stable sort as ``rank_topk``'s host path.  Keys are unique, so
+    the two agree bit for bit, and with ``rank_topk`` for k <= 128."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
+        raise _lib.FpmError("rank_select: scores must be a (P, G) fp32 tensor")
+    P, G = int(scores.shape[0]), int(scores.shape[1])
+    k = int(k)
+    if not 1 <= k <= min(G, RANK_SELECT_KMAX):
+        raise _lib.FpmError("rank_select: k = %d outside [1, min(G, %d) = %d]"
+                            % (k, RANK_SELECT_KMAX, min(G, RANK_SELECT_KMAX)))
+    if not scores.is_cuda:
+        order = torch.argsort(rank_key(scores), dim=1, descending=True, stable=True)[:, :k]
+        return order.to(torch.int32), torch.gather(scores, 1, order)
+    if P > 65535:
+        raise _lib.FpmError("rank_select: at most 65535 rows per call")
+    if G > 1 and scores.stride(1) != 1:
+        scores = scores.contiguous()
+    ld = int(scores.stride(0)) if P > 1 else G
+    if ld < G:
+        scores, ld = scores.contiguous(), G
+    if top_idx is None:
+        top_idx = torch.empty(P, k, device=scores.device, dtype=torch.int32)
+    if top_score is None:
+        top_score = torch.empty(P, k, device=scores.device, dtype=torch.float32)
+    _shape(top_idx, (P, k), "rank_select top_idx")
+    _shape(top_score, (P, k), "rank_select top_score")
+    if top_idx.dtype != torch.int32 or top_score.dtype != torch.float32 or not top_idx.is_contiguous() \
+            or not top_score.is_contiguous():
+        raise _lib.FpmError("rank_select: top_idx must be contiguous int32, top_score contiguous fp32")
+    _dev(top_idx, top_score)
+    if P == 0:
+        return top_idx, top_score
+    # scratch of this call alone, allocated on the caller's stream (histograms, prefix states, the k keys)
+    wsb = int(_lib.load().fpm_rank_select_ws_bytes(P))
+    ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
+    _lib.call("fpm_rank_select", _p(scores), ld, P, G, k, _p(top_idx), _p(top_score), _p(ws), wsb, _stream(scores))
+    return top_idx, top_score
+
+
+COARSE_NMAX = 128
+
+
+def _bf16_rne(t):
+    """fp32 -> the nearest bf16 value (ties to even), as fp32."""
+    return t.to(torch.bfloat16).to(torch.float32)
+
+
+def _coarse_score_host(y, row_off, idx, yp, coef, iters, tau, dtype):
+    """The definition of the coarse score in plain torch (``dtype`` fp32 or fp64 arithmetic on the
+    bf16-rounded operands): Kp = softplus(a b^T) - 0.5, pygmtools' log Sinkhorn with dummy rows,
+    sum P o Kp / min(n0, n_g)."""
+    n0 = int(yp.shape[0])
+    out = torch.empty(int(idx.numel()), dtype=dtype)
+    for b, g in enumerate(idx.tolist()):
+        r0, r1 = int(row_off[g]), int(row_off[g + 1])
+        a = _bf16_rne(yp * coef[b]).to(dtype)                 # one fp32 multiply, rounded once
+        bm = _bf16_rne(y[r0:r1]).to(dtype)
+        Kp = torch.nn.functional.softplus(a @ bm.t()) - 0.5
+        L = Kp / tau
+        r, c = n0, r1 - r0
+        if r > c:
+            L, r, c = L.t(), c, r
+        if c > r:
+            L = torch.cat([L, torch.full((c - r, c), -100.0, dtype=dtype)], 0)
+        for i in range(iters):
+            L = L - torch.logsumexp(L, 1 if i % 2 == 0 else 0, keepdim=True)
+            L = torch.where(torch.isnan(L), torch.full_like(L, -float("inf")), L)
+        Pm = torch.exp(L[:r])
+        if n0 > r1 - r0:
+            Pm = Pm.t()
+        out[b] = (Pm * Kp).sum() / min(n0, r1 - r0)
+    return out
+
+
+def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
+                 dtype=None):
+    """Coarse 1:N score of one probe against gallery entries idx[b] of a ragged index
+    (fpm_coarse_score) -> (B,) fp32:
+
+        a = bf16(yp o coef[b]), b = bf16(y rows of entry idx[b]), Kp = softplus(a b^T) - 0.5,
+        P = Sinkhorn(Kp; dummy rows, iters, tau), score[b] = sum P o Kp / min(n0, n_g).
+
+    y (sum n_g, 768) fp32 with row_off int64 [G + 1] and idx int32 [B] as ``rows_gather_scale`` takes
+    them; yp (n0, 768) fp32, the probe's SplineConv rows; coef (B, 768) fp32 (``coef_tanh``).  Checked
+    on the host before anything is launched: dtypes, contiguity and devices, every idx in [0, G),
+    n0 and every selected n_g in [1, COARSE_NMAX = 128] (``idx_host`` / ``row_off_host``: host
+    copies, so the check needs no device synchronisation).
+
+    CPU tensors take the plain-torch statement of the definition, in ``dtype`` arithmetic
+    (torch.float32, the default, or torch.float64) on the same bf16-rounded operands."""
+    for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise _lib.FpmError("coarse_score: %s must be a %s tensor (got %s)"
+                                % (name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise _lib.FpmError("coarse_score: %s must be a contiguous 1-d tensor" % name)
+    for name, t in (("y", y), ("yp", yp), ("coef", coef)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
+                or not t.is_contiguous():
+            raise _lib.FpmError("coarse_score: %s must be contiguous fp32 rows of 768 channels" % name)
+    for name, t in (("row_off", row_off), ("idx", idx), ("yp", yp), ("coef", coef), ("out", out)):
+        if t is not None and t.device != y.device:
+            raise _lib.FpmError("coarse_score: %s is on %s, y on %s" % (name, t.device, y.device))
+    G, B, n0 = int(row_off.numel()) - 1, int(idx.numel()), int(yp.shape[0])
+    if G < 1:
+        raise _lib.FpmError("coarse_score: empty gallery")
+    _shape(coef, (B, 768), "coarse_score coef")
+    ih = torch.as_tensor(idx_host if idx_host is not None else idx.cpu()).view(-1).long()
+    oh = torch.as_tensor(row_off_host if row_off_host is not None else row_off.cpu()).view(-1).long()
+    if ih.numel() != B or oh.numel() != G + 1:
+        raise _lib.FpmError("coarse_score: host copies of idx / row_off do not match the device tensors")
+    if int(oh[0]) != 0 or int(oh[-1]) != y.shape[0] or bool((oh[1:] < oh[:-1]).any()):
+        raise _lib.FpmError("coarse_score: row_off must rise from 0 to the %d rows of y" % y.shape[0])
+    if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
+        raise _lib.FpmError("coarse_score: idx value outside [0, %d)" % G)
+    if not 1 <= n0 <= COARSE_NMAX:
+        raise _lib.FpmError("coarse_score: a probe of %d keypoints; the coarse pass takes 1 to COARSE_NMAX = %d"
+                            % (n0, COARSE_NMAX))
+    if B:
+        ng = oh[ih + 1] - oh[ih]
+        if int(ng.max()) > COARSE_NMAX or int(ng.min()) < 1:
+            raise _lib.FpmError("coarse_score: a selected entry has n_g = %d; the coarse pass takes 1 to "
+                                "COARSE_NMAX = %d" % (int(ng.max()) if int(ng.max()) > COARSE_NMAX else int(ng.min()),
+                                                      COARSE_NMAX))
+    iters, tau = int(iters), float(tau)
+    if iters < 0 or not tau > 0:
+        raise _lib.FpmError("coarse_score: iters >= 0 and tau > 0 required")
+    if not y.is_cuda:
+        dtype = dtype or torch.float32
+        if dtype not in (torch.float32, torch.float64):
+            raise _lib.FpmError("coarse_score: the host statement runs in float32 or float64")
+        res = _coarse_score_host(y, oh, ih, yp, coef, iters, tau, dtype)
+        if out is not None:
+            _shape(out, (B,), "coarse_score out")
+            out.copy_(res)
+            return out
+        return res
+    if dtype is not None:
+        raise _lib.FpmError("coarse_score: dtype selects the host statement's arithmetic; the kernel is fp32")
+    if out is None:
+        out = torch.empty(B, device=y.device, dtype=torch.float32)
+    _shape(out, (B,), "coarse_score out")
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.FpmError("coarse_score: out must be contiguous fp32")
+    if B:
+        _lib.call("fpm_coarse_score", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau, _p(out),
+                  _stream(y))
+    return out
 
 
 def edge_diff(x, src, dst):

@@ -510,6 +510,31 @@ int fpm_feature_align_bwd(const float* nodes, const long* node_shape, const long
  * scores go to the lower index; NaN ranks after every number (NaNs among themselves by index); -0
  * ranks below +0.  No reference counterpart (the reference scores one pair at a time). */
 int fpm_rank_topk(const float* scores, long ld, int P, int G, int k, int* top_idx, float* top_score, void* stream);
+/* The same ranking for 1 <= k <= min(G, FPM_RANK_SELECT_KMAX = 1024) at a cost that does not grow with
+ * k passes over the row: a radix search for the k-th largest 64-bit key (six digit passes, several
+ * workgroups per row, integer histograms), a compaction of the keys at or above it and a sort of
+ * those k in LDS.  Keys are unique, so the result has one answer: equal to fpm_rank_topk for
+ * k <= 128.  ws: fpm_rank_select_ws_bytes(P) bytes of device scratch, owned by the call until the
+ * stream has run it (the entry point clears it on the stream). */
+#define FPM_RANK_SELECT_KMAX 1024
+long fpm_rank_select_ws_bytes(int P);
+int fpm_rank_select(const float* scores, long ld, int P, int G, int k, int* top_idx, float* top_score, void* ws,
+                    long ws_bytes, void* stream);
+
+/* ---- coarse 1:N score (the first pass of a shortlisted identification) ---------------------------
+ * One scalar per (probe, enrolled entry) pair, one workgroup per pair, B pairs per launch:
+ *   a = bf16(yp o coef[b]) (one fp32 multiply, round to nearest even), b = bf16(y rows of idx[b]),
+ *   Kp = softplus(a b^T) - 0.5 (bf16 MFMA, fp32 accumulation),
+ *   P = pygmtools' log Sinkhorn of Kp / tau over iters steps with dummy rows (transposed when
+ *   n0 > n_g), score[b] = sum_{i < n0, j < n_g} P_ij Kp_ij / min(n0, n_g).
+ * y / row_off / idx / G as fpm_rows_gather_scale takes them; yp: the probe's n0 x 768 fp32 rows;
+ * coef: B x 768 fp32 (fpm_coef_tanh's output).  n0 and every selected n_g lie in
+ * [1, FPM_COARSE_NMAX]; the caller checks idx and n_g (a pair that violates either reads no rows
+ * and gets NaN).  The n0 x n_g block lives in LDS and registers only; every sum runs in an order
+ * fixed by the pair, so score[b] does not depend on the launch.  68.6 KB of LDS per workgroup. */
+#define FPM_COARSE_NMAX 128
+int fpm_coarse_score(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp, int n0,
+                     const float* coef, int iters, float tau, float* score, void* stream);
 
 /* ---- profiling hooks: HIP-event timing of the dominant kernel (edge-message GEMM) ------------ */
 int fpm_profile_enable(int on);

@@ -3,6 +3,11 @@
 ``DeviceBatch.from_probe_gallery``) on the same graphs.  GPU.
 
     python tools/identify_bench.py [--gallery 1024] [--n 128] [--reps 7] [--out profiles/identify_c4.json]
+    python tools/identify_bench.py --shortlist 64 [--large 16384]      (-> profiles/identify_shortlist.json)
+
+``--shortlist M``: by the same protocol, the shortlisted query ``identify(shortlist=M)`` against the
+full ``identify`` in one process, at the C4 shape and at a larger gallery, with the coarse pass
+(ms and index bytes per second), the selection and the M-pair forward each timed alone.
 
 Shape: config C4 (one probe, n = 128 keypoints, a gallery of 1024), both dtypes.  Per dtype, in a
 fresh child process under its own time limit: one warm-up, then ``--reps`` (>= 5) timed forwards of
@@ -122,8 +127,114 @@ def child(args):
     print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
 
 
+def _ev(samples):
+    ev = sorted(s[0] for s in samples)
+    return dict(event_ms=[round(x, 3) for x in ev], in_order_ms=[round(s[0], 3) for s in samples],
+                median_ms=round(statistics.median(ev), 3), min_ms=round(ev[0], 3), max_ms=round(ev[-1], 3),
+                wall_median_ms=round(statistics.median(s[1] for s in samples), 3))
+
+
+def child_shortlist(args):
+    """``--shortlist M``: the shortlisted query (coarse pass, selection, M-pair forward) against the
+    full ``identify`` over the same gallery, in this one process; and each part alone."""
+    import torch
+    import bench
+    import fpm
+    from fpm import ops, params, synth
+    dev = torch.device("cuda", 0)
+    G, n, dtype, M = args.gallery, args.n, args.child, args.shortlist
+    probe = synth.make_graph(args.seed, 0, 0, n)
+    base = bench.make_gallery(args.seed, 1, min(G, args.distinct), n, args.gen_workers)
+    gallery = [base[i % len(base)] for i in range(G)]      # past --distinct graphs the gallery repeats them
+    net = fpm.Net(regression=True, backbone=False, dtype=dtype)
+    net.load_state_dict(params.init_params(args.seed))
+    index = net.enroll(gallery, dev)
+    torch.cuda.synchronize()
+    del gallery, base
+    row_bytes = int(index.y.numel()) * 4
+    res = dict(dtype=dtype, gallery=G, distinct_graphs=min(G, args.distinct), n=n, shortlist=M, sc_mode=index.sc_mode,
+               reps=args.reps, index_mb=round(index.nbytes() / 2 ** 20, 1), row_bytes=row_bytes)
+    # warm-ups; the full query last, so its timed runs find the index's whole-gallery selection staged
+    # (as a service that only runs full queries would), not the shortlist's
+    short = net.identify(probe, index, topk=10, shortlist=M)
+    full = net.identify(probe, index, topk=10)
+    torch.cuda.synchronize()
+    sidx = short["short_idx"]
+    res["full_top10"] = full["top_idx"].tolist()
+    res["short_top10"] = short["top_idx"].tolist()
+    res["full_top10_in_shortlist"] = len(set(full["top_idx"].tolist()) & set(sidx.tolist()))
+    call = short["coarse_all"].view(1, -1).clone()
+    del full, short
+
+    def series(fn):
+        # one warm-up of this very call, then the timed queries
+        fn()
+        torch.cuda.synchronize()
+        return _ev(_timed(fn, args.reps))
+
+    def fresh(fn):
+        # a repeated probe repeats its shortlist; drop the index's staged selection so that every
+        # timed shortlisted query stages its M entries, as a new probe's would
+        index._sel = None
+        return fn()
+    # the full query keeps the index's whole-gallery selection staged across its runs, as a service
+    # that only runs full queries would
+    res["full"] = series(lambda: net.identify(probe, index, topk=10))
+    res["shortlisted"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, shortlist=M)))
+    res["coarse"] = series(lambda: net.coarse_scores(probe, index))
+    res["coarse"]["index_tb_per_s"] = round(row_bytes / res["coarse"]["median_ms"] / 1e9, 3)
+    res["coarse"]["fraction_of_5p5_tb_per_s"] = round(res["coarse"]["index_tb_per_s"] / 5.5, 3)
+    res["select"] = series(lambda: ops.rank_select(call, M))
+    res["forward_M"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, select=sidx)))
+    f, s = res["full"], res["shortlisted"]
+    res["speedup_median"] = round(f["median_ms"] / s["median_ms"], 2)
+    # the project's A/B rule: the candidate's median beats the baseline's best run by more than the
+    # baseline's own spread
+    res["ab_margin_ms"] = round(f["min_ms"] - (f["max_ms"] - f["min_ms"]) - s["median_ms"], 3)
+    res["ab_pass"] = res["ab_margin_ms"] > 0
+    print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
+
+
+def main_shortlist(ap, args):
+    lines = []
+    shapes = [(args.gallery, dt) for dt in args.dtypes.split(",")]
+    if args.large:
+        shapes.append((args.large, args.dtypes.split(",")[0]))
+    for G, dtype in shapes:
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", dtype, "--gallery", str(G), "--n", str(args.n),
+               "--reps", str(args.reps), "--seed", str(args.seed), "--gen-workers", str(args.gen_workers),
+               "--shortlist", str(args.shortlist), "--distinct", str(args.distinct)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
+        except subprocess.TimeoutExpired:
+            sys.exit("identify_bench: the %s x %d step ran over its %d s limit; stopping" % (dtype, G, args.step_timeout))
+        got = [l for l in r.stdout.splitlines() if l.startswith("IDENTIFY_BENCH ")]
+        if r.returncode != 0 or not got:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            sys.exit("identify_bench: the %s x %d step failed (exit %d); stopping" % (dtype, G, r.returncode))
+        lines.append(json.loads(got[-1][len("IDENTIFY_BENCH "):]))
+        print(json.dumps(lines[-1]), flush=True)
+    out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", "identify_shortlist.json")
+    doc = dict(tool="tools/identify_bench.py --shortlist %d" % args.shortlist,
+               config="1 probe x gallery, n keypoints per graph; full = identify over every entry (the path before "
+                      "the shortlist existed), shortlisted = coarse pass + rank_select + identify over the M entries",
+               method="1 warm-up, `reps` queries each, HIP events around each query, median and min-max; both sides "
+                      "in one process; a fresh process per shape",
+               results=lines)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print("wrote %s" % out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--shortlist", type=int, default=0,
+                    help="M > 0: time identify(shortlist=M) against the full identify (profiles/identify_shortlist.json)")
+    ap.add_argument("--large", type=int, default=16384, help="--shortlist: a second, larger gallery (0: none)")
+    ap.add_argument("--distinct", type=int, default=1024,
+                    help="--shortlist: distinct graphs generated; a larger gallery repeats them (rows are enrolled apart)")
     ap.add_argument("--gallery", type=int, default=1024)
     ap.add_argument("--n", type=int, default=128)
     ap.add_argument("--reps", type=int, default=7)
@@ -137,7 +248,9 @@ def main():
     if args.reps < 5:
         ap.error("--reps must be at least 5")
     if args.child:
-        return child(args)
+        return child_shortlist(args) if args.shortlist > 0 else child(args)
+    if args.shortlist > 0:
+        return main_shortlist(ap, args)
     lines = []
     for dtype in args.dtypes.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", dtype, "--gallery", str(args.gallery), "--n",
