@@ -9,7 +9,8 @@ every output equals ``net.run(DeviceBatch.from_probe_gallery(probe, gallery))`` 
 ranks the pair scores on the device (``fpm_rank_topk``).
 
 ``identify(shortlist=M)`` puts a coarse pass in front: ``coarse_scores`` (one fused kernel per pair,
-``fpm_coarse_score``: bf16 vertex affinity, Sinkhorn and <P, Kp> without the block leaving the CU)
+``fpm_coarse_score``: bf16 vertex affinity, Sinkhorn and <P, Kp> without the block leaving the CU;
+``coarse="wide"`` / ``"auto"``: ``fpm_coarse_score_wide`` for boxes of up to 256 keypoints)
 over the selected entries, ``fpm_rank_select`` to the M best, and the forward above over those alone.
 
 Size of an index: 768 fp32 channels = 3 KB per keypoint (0.39 MB per template at n = 128, 0.4 GB per
@@ -323,13 +324,37 @@ def _select_host(index, select, what):
     return sel
 
 
-def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk):
-    """One probe's coarse scores over the entries ``sel`` into ``out`` (len(sel),)."""
+COARSE_ROUTES = ("fused", "wide", "auto")
+
+
+def _check_coarse(coarse, what):
+    if coarse not in COARSE_ROUTES:
+        raise FpmError("%s: coarse must be one of %s" % (what, COARSE_ROUTES))
+
+
+def _coarse_launch(wide, index, sel_d, sel32, yp, cf, out, iters, tau):
+    op = ops.coarse_score_wide if wide else ops.coarse_score
+    op(index.y, index.row_off, sel_d, yp, cf, iters=iters, tau=tau, out=out, idx_host=sel32,
+       row_off_host=index.row_off_host)
+
+
+def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk, coarse="fused"):
+    """One probe's coarse scores over the entries ``sel`` into ``out`` (len(sel),).  ``coarse``: the
+    kernel, "fused" (boxes up to COARSE_NMAX), "wide" (up to COARSE_WIDE_NMAX) or "auto" (per pair:
+    fused when both sides fit COARSE_NMAX, wide otherwise -- the route depends on the pair alone)."""
     n0 = int(probe["n"])
     ng = index.n[sel]
-    if n0 > ops.COARSE_NMAX or n0 < 1 or int(ng.max()) > ops.COARSE_NMAX:
-        raise FpmError("coarse_scores: a graph of %d keypoints; the coarse pass takes boxes up to COARSE_NMAX = %d "
-                       "(identify without a shortlist has no such bound)" % (max(n0, int(ng.max())), ops.COARSE_NMAX))
+    if coarse == "fused":
+        if n0 > ops.COARSE_NMAX or n0 < 1 or int(ng.max()) > ops.COARSE_NMAX:
+            raise FpmError("coarse_scores: a graph of %d keypoints; the coarse pass takes boxes up to COARSE_NMAX = %d "
+                           "(identify without a shortlist has no such bound)"
+                           % (max(n0, int(ng.max())), ops.COARSE_NMAX))
+    elif n0 > ops.COARSE_WIDE_NMAX or n0 < 1 or int(ng.max()) > ops.COARSE_WIDE_NMAX:
+        raise FpmError("coarse_scores: a graph of %d keypoints; the wide coarse pass takes boxes up to "
+                       "COARSE_WIDE_NMAX = %d (identify without a shortlist has no such bound)"
+                       % (max(n0, int(ng.max())), ops.COARSE_WIDE_NMAX))
+    # per pair: True -> the wide kernel (host copy of n: no synchronisation)
+    to_wide = torch.as_tensor(ng).view(-1) > ops.COARSE_NMAX if coarse == "auto" and n0 <= ops.COARSE_NMAX else None
     ps = _ProbeSide(probe, index)
     yp = net._probe_rows(wp, ps)
     sel32 = sel.to(torch.int32)
@@ -342,12 +367,24 @@ def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk):
         gw = ops.global_weights(w0[:b1 - b0], index.w[sel_d[b0:b1].long()])
         cf = coef[:b1 - b0]
         ops.coef_tanh(gw, wp["aff_wT"], wp["aff_b"], cf)
-        ops.coarse_score(index.y, index.row_off, sel_d[b0:b1], yp, cf, iters=C.SK_ITER_NUM, tau=net.tau,
-                         out=out[b0:b1], idx_host=sel32[b0:b1], row_off_host=index.row_off_host)
+        mixed = to_wide is not None and bool(to_wide[b0:b1].any()) and not bool(to_wide[b0:b1].all())
+        if not mixed:
+            wide = coarse == "wide" or (coarse == "auto" and (to_wide is None or bool(to_wide[b0])))
+            _coarse_launch(wide, index, sel_d[b0:b1], sel32[b0:b1], yp, cf, out[b0:b1], C.SK_ITER_NUM, net.tau)
+            continue
+        # both kernels in this chunk: each part's entries and coefficient rows, the scores scattered back
+        for wide in (False, True):
+            pos = torch.nonzero(to_wide[b0:b1] == wide).view(-1)
+            pos_d = pos.to(index.device)
+            part = torch.empty(int(pos.numel()), device=index.device, dtype=torch.float32)
+            _coarse_launch(wide, index, sel_d[b0:b1][pos_d].contiguous(), sel32[b0:b1][pos],
+                           yp, cf[pos_d].contiguous(), part, C.SK_ITER_NUM, net.tau)
+            out[b0:b1][pos_d] = part
 
 
-def coarse_scores(net, probes, index, select=None, chunk=COARSE_CHUNK):
+def coarse_scores(net, probes, index, select=None, chunk=COARSE_CHUNK, coarse="fused"):
     """``Net.coarse_scores``: see there."""
+    _check_coarse(coarse, "coarse_scores")
     _check_query(net, index, "coarse_scores")
     sel = _select_host(index, select, "coarse_scores")
     single = isinstance(probes, dict)
@@ -358,12 +395,14 @@ def coarse_scores(net, probes, index, select=None, chunk=COARSE_CHUNK):
     with torch.cuda.device(dev):
         sel_d = sel.to(dev).to(torch.int32).contiguous()
         for i, p in enumerate(plist):
-            _coarse_one(net, wp, p, index, sel, sel_d, out[i], chunk)
+            _coarse_one(net, wp, p, index, sel, sel_d, out[i], chunk, coarse)
     return out
 
 
-def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None, shortlist=None):
+def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None, shortlist=None,
+             coarse="fused"):
     """``Net.identify``: see there."""
+    _check_coarse(coarse, "identify")
     if net.training:
         raise FpmError("identify: inference only (call net.eval()); training through an index is not supported")
     if net.use_graphs:
@@ -372,7 +411,7 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
         raise FpmError("identify: score must be one of %s" % (SCORES,))
     _check_query(net, index, "identify")
     if shortlist is not None:
-        return _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist)
+        return _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist, coarse)
     single = isinstance(probes, dict)
     plist = [probes] if single else list(probes)
     outs, sel = [], None
@@ -396,7 +435,7 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
     return outs[0] if single else outs
 
 
-def _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist):
+def _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist, coarse="fused"):
     """``identify(shortlist=M)``: per probe the coarse pass over ``select``, the M best entries
     (``ops.rank_select``), and the plain ``identify`` over exactly those, in coarse-rank order."""
     M = int(shortlist)
@@ -409,7 +448,7 @@ def _identify_shortlist(net, probes, index, topk, select, score, chunks, shortli
     outs = []
     if not plist:
         return outs
-    call = coarse_scores(net, plist, index, select=sel)
+    call = coarse_scores(net, plist, index, select=sel, coarse=coarse)
     with torch.cuda.device(index.device):
         pos, csc = ops.rank_select(call, M)
         short = sel.to(index.device)[pos.long()].to(torch.int32)

@@ -1469,7 +1469,7 @@ class Net(nn.Module):
         from . import gallery
         return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch)
 
-    def coarse_scores(self, probes, index, select=None):
+    def coarse_scores(self, probes, index, select=None, coarse="fused"):
         """The coarse first pass of a shortlisted identification: for each probe graph (one dict, or a
         list) one cheap score per gallery entry of ``select`` (default all) -> (P, len(select)) fp32 on
         the index's device.  Per pair: Kp = softplus(a b^T) - 0.5 on single-bf16 operands (the probe's
@@ -1478,11 +1478,19 @@ class Net(nn.Module):
         sum P o Kp / min(n0, n_g): the entropy-relaxed assignment value of the vertex affinity per
         matched keypoint (``ops.coarse_score``; one fused kernel, the block never leaves the CU).
         The gallery is walked in bounded chunks, so the scratch does not grow with it.  Boxes of at
-        most ``ops.COARSE_NMAX`` = 128 keypoints; the refusals of ``identify`` apply."""
-        from . import gallery
-        return gallery.coarse_scores(self, probes, index, select=select)
+        most ``ops.COARSE_NMAX`` = 128 keypoints; the refusals of ``identify`` apply.
 
-    def identify(self, probes, index, topk=10, select=None, shortlist=None, score="cls_prob", chunks=None):
+        ``coarse`` picks the kernel: "fused" (the default) as above; "wide": every pair through
+        ``ops.coarse_score_wide`` (the block in registers, Kp parked in at most 64 MB of scratch), boxes
+        of at most ``ops.COARSE_WIDE_NMAX`` = 256 keypoints; "auto": per pair, the fused kernel when
+        probe and entry both have at most 128 keypoints and the wide one otherwise (refused over 256).
+        Both kernels compute the same definition and agree to fp32 rounding, not bit for bit; the
+        route depends on the pair alone, so a score does not depend on what else is selected."""
+        from . import gallery
+        return gallery.coarse_scores(self, probes, index, select=select, coarse=coarse)
+
+    def identify(self, probes, index, topk=10, select=None, shortlist=None, score="cls_prob", chunks=None,
+                 coarse="fused"):
         """1:N identification against an enrolled gallery: for each probe graph (one dict, or a list)
         the shared-probe forward over the gallery entries ``select`` (an index list; default all),
         with side 1's operand rows gathered from ``index`` (no SplineConv for the gallery side) --
@@ -1498,10 +1506,12 @@ class Net(nn.Module):
         forward above over exactly those, in coarse-rank order -- every output equals
         ``identify(probe, index, select=short_idx)`` bit for bit.  The dict then also carries
         ``short_idx`` (M, int32 gallery entry numbers), ``coarse_score`` (M) and ``coarse_all``
-        (len(select))."""
+        (len(select)).  ``coarse`` ("fused", "wide" or "auto": see ``coarse_scores``) picks the coarse
+        pass's kernel: the default takes boxes of at most 128 keypoints, "wide" and "auto" boxes of at
+        most 256; without a shortlist it is only checked: the full query has no size bound."""
         from . import gallery
         return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
-                                shortlist=shortlist)
+                                shortlist=shortlist, coarse=coarse)
 
     def image_features(self, images, Ps, ns, dev=None):
         """ngm.py:226-248 on the device: per side, node_layers/edge_layers (ResNet-18 convolutions

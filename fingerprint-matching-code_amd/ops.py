@@ -462,6 +462,7 @@ def rank_select(scores, k, top_idx=None, top_score=None):
 
 
 COARSE_NMAX = 128
+COARSE_WIDE_NMAX = 256          # ``coarse_score_wide``: the block in registers
 
 
 def _bf16_rne(t):
@@ -496,6 +497,68 @@ def _coarse_score_host(y, row_off, idx, yp, coef, iters, tau, dtype):
     return out
 
 
+def _coarse_score_op(op, bound, nmax, launch, y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host,
+                     dtype):
+    """The host-side checks and dispatch shared by ``coarse_score`` and ``coarse_score_wide``: ``op`` names
+    the operation in every message, ``bound`` / ``nmax`` the size limit of its kernel;
+    ``launch(G, B, n0, iters, tau, out)`` runs the kernel once everything has been checked."""
+    for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise _lib.FpmError("%s: %s must be a %s tensor (got %s)"
+                                % (op, name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise _lib.FpmError("%s: %s must be a contiguous 1-d tensor" % (op, name))
+    for name, t in (("y", y), ("yp", yp), ("coef", coef)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
+                or not t.is_contiguous():
+            raise _lib.FpmError("%s: %s must be contiguous fp32 rows of 768 channels" % (op, name))
+    for name, t in (("row_off", row_off), ("idx", idx), ("yp", yp), ("coef", coef), ("out", out)):
+        if t is not None and t.device != y.device:
+            raise _lib.FpmError("%s: %s is on %s, y on %s" % (op, name, t.device, y.device))
+    G, B, n0 = int(row_off.numel()) - 1, int(idx.numel()), int(yp.shape[0])
+    if G < 1:
+        raise _lib.FpmError("%s: empty gallery" % op)
+    _shape(coef, (B, 768), "%s coef" % op)
+    ih = torch.as_tensor(idx_host if idx_host is not None else idx.cpu()).view(-1).long()
+    oh = torch.as_tensor(row_off_host if row_off_host is not None else row_off.cpu()).view(-1).long()
+    if ih.numel() != B or oh.numel() != G + 1:
+        raise _lib.FpmError("%s: host copies of idx / row_off do not match the device tensors" % op)
+    if int(oh[0]) != 0 or int(oh[-1]) != y.shape[0] or bool((oh[1:] < oh[:-1]).any()):
+        raise _lib.FpmError("%s: row_off must rise from 0 to the %d rows of y" % (op, y.shape[0]))
+    if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
+        raise _lib.FpmError("%s: idx value outside [0, %d)" % (op, G))
+    if not 1 <= n0 <= nmax:
+        raise _lib.FpmError("%s: a probe of %d keypoints; the coarse pass takes 1 to %s = %d" % (op, n0, bound, nmax))
+    if B:
+        ng = oh[ih + 1] - oh[ih]
+        if int(ng.max()) > nmax or int(ng.min()) < 1:
+            raise _lib.FpmError("%s: a selected entry has n_g = %d; the coarse pass takes 1 to "
+                                "%s = %d" % (op, int(ng.max()) if int(ng.max()) > nmax else int(ng.min()), bound, nmax))
+    iters, tau = int(iters), float(tau)
+    if iters < 0 or not tau > 0:
+        raise _lib.FpmError("%s: iters >= 0 and tau > 0 required" % op)
+    if not y.is_cuda:
+        dtype = dtype or torch.float32
+        if dtype not in (torch.float32, torch.float64):
+            raise _lib.FpmError("%s: the host statement runs in float32 or float64" % op)
+        res = _coarse_score_host(y, oh, ih, yp, coef, iters, tau, dtype)
+        if out is not None:
+            _shape(out, (B,), "%s out" % op)
+            out.copy_(res)
+            return out
+        return res
+    if dtype is not None:
+        raise _lib.FpmError("%s: dtype selects the host statement's arithmetic; the kernel is fp32" % op)
+    if out is None:
+        out = torch.empty(B, device=y.device, dtype=torch.float32)
+    _shape(out, (B,), "%s out" % op)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.FpmError("%s: out must be contiguous fp32" % op)
+    if B:
+        launch(G, B, n0, iters, tau, out)
+    return out
+
+
 def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
                  dtype=None):
     """Coarse 1:N score of one probe against gallery entries idx[b] of a ragged index
@@ -512,64 +575,29 @@ def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_ho
 
     CPU tensors take the plain-torch statement of the definition, in ``dtype`` arithmetic
     (torch.float32, the default, or torch.float64) on the same bf16-rounded operands."""
-    for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt:
-            raise _lib.FpmError("coarse_score: %s must be a %s tensor (got %s)"
-                                % (name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
-        if t.dim() != 1 or not t.is_contiguous():
-            raise _lib.FpmError("coarse_score: %s must be a contiguous 1-d tensor" % name)
-    for name, t in (("y", y), ("yp", yp), ("coef", coef)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
-                or not t.is_contiguous():
-            raise _lib.FpmError("coarse_score: %s must be contiguous fp32 rows of 768 channels" % name)
-    for name, t in (("row_off", row_off), ("idx", idx), ("yp", yp), ("coef", coef), ("out", out)):
-        if t is not None and t.device != y.device:
-            raise _lib.FpmError("coarse_score: %s is on %s, y on %s" % (name, t.device, y.device))
-    G, B, n0 = int(row_off.numel()) - 1, int(idx.numel()), int(yp.shape[0])
-    if G < 1:
-        raise _lib.FpmError("coarse_score: empty gallery")
-    _shape(coef, (B, 768), "coarse_score coef")
-    ih = torch.as_tensor(idx_host if idx_host is not None else idx.cpu()).view(-1).long()
-    oh = torch.as_tensor(row_off_host if row_off_host is not None else row_off.cpu()).view(-1).long()
-    if ih.numel() != B or oh.numel() != G + 1:
-        raise _lib.FpmError("coarse_score: host copies of idx / row_off do not match the device tensors")
-    if int(oh[0]) != 0 or int(oh[-1]) != y.shape[0] or bool((oh[1:] < oh[:-1]).any()):
-        raise _lib.FpmError("coarse_score: row_off must rise from 0 to the %d rows of y" % y.shape[0])
-    if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
-        raise _lib.FpmError("coarse_score: idx value outside [0, %d)" % G)
-    if not 1 <= n0 <= COARSE_NMAX:
-        raise _lib.FpmError("coarse_score: a probe of %d keypoints; the coarse pass takes 1 to COARSE_NMAX = %d"
-                            % (n0, COARSE_NMAX))
-    if B:
-        ng = oh[ih + 1] - oh[ih]
-        if int(ng.max()) > COARSE_NMAX or int(ng.min()) < 1:
-            raise _lib.FpmError("coarse_score: a selected entry has n_g = %d; the coarse pass takes 1 to "
-                                "COARSE_NMAX = %d" % (int(ng.max()) if int(ng.max()) > COARSE_NMAX else int(ng.min()),
-                                                      COARSE_NMAX))
-    iters, tau = int(iters), float(tau)
-    if iters < 0 or not tau > 0:
-        raise _lib.FpmError("coarse_score: iters >= 0 and tau > 0 required")
-    if not y.is_cuda:
-        dtype = dtype or torch.float32
-        if dtype not in (torch.float32, torch.float64):
-            raise _lib.FpmError("coarse_score: the host statement runs in float32 or float64")
-        res = _coarse_score_host(y, oh, ih, yp, coef, iters, tau, dtype)
-        if out is not None:
-            _shape(out, (B,), "coarse_score out")
-            out.copy_(res)
-            return out
-        return res
-    if dtype is not None:
-        raise _lib.FpmError("coarse_score: dtype selects the host statement's arithmetic; the kernel is fp32")
-    if out is None:
-        out = torch.empty(B, device=y.device, dtype=torch.float32)
-    _shape(out, (B,), "coarse_score out")
-    if out.dtype != torch.float32 or not out.is_contiguous():
-        raise _lib.FpmError("coarse_score: out must be contiguous fp32")
-    if B:
+    def launch(G, B, n0, iters, tau, out):
         _lib.call("fpm_coarse_score", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau, _p(out),
                   _stream(y))
-    return out
+    return _coarse_score_op("coarse_score", "COARSE_NMAX", COARSE_NMAX, launch, y, row_off, idx, yp, coef, iters, tau,
+                            out, idx_host, row_off_host, dtype)
+
+
+def coarse_score_wide(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
+                      dtype=None):
+    """``coarse_score`` for boxes of up to COARSE_WIDE_NMAX = 256 keypoints (fpm_coarse_score_wide): the
+    same definition, arguments and host-side checks, with n0 and every selected n_g in
+    [1, COARSE_WIDE_NMAX].  The kernel keeps the block in registers and parks Kp in a scratch of
+    min(B, 256) slots of 256 KB (at most 64 MB whatever B), allocated here on the caller's stream.
+    Its sums run in another order than ``coarse_score``'s, so the two agree to rounding, not bit for
+    bit, on boxes both take.  CPU tensors take the same plain-torch statement as ``coarse_score``
+    (which has no size bound of its own)."""
+    def launch(G, B, n0, iters, tau, out):
+        wsb = int(_lib.load().fpm_coarse_score_wide_ws_bytes(B))
+        ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
+        _lib.call("fpm_coarse_score_wide", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau,
+                  _p(out), _p(ws), wsb, _stream(y))
+    return _coarse_score_op("coarse_score_wide", "COARSE_WIDE_NMAX", COARSE_WIDE_NMAX, launch, y, row_off, idx, yp,
+                            coef, iters, tau, out, idx_host, row_off_host, dtype)
 
 
 def edge_diff(x, src, dst):

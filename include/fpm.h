@@ -535,6 +535,24 @@ int fpm_rank_select(const float* scores, long ld, int P, int G, int k, int* top_
 #define FPM_COARSE_NMAX 128
 int fpm_coarse_score(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp, int n0,
                      const float* coef, int iters, float tau, float* score, void* stream);
+/* The same score (the same definition, argument for argument) for boxes of up to 256 keypoints: n0
+ * and every selected n_g lie in [1, FPM_COARSE_WIDE_NMAX]; a pair that violates either, or whose idx
+ * is outside [0, G), reads no rows and gets NaN.  One workgroup of 512 threads per pair; the
+ * n0 x n_g block of L lives in registers (the MFMA accumulators' layout, 128 per thread) and is
+ * updated in place; Kp is parked in fp32 in the workgroup's own 256 KB slot of ws and read back by
+ * the thread that wrote it for the final sum.  The grid is persistent (min(B, 256) workgroups walk the
+ * B pairs), so ws holds fpm_coarse_score_wide_ws_bytes(B) = min(B, 256) * 256 KB, at most 64 MB
+ * whatever B; 16-byte aligned, owned by the call until the stream has run it, never read before it is
+ * written (no clearing needed); a short or missing workspace is an error.  93.0 KB of LDS per
+ * workgroup (operand tiles, the (max, sum) partials of the row and column waves, the dummy rows'
+ * vector).  Every sum runs in an order fixed by the pair, so score[b] depends neither on the launch
+ * nor on the workgroup that computes it.  Not bit-identical to fpm_coarse_score on boxes both
+ * take (other orders of summation); both are held to the same float64 statement. */
+#define FPM_COARSE_WIDE_NMAX 256
+long fpm_coarse_score_wide_ws_bytes(int B);
+int fpm_coarse_score_wide(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp, int n0,
+                          const float* coef, int iters, float tau, float* score, void* ws, long ws_bytes,
+                          void* stream);
 
 /* ---- profiling hooks: HIP-event timing of the dominant kernel (edge-message GEMM) ------------ */
 int fpm_profile_enable(int on);

@@ -4,10 +4,15 @@
 
     python tools/identify_bench.py [--gallery 1024] [--n 128] [--reps 7] [--out profiles/identify_c4.json]
     python tools/identify_bench.py --shortlist 64 [--large 16384]      (-> profiles/identify_shortlist.json)
+    python tools/identify_bench.py --shortlist 64 --coarse wide --n 256 --large 4096
+                                                                       (-> profiles/identify_shortlist_wide.json)
 
 ``--shortlist M``: by the same protocol, the shortlisted query ``identify(shortlist=M)`` against the
 full ``identify`` in one process, at the C4 shape and at a larger gallery, with the coarse pass
 (ms and index bytes per second), the selection and the M-pair forward each timed alone.
+``--coarse wide|auto`` runs the coarse pass on ``fpm_coarse_score_wide`` (boxes of up to 256 keypoints)
+and adds that kernel alone on synthetic rows; at n <= 128 it also times the fused coarse pass over the
+same gallery, the number that decides which kernel small boxes take.
 
 Shape: config C4 (one probe, n = 128 keypoints, a gallery of 1024), both dtypes.  Per dtype, in a
 fresh child process under its own time limit: one warm-up, then ``--reps`` (>= 5) timed forwards of
@@ -142,7 +147,7 @@ def child_shortlist(args):
     import fpm
     from fpm import ops, params, synth
     dev = torch.device("cuda", 0)
-    G, n, dtype, M = args.gallery, args.n, args.child, args.shortlist
+    G, n, dtype, M, coarse = args.gallery, args.n, args.child, args.shortlist, args.coarse
     probe = synth.make_graph(args.seed, 0, 0, n)
     base = bench.make_gallery(args.seed, 1, min(G, args.distinct), n, args.gen_workers)
     gallery = [base[i % len(base)] for i in range(G)]      # past --distinct graphs the gallery repeats them
@@ -153,10 +158,10 @@ def child_shortlist(args):
     del gallery, base
     row_bytes = int(index.y.numel()) * 4
     res = dict(dtype=dtype, gallery=G, distinct_graphs=min(G, args.distinct), n=n, shortlist=M, sc_mode=index.sc_mode,
-               reps=args.reps, index_mb=round(index.nbytes() / 2 ** 20, 1), row_bytes=row_bytes)
+               reps=args.reps, index_mb=round(index.nbytes() / 2 ** 20, 1), row_bytes=row_bytes, coarse=coarse)
     # warm-ups; the full query last, so its timed runs find the index's whole-gallery selection staged
     # (as a service that only runs full queries would), not the shortlist's
-    short = net.identify(probe, index, topk=10, shortlist=M)
+    short = net.identify(probe, index, topk=10, shortlist=M, coarse=coarse)
     full = net.identify(probe, index, topk=10)
     torch.cuda.synchronize()
     sidx = short["short_idx"]
@@ -180,10 +185,37 @@ def child_shortlist(args):
     # the full query keeps the index's whole-gallery selection staged across its runs, as a service
     # that only runs full queries would
     res["full"] = series(lambda: net.identify(probe, index, topk=10))
-    res["shortlisted"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, shortlist=M)))
-    res["coarse"] = series(lambda: net.coarse_scores(probe, index))
-    res["coarse"]["index_tb_per_s"] = round(row_bytes / res["coarse"]["median_ms"] / 1e9, 3)
-    res["coarse"]["fraction_of_5p5_tb_per_s"] = round(res["coarse"]["index_tb_per_s"] / 5.5, 3)
+    res["shortlisted"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, shortlist=M,
+                                                                   coarse=coarse)))
+
+    def coarse_pass(route):
+        r = series(lambda: net.coarse_scores(probe, index, coarse=route))
+        r["index_tb_per_s"] = round(row_bytes / r["median_ms"] / 1e9, 3)
+        r["fraction_of_5p5_tb_per_s"] = round(r["index_tb_per_s"] / 5.5, 3)
+        return r
+    res["coarse"] = coarse_pass(coarse)
+    if coarse != "fused":
+        if n <= ops.COARSE_NMAX:
+            # the same gallery through the fused kernel: which of the two small boxes should take
+            res["coarse_fused"] = coarse_pass("fused")
+            res["wide_over_fused"] = round(res["coarse"]["median_ms"] / res["coarse_fused"]["median_ms"], 3)
+        # the wide kernel alone: synthetic rows (N(0, 0.05)), min(G, 1024) entries of n keypoints, one launch
+        Gs = min(G, 1024)
+        ys = torch.randn(Gs * n, 768, device=dev) * 0.05
+        offs = torch.arange(Gs + 1, dtype=torch.int64) * n
+        ids = torch.arange(Gs, dtype=torch.int32)
+        offs_d, ids_d = offs.to(dev), ids.to(dev)
+        yps = torch.randn(n, 768, device=dev) * 0.05
+        cfs = torch.tanh(torch.randn(Gs, 768, device=dev))
+        outs = torch.empty(Gs, device=dev)
+        res["wide_kernel"] = series(lambda: ops.coarse_score_wide(ys, offs_d, ids_d, yps, cfs, tau=net.tau, out=outs,
+                                                                  idx_host=ids, row_off_host=offs))
+        kb = int(ys.numel()) * 4
+        res["wide_kernel"].update(entries=Gs, row_bytes=kb,
+                                  rows_tb_per_s=round(kb / res["wide_kernel"]["median_ms"] / 1e9, 3),
+                                  us_per_pair_per_cu=round(res["wide_kernel"]["median_ms"] * 1e3 * 256 / Gs, 1),
+                                  note="events around one launch: launch latency and the scratch allocation included")
+        del ys, cfs
     res["select"] = series(lambda: ops.rank_select(call, M))
     res["forward_M"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, select=sidx)))
     f, s = res["full"], res["shortlisted"]
@@ -203,7 +235,7 @@ def main_shortlist(ap, args):
     for G, dtype in shapes:
         cmd = [sys.executable, os.path.abspath(__file__), "--child", dtype, "--gallery", str(G), "--n", str(args.n),
                "--reps", str(args.reps), "--seed", str(args.seed), "--gen-workers", str(args.gen_workers),
-               "--shortlist", str(args.shortlist), "--distinct", str(args.distinct)]
+               "--shortlist", str(args.shortlist), "--distinct", str(args.distinct), "--coarse", args.coarse]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
         except subprocess.TimeoutExpired:
@@ -214,13 +246,20 @@ def main_shortlist(ap, args):
             sys.exit("identify_bench: the %s x %d step failed (exit %d); stopping" % (dtype, G, r.returncode))
         lines.append(json.loads(got[-1][len("IDENTIFY_BENCH "):]))
         print(json.dumps(lines[-1]), flush=True)
-    out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", "identify_shortlist.json")
-    doc = dict(tool="tools/identify_bench.py --shortlist %d" % args.shortlist,
+    name = "identify_shortlist.json" if args.coarse == "fused" else "identify_shortlist_wide.json"
+    out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", name)
+    doc = dict(tool="tools/identify_bench.py --shortlist %d%s" % (args.shortlist, "" if args.coarse == "fused" else
+                                                                  " --coarse %s --n %d" % (args.coarse, args.n)),
                config="1 probe x gallery, n keypoints per graph; full = identify over every entry (the path before "
                       "the shortlist existed), shortlisted = coarse pass + rank_select + identify over the M entries",
                method="1 warm-up, `reps` queries each, HIP events around each query, median and min-max; both sides "
                       "in one process; a fresh process per shape",
                results=lines)
+    if args.append and os.path.exists(out):
+        with open(out) as f:
+            old = json.load(f)
+        doc["tool"] = old["tool"] + "; " + doc["tool"]
+        doc["results"] = old["results"] + lines
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as f:
         json.dump(doc, f, indent=1)
@@ -232,6 +271,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shortlist", type=int, default=0,
                     help="M > 0: time identify(shortlist=M) against the full identify (profiles/identify_shortlist.json)")
+    ap.add_argument("--coarse", choices=("fused", "wide", "auto"), default="fused",
+                    help="--shortlist: the coarse pass's kernel (wide / auto: profiles/identify_shortlist_wide.json)")
+    ap.add_argument("--append", action="store_true",
+                    help="--shortlist: add the results to those the output file already holds (another --n)")
     ap.add_argument("--large", type=int, default=16384, help="--shortlist: a second, larger gallery (0: none)")
     ap.add_argument("--distinct", type=int, default=1024,
                     help="--shortlist: distinct graphs generated; a larger gallery repeats them (rows are enrolled apart)")
