@@ -50,6 +50,8 @@ SIGNATURES = {
     "fpm_coarse_score": (I, [P, P, P, I, I, P, I, P, I, F, P, P]),
     "fpm_coarse_score_wide_ws_bytes": (L, [I]),
     "fpm_coarse_score_wide": (I, [P, P, P, I, I, P, I, P, I, F, P, P, L, P]),
+    "fpm_coarse_score_stream_ws_bytes": (L, [I, I, I]),
+    "fpm_coarse_score_stream": (I, [P, P, P, I, I, P, I, P, I, F, P, P, L, P]),
     "fpm_edge_diff_padded": (I, [P, P, P, P, P, P, L, I, P, P]),
     "fpm_kron_gnn_layer_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fpm_kron_gnn_layer_fwd_ord": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),

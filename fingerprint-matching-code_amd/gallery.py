@@ -10,7 +10,8 @@ ranks the pair scores on the device (``fpm_rank_topk``).
 
 ``identify(shortlist=M)`` puts a coarse pass in front: ``coarse_scores`` (one fused kernel per pair,
 ``fpm_coarse_score``: bf16 vertex affinity, Sinkhorn and <P, Kp> without the block leaving the CU;
-``coarse="wide"`` / ``"auto"``: ``fpm_coarse_score_wide`` for boxes of up to 256 keypoints)
+``coarse="wide"`` / ``"auto"``: ``fpm_coarse_score_wide`` for boxes of up to 256 keypoints;
+``"stream"`` / ``"any"``: ``fpm_coarse_score_stream`` for every box the matcher takes, up to 600)
 over the selected entries, ``fpm_rank_select`` to the M best, and the forward above over those alone.
 
 Size of an index: 768 fp32 channels = 3 KB per keypoint (0.39 MB per template at n = 128, 0.4 GB per
@@ -324,7 +325,8 @@ def _select_host(index, select, what):
     return sel
 
 
-COARSE_ROUTES = ("fused", "wide", "auto")
+COARSE_ROUTES = ("fused", "wide", "auto", "stream", "any")
+_COARSE_OPS = (ops.coarse_score, ops.coarse_score_wide, ops.coarse_score_stream)     # by route number
 
 
 def _check_coarse(coarse, what):
@@ -332,29 +334,49 @@ def _check_coarse(coarse, what):
         raise FpmError("%s: coarse must be one of %s" % (what, COARSE_ROUTES))
 
 
-def _coarse_launch(wide, index, sel_d, sel32, yp, cf, out, iters, tau):
-    op = ops.coarse_score_wide if wide else ops.coarse_score
-    op(index.y, index.row_off, sel_d, yp, cf, iters=iters, tau=tau, out=out, idx_host=sel32,
-       row_off_host=index.row_off_host)
+def coarse_routes(n0, ng, coarse="any"):
+    """The kernel of each pair of a probe of ``n0`` keypoints and entries of ``ng`` keypoints (host
+    tensor), by number: 0 fused, 1 wide, 2 stream -> host int64 tensor.  "fused" / "wide" / "stream":
+    that kernel for every pair; "auto": fused when both sides fit COARSE_NMAX, wide otherwise; "any":
+    fused when both sides fit COARSE_NMAX, wide when both fit COARSE_WIDE_NMAX, stream otherwise.
+    The route depends on the pair alone.  Refuses what the route's largest kernel does not take."""
+    _check_coarse(coarse, "coarse_scores")
+    n0 = int(n0)
+    ng = torch.as_tensor(ng).view(-1).long().cpu()
+    top = max(n0, int(ng.max()))
+    low = min(n0, int(ng.min()))
+    if coarse == "fused":
+        if top > ops.COARSE_NMAX or low < 1:
+            raise FpmError("coarse_scores: a graph of %d keypoints; the coarse pass takes boxes up to COARSE_NMAX = %d "
+                           "(identify without a shortlist has no such bound)" % (top, ops.COARSE_NMAX))
+    elif coarse in ("wide", "auto"):
+        if top > ops.COARSE_WIDE_NMAX or low < 1:
+            raise FpmError("coarse_scores: a graph of %d keypoints; the wide coarse pass takes boxes up to "
+                           "COARSE_WIDE_NMAX = %d (identify without a shortlist has no such bound)"
+                           % (top, ops.COARSE_WIDE_NMAX))
+    elif top > ops.COARSE_STREAM_NMAX or low < 1:
+        raise FpmError("coarse_scores: a graph of %d keypoints; the streamed coarse pass takes boxes up to "
+                       "COARSE_STREAM_NMAX = %d (identify without a shortlist has no such bound)"
+                       % (top, ops.COARSE_STREAM_NMAX))
+    if coarse in ("fused", "wide", "stream"):
+        return torch.full_like(ng, ("fused", "wide", "stream").index(coarse))
+    side = torch.clamp(ng, min=n0)                               # the pair's larger side
+    rt = (side > ops.COARSE_NMAX).long()
+    if coarse == "any":
+        rt += (side > ops.COARSE_WIDE_NMAX).long()
+    return rt
+
+
+def _coarse_launch(route, index, sel_d, sel32, yp, cf, out, iters, tau):
+    _COARSE_OPS[route](index.y, index.row_off, sel_d, yp, cf, iters=iters, tau=tau, out=out, idx_host=sel32,
+                       row_off_host=index.row_off_host)
 
 
 def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk, coarse="fused"):
     """One probe's coarse scores over the entries ``sel`` into ``out`` (len(sel),).  ``coarse``: the
-    kernel, "fused" (boxes up to COARSE_NMAX), "wide" (up to COARSE_WIDE_NMAX) or "auto" (per pair:
-    fused when both sides fit COARSE_NMAX, wide otherwise -- the route depends on the pair alone)."""
-    n0 = int(probe["n"])
-    ng = index.n[sel]
-    if coarse == "fused":
-        if n0 > ops.COARSE_NMAX or n0 < 1 or int(ng.max()) > ops.COARSE_NMAX:
-            raise FpmError("coarse_scores: a graph of %d keypoints; the coarse pass takes boxes up to COARSE_NMAX = %d "
-                           "(identify without a shortlist has no such bound)"
-                           % (max(n0, int(ng.max())), ops.COARSE_NMAX))
-    elif n0 > ops.COARSE_WIDE_NMAX or n0 < 1 or int(ng.max()) > ops.COARSE_WIDE_NMAX:
-        raise FpmError("coarse_scores: a graph of %d keypoints; the wide coarse pass takes boxes up to "
-                       "COARSE_WIDE_NMAX = %d (identify without a shortlist has no such bound)"
-                       % (max(n0, int(ng.max())), ops.COARSE_WIDE_NMAX))
-    # per pair: True -> the wide kernel (host copy of n: no synchronisation)
-    to_wide = torch.as_tensor(ng).view(-1) > ops.COARSE_NMAX if coarse == "auto" and n0 <= ops.COARSE_NMAX else None
+    route (``coarse_routes``; host copy of n: no synchronisation).  A chunk whose pairs take more than
+    one kernel is split: each part's entries and coefficient rows, the scores scattered back."""
+    rt = coarse_routes(int(probe["n"]), index.n[sel], coarse)
     ps = _ProbeSide(probe, index)
     yp = net._probe_rows(wp, ps)
     sel32 = sel.to(torch.int32)
@@ -367,17 +389,15 @@ def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk, coarse="fused"):
         gw = ops.global_weights(w0[:b1 - b0], index.w[sel_d[b0:b1].long()])
         cf = coef[:b1 - b0]
         ops.coef_tanh(gw, wp["aff_wT"], wp["aff_b"], cf)
-        mixed = to_wide is not None and bool(to_wide[b0:b1].any()) and not bool(to_wide[b0:b1].all())
-        if not mixed:
-            wide = coarse == "wide" or (coarse == "auto" and (to_wide is None or bool(to_wide[b0])))
-            _coarse_launch(wide, index, sel_d[b0:b1], sel32[b0:b1], yp, cf, out[b0:b1], C.SK_ITER_NUM, net.tau)
+        kinds = torch.unique(rt[b0:b1]).tolist()
+        if len(kinds) == 1:
+            _coarse_launch(kinds[0], index, sel_d[b0:b1], sel32[b0:b1], yp, cf, out[b0:b1], C.SK_ITER_NUM, net.tau)
             continue
-        # both kernels in this chunk: each part's entries and coefficient rows, the scores scattered back
-        for wide in (False, True):
-            pos = torch.nonzero(to_wide[b0:b1] == wide).view(-1)
+        for route in kinds:
+            pos = torch.nonzero(rt[b0:b1] == route).view(-1)
             pos_d = pos.to(index.device)
             part = torch.empty(int(pos.numel()), device=index.device, dtype=torch.float32)
-            _coarse_launch(wide, index, sel_d[b0:b1][pos_d].contiguous(), sel32[b0:b1][pos],
+            _coarse_launch(route, index, sel_d[b0:b1][pos_d].contiguous(), sel32[b0:b1][pos],
                            yp, cf[pos_d].contiguous(), part, C.SK_ITER_NUM, net.tau)
             out[b0:b1][pos_d] = part
 

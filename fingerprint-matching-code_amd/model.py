@@ -1484,7 +1484,11 @@ class Net(nn.Module):
         ``ops.coarse_score_wide`` (the block in registers, Kp parked in at most 64 MB of scratch), boxes
         of at most ``ops.COARSE_WIDE_NMAX`` = 256 keypoints; "auto": per pair, the fused kernel when
         probe and entry both have at most 128 keypoints and the wide one otherwise (refused over 256).
-        Both kernels compute the same definition and agree to fp32 rounding, not bit for bit; the
+        "stream": every pair through ``ops.coarse_score_stream`` (Kp written to at most 352 MiB of
+        scratch and the Sinkhorn streamed from it), boxes of at most ``ops.COARSE_STREAM_NMAX`` = 600
+        keypoints, every graph the matcher takes; "any": per pair, fused when both sides have at
+        most 128 keypoints, wide when both have at most 256, stream otherwise (refused over 600).
+        The kernels compute the same definition and agree to fp32 rounding, not bit for bit; the
         route depends on the pair alone, so a score does not depend on what else is selected."""
         from . import gallery
         return gallery.coarse_scores(self, probes, index, select=select, coarse=coarse)
@@ -1506,9 +1510,10 @@ class Net(nn.Module):
         forward above over exactly those, in coarse-rank order -- every output equals
         ``identify(probe, index, select=short_idx)`` bit for bit.  The dict then also carries
         ``short_idx`` (M, int32 gallery entry numbers), ``coarse_score`` (M) and ``coarse_all``
-        (len(select)).  ``coarse`` ("fused", "wide" or "auto": see ``coarse_scores``) picks the coarse
-        pass's kernel: the default takes boxes of at most 128 keypoints, "wide" and "auto" boxes of at
-        most 256; without a shortlist it is only checked: the full query has no size bound."""
+        (len(select)).  ``coarse`` ("fused", "wide", "auto", "stream" or "any": see ``coarse_scores``)
+        picks the coarse pass's kernel: the default takes boxes of at most 128 keypoints, "wide" and
+        "auto" boxes of at most 256, "stream" and "any" boxes of at most 600 (every graph the matcher
+        takes); without a shortlist it is only checked: the full query has no size bound."""
         from . import gallery
         return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
                                 shortlist=shortlist, coarse=coarse)

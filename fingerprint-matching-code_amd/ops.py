@@ -463,6 +463,7 @@ def rank_select(scores, k, top_idx=None, top_score=None):
 
 COARSE_NMAX = 128
 COARSE_WIDE_NMAX = 256          # ``coarse_score_wide``: the block in registers
+COARSE_STREAM_NMAX = 600        # ``coarse_score_stream``: the block streamed from a workspace (the matcher's cap)
 
 
 def _bf16_rne(t):
@@ -499,9 +500,10 @@ def _coarse_score_host(y, row_off, idx, yp, coef, iters, tau, dtype):
 
 def _coarse_score_op(op, bound, nmax, launch, y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host,
                      dtype):
-    """The host-side checks and dispatch shared by ``coarse_score`` and ``coarse_score_wide``: ``op`` names
-    the operation in every message, ``bound`` / ``nmax`` the size limit of its kernel;
-    ``launch(G, B, n0, iters, tau, out)`` runs the kernel once everything has been checked."""
+    """The host-side checks and dispatch shared by ``coarse_score``, ``coarse_score_wide`` and
+    ``coarse_score_stream``: ``op`` names the operation in every message, ``bound`` / ``nmax`` the size
+    limit of its kernel; ``launch(G, B, n0, iters, tau, out, ngmax)`` (ngmax: the largest selected
+    n_g) runs the kernel once everything has been checked."""
     for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)):
         if not isinstance(t, torch.Tensor) or t.dtype != dt:
             raise _lib.FpmError("%s: %s must be a %s tensor (got %s)"
@@ -555,7 +557,7 @@ def _coarse_score_op(op, bound, nmax, launch, y, row_off, idx, yp, coef, iters, 
     if out.dtype != torch.float32 or not out.is_contiguous():
         raise _lib.FpmError("%s: out must be contiguous fp32" % op)
     if B:
-        launch(G, B, n0, iters, tau, out)
+        launch(G, B, n0, iters, tau, out, int(ng.max()))
     return out
 
 
@@ -575,7 +577,7 @@ def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_ho
 
     CPU tensors take the plain-torch statement of the definition, in ``dtype`` arithmetic
     (torch.float32, the default, or torch.float64) on the same bf16-rounded operands."""
-    def launch(G, B, n0, iters, tau, out):
+    def launch(G, B, n0, iters, tau, out, ngmax):
         _lib.call("fpm_coarse_score", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau, _p(out),
                   _stream(y))
     return _coarse_score_op("coarse_score", "COARSE_NMAX", COARSE_NMAX, launch, y, row_off, idx, yp, coef, iters, tau,
@@ -591,13 +593,32 @@ def coarse_score_wide(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, i
     Its sums run in another order than ``coarse_score``'s, so the two agree to rounding, not bit for
     bit, on boxes both take.  CPU tensors take the same plain-torch statement as ``coarse_score``
     (which has no size bound of its own)."""
-    def launch(G, B, n0, iters, tau, out):
+    def launch(G, B, n0, iters, tau, out, ngmax):
         wsb = int(_lib.load().fpm_coarse_score_wide_ws_bytes(B))
         ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
         _lib.call("fpm_coarse_score_wide", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau,
                   _p(out), _p(ws), wsb, _stream(y))
     return _coarse_score_op("coarse_score_wide", "COARSE_WIDE_NMAX", COARSE_WIDE_NMAX, launch, y, row_off, idx, yp,
                             coef, iters, tau, out, idx_host, row_off_host, dtype)
+
+
+def coarse_score_stream(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
+                        dtype=None):
+    """``coarse_score`` for every box the matcher takes, up to COARSE_STREAM_NMAX = 600 keypoints
+    (fpm_coarse_score_stream): the same definition, arguments and host-side checks, with n0 and every
+    selected n_g in [1, COARSE_STREAM_NMAX].  The kernel writes Kp to a scratch of min(B, 256) slots of
+    min(n0, ngmax) x max(n0, ngmax) fp32 (ngmax: the largest selected n_g; at most 352 MiB whatever
+    B), allocated here on the caller's stream, and streams the Sinkhorn from it: the first row step in
+    place, the others on potentials.  It agrees with ``coarse_score`` and ``coarse_score_wide`` to
+    rounding, not bit for bit, on boxes they take.  CPU tensors take the same plain-torch statement
+    (which has no size bound of its own)."""
+    def launch(G, B, n0, iters, tau, out, ngmax):
+        wsb = int(_lib.load().fpm_coarse_score_stream_ws_bytes(B, n0, ngmax))
+        ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
+        _lib.call("fpm_coarse_score_stream", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau,
+                  _p(out), _p(ws), wsb, _stream(y))
+    return _coarse_score_op("coarse_score_stream", "COARSE_STREAM_NMAX", COARSE_STREAM_NMAX, launch, y, row_off, idx,
+                            yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
 
 
 def edge_diff(x, src, dst):

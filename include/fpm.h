@@ -553,6 +553,30 @@ long fpm_coarse_score_wide_ws_bytes(int B);
 int fpm_coarse_score_wide(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp, int n0,
                           const float* coef, int iters, float tau, float* score, void* ws, long ws_bytes,
                           void* stream);
+/* The same score (the same definition, argument for argument) for every box the matcher takes: n0 and
+ * every selected n_g lie in [1, FPM_COARSE_STREAM_NMAX]; a pair that violates either, whose idx is
+ * outside [0, G), or whose block does not fit a slot of the workspace as given, reads no rows and gets
+ * NaN.  One workgroup of 512 threads per pair.  With R = min(n0, n_g) and C = max(n0, n_g), Kp
+ * (bf16 MFMA, tiles of 128 entry rows x 256 probe rows) is written in fp32, row-major R x C4 (C4 = C rounded up to 4), into the
+ * workgroup's own slot of ws and streamed from there (L2 / Infinity Cache): the first Sinkhorn row step
+ * in place (only the rows' lse kept), the other iters - 1 steps on potentials over that row-normalised
+ * matrix, then the sum.  The grid is persistent (min(B, 256) workgroups walk the B pairs), so ws holds
+ * fpm_coarse_score_stream_ws_bytes(B, n0, ngmax) = min(B, 256) slots of
+ * min(n0, ngmax) x roundup4(max(n0, ngmax)) fp32, ngmax the largest selected n_g (or any bound on it):
+ * at most 256 x 600 x 600 x 4 B = 352 MiB whatever B and the gallery; monotone in every argument.  The
+ * call divides the ws_bytes it is given into min(B, 256) equal slots, so a larger workspace is taken
+ * as it is and the scores do not depend on its size; 16-byte aligned, owned by the call until the
+ * stream has run it, never read before it is written (no clearing needed); a missing workspace, or
+ * one under fpm_coarse_score_stream_ws_bytes(B, n0, 1) (no entry at all would fit), is an error.
+ * 134.0 KB of LDS per workgroup (operand tiles, potentials, the column partials).  iters >= 0; an odd
+ * count ends on a row step, iters = 1 is the in-place step alone.  Every sum runs in an order fixed
+ * by (R, C), so score[b] depends neither on the launch nor on the workgroup that computes it.  Not
+ * bit-identical to the two kernels above on boxes they take; all are held to one float64 statement. */
+#define FPM_COARSE_STREAM_NMAX 600
+long fpm_coarse_score_stream_ws_bytes(int B, int n0, int ngmax);
+int fpm_coarse_score_stream(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp,
+                            int n0, const float* coef, int iters, float tau, float* score, void* ws, long ws_bytes,
+                            void* stream);
 
 /* ---- profiling hooks: HIP-event timing of the dominant kernel (edge-message GEMM) ------------ */
 int fpm_profile_enable(int on);

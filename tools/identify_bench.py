@@ -6,6 +6,9 @@
     python tools/identify_bench.py --shortlist 64 [--large 16384]      (-> profiles/identify_shortlist.json)
     python tools/identify_bench.py --shortlist 64 --coarse wide --n 256 --large 4096
                                                                        (-> profiles/identify_shortlist_wide.json)
+    python tools/identify_bench.py --shortlist 64 --coarse stream --n 512 --large 4096
+    python tools/identify_bench.py --shortlist 64 --coarse stream --n 256 --large 0 --append
+                                                                       (-> profiles/identify_shortlist_stream.json)
 
 ``--shortlist M``: by the same protocol, the shortlisted query ``identify(shortlist=M)`` against the
 full ``identify`` in one process, at the C4 shape and at a larger gallery, with the coarse pass
@@ -13,6 +16,10 @@ full ``identify`` in one process, at the C4 shape and at a larger gallery, with 
 ``--coarse wide|auto`` runs the coarse pass on ``fpm_coarse_score_wide`` (boxes of up to 256 keypoints)
 and adds that kernel alone on synthetic rows; at n <= 128 it also times the fused coarse pass over the
 same gallery, the number that decides which kernel small boxes take.
+``--coarse stream|any`` runs it on ``fpm_coarse_score_stream`` (boxes of up to 600 keypoints; the full
+``identify`` is then the only other query there is) and adds that kernel alone on synthetic rows; at
+n <= 256 it also times the wide coarse pass and the wide kernel alone over the same gallery, stream
+against wide in one process: the number that decides which kernel boxes of up to 256 take.
 
 Shape: config C4 (one probe, n = 128 keypoints, a gallery of 1024), both dtypes.  Per dtype, in a
 fresh child process under its own time limit: one warm-up, then ``--reps`` (>= 5) timed forwards of
@@ -194,12 +201,9 @@ def child_shortlist(args):
         r["fraction_of_5p5_tb_per_s"] = round(r["index_tb_per_s"] / 5.5, 3)
         return r
     res["coarse"] = coarse_pass(coarse)
-    if coarse != "fused":
-        if n <= ops.COARSE_NMAX:
-            # the same gallery through the fused kernel: which of the two small boxes should take
-            res["coarse_fused"] = coarse_pass("fused")
-            res["wide_over_fused"] = round(res["coarse"]["median_ms"] / res["coarse_fused"]["median_ms"], 3)
-        # the wide kernel alone: synthetic rows (N(0, 0.05)), min(G, 1024) entries of n keypoints, one launch
+
+    def kernel_alone(op):
+        # one coarse kernel alone: synthetic rows (N(0, 0.05)), min(G, 1024) entries of n keypoints, one launch
         Gs = min(G, 1024)
         ys = torch.randn(Gs * n, 768, device=dev) * 0.05
         offs = torch.arange(Gs + 1, dtype=torch.int64) * n
@@ -208,14 +212,28 @@ def child_shortlist(args):
         yps = torch.randn(n, 768, device=dev) * 0.05
         cfs = torch.tanh(torch.randn(Gs, 768, device=dev))
         outs = torch.empty(Gs, device=dev)
-        res["wide_kernel"] = series(lambda: ops.coarse_score_wide(ys, offs_d, ids_d, yps, cfs, tau=net.tau, out=outs,
-                                                                  idx_host=ids, row_off_host=offs))
+        r = series(lambda: op(ys, offs_d, ids_d, yps, cfs, tau=net.tau, out=outs, idx_host=ids, row_off_host=offs))
         kb = int(ys.numel()) * 4
-        res["wide_kernel"].update(entries=Gs, row_bytes=kb,
-                                  rows_tb_per_s=round(kb / res["wide_kernel"]["median_ms"] / 1e9, 3),
-                                  us_per_pair_per_cu=round(res["wide_kernel"]["median_ms"] * 1e3 * 256 / Gs, 1),
-                                  note="events around one launch: launch latency and the scratch allocation included")
-        del ys, cfs
+        r.update(entries=Gs, row_bytes=kb, rows_tb_per_s=round(kb / r["median_ms"] / 1e9, 3),
+                 us_per_pair_per_cu=round(r["median_ms"] * 1e3 * 256 / Gs, 1),
+                 note="events around one launch: launch latency and the scratch allocation included")
+        return r
+    if coarse in ("wide", "auto"):
+        if n <= ops.COARSE_NMAX:
+            # the same gallery through the fused kernel: which of the two small boxes should take
+            res["coarse_fused"] = coarse_pass("fused")
+            res["wide_over_fused"] = round(res["coarse"]["median_ms"] / res["coarse_fused"]["median_ms"], 3)
+        res["wide_kernel"] = kernel_alone(ops.coarse_score_wide)
+    if coarse in ("stream", "any"):
+        res["stream_kernel"] = kernel_alone(ops.coarse_score_stream)
+        if n <= ops.COARSE_WIDE_NMAX:
+            # the same gallery through the wide kernel: which of the two boxes of up to 256 should take
+            res["coarse_stream"] = res["coarse"] if coarse == "stream" else coarse_pass("stream")
+            res["coarse_wide"] = coarse_pass("wide")
+            res["stream_over_wide"] = round(res["coarse_stream"]["median_ms"] / res["coarse_wide"]["median_ms"], 3)
+            res["wide_kernel"] = kernel_alone(ops.coarse_score_wide)
+            res["stream_kernel_over_wide_kernel"] = round(res["stream_kernel"]["median_ms"]
+                                                          / res["wide_kernel"]["median_ms"], 3)
     res["select"] = series(lambda: ops.rank_select(call, M))
     res["forward_M"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, select=sidx)))
     f, s = res["full"], res["shortlisted"]
@@ -246,7 +264,8 @@ def main_shortlist(ap, args):
             sys.exit("identify_bench: the %s x %d step failed (exit %d); stopping" % (dtype, G, r.returncode))
         lines.append(json.loads(got[-1][len("IDENTIFY_BENCH "):]))
         print(json.dumps(lines[-1]), flush=True)
-    name = "identify_shortlist.json" if args.coarse == "fused" else "identify_shortlist_wide.json"
+    name = {"fused": "identify_shortlist.json", "wide": "identify_shortlist_wide.json",
+            "auto": "identify_shortlist_wide.json"}.get(args.coarse, "identify_shortlist_stream.json")
     out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", name)
     doc = dict(tool="tools/identify_bench.py --shortlist %d%s" % (args.shortlist, "" if args.coarse == "fused" else
                                                                   " --coarse %s --n %d" % (args.coarse, args.n)),
@@ -271,8 +290,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shortlist", type=int, default=0,
                     help="M > 0: time identify(shortlist=M) against the full identify (profiles/identify_shortlist.json)")
-    ap.add_argument("--coarse", choices=("fused", "wide", "auto"), default="fused",
-                    help="--shortlist: the coarse pass's kernel (wide / auto: profiles/identify_shortlist_wide.json)")
+    ap.add_argument("--coarse", choices=("fused", "wide", "auto", "stream", "any"), default="fused",
+                    help="--shortlist: the coarse pass's kernel (wide / auto: profiles/identify_shortlist_wide.json; "
+                         "stream / any: profiles/identify_shortlist_stream.json)")
     ap.add_argument("--append", action="store_true",
                     help="--shortlist: add the results to those the output file already holds (another --n)")
     ap.add_argument("--large", type=int, default=16384, help="--shortlist: a second, larger gallery (0: none)")
