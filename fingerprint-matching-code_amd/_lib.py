@@ -36,6 +36,7 @@ SIGNATURES = {
     "fpm_spline_plan": (I, [P, P, P, L, L, I, P, L, P]),
     "fpm_spline_plan_graphs": (I, [P, P, P, L, L, I, L, P, L, P]),
     "fpm_spline_plan_csr": (I, [P, L, L, ctypes.POINTER(P), ctypes.POINTER(P)]),
+    "fpm_spline_plan_edges": (I, [P, L, L, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P)]),
     "fpm_spline_plan_multi": (I, [P, I, I, I, P, P]),
     "fpm_spline_plan_job_bytes": (I, []),
     "fpm_spline_y_bytes": (L, [I, L, L]),

@@ -1585,6 +1585,16 @@ extern "C" int fpm_spline_plan_rows(void* ws, long E, long num_nodes, int** arow
     return 0;
 }
 
+// Per-CSR-slot tables of a plan (E entries each): csr_e[p] = the edge in slot p, rows4[p] = its 4
+// product rows (corner order s = 0..3), basis4[p] = its 4 basis weights.  Device pointers.
+extern "C" int fpm_spline_plan_edges(void* ws, long E, long num_nodes, int** csr_e, int** rows4, float** basis4) {
+    PlanLayout L = plan_layout(E, num_nodes);
+    *csr_e = (int*)((char*)ws + L.csr_e);
+    *rows4 = (int*)((char*)ws + L.rows4);
+    *basis4 = (float*)((char*)ws + L.basis4);
+    return 0;
+}
+
 // Backward of one SplineConv layer w.r.t. its input rows (the weight gradient is the caller's
 // grouped X^T dY product over the same row ranges):
 //   dY   = combine backward (max routing, root rows)                     fp32, max_rows x 768

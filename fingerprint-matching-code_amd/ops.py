@@ -214,7 +214,8 @@ def cast_bf16(x, out=None):
 
 def spline_plan(src, dst, pseudo, num_nodes, nmax, max_graph_edges=0):
     """``max_graph_edges``: the largest per-graph edge count (host-known, e.g. from the batch's edge
-    offsets) -> the per-graph plan kernels when it allows; 0 -> the global plan kernels."""
+    offsets) -> the per-graph plan kernels when it allows; 0 -> the global plan kernels.
+    Edges are grouped by graph, in graph order; inside a graph any order gives the same plan."""
     _dev(src, dst, pseudo)
     E = src.numel()
     nbytes = _lib.load().fpm_spline_plan_bytes(E, num_nodes)
@@ -1174,6 +1175,19 @@ def spline_plan_rows(plan, E, num_nodes):
     arows = plan[oa:].view(torch.int32)
     cell_off = plan[oc:oc + 4 * 27].view(torch.int32)
     return arows, cell_off
+
+
+def spline_plan_edges(plan, E, num_nodes):
+    """(csr_e (E,) int32, rows4 (E, 4) int32, basis4 (E, 4) float32) views into a plan: per CSR slot
+    of the in-edge lists, the edge id, its 4 product rows and its 4 basis weights (corner order)."""
+    a, r, b = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    _lib.call("fpm_spline_plan_edges", _p(plan), E, num_nodes, ctypes.byref(a), ctypes.byref(r), ctypes.byref(b))
+    base = plan.data_ptr()
+    oa, orr, ob = a.value - base, r.value - base, b.value - base
+    csr_e = plan[oa:oa + 4 * E].view(torch.int32)
+    rows4 = plan[orr:orr + 16 * E].view(torch.int32).view(E, 4)
+    basis4 = plan[ob:ob + 16 * E].view(torch.float32).view(E, 4)
+    return csr_e, rows4, basis4
 
 
 def spline_conv_bwd_data(x_op, plan, E, num_nodes, nmax, nvalid, Wb, y_ws, mode, gout, hout, dY, dY_op, dXrows, dX,

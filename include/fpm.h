@@ -214,6 +214,9 @@ int fpm_spline_plan(const int* src, const int* dst, const float* pseudo, long E,
 int fpm_spline_plan_graphs(const int* src, const int* dst, const float* pseudo, long E, long num_nodes, int nmax,
                            long max_graph_edges, void* ws, long ws_bytes, void* stream);
 int fpm_spline_plan_csr(void* ws, long E, long num_nodes, int** dst_ptr, int** nbr_local);
+/* per-CSR-slot tables of a plan, E entries each (device pointers): the edge of slot p, its 4 product
+ * rows (int4, corner order s = 0..3) and its 4 basis weights (float4) */
+int fpm_spline_plan_edges(void* ws, long E, long num_nodes, int** csr_e, int** rows4, float** basis4);
 /* several per-graph plans (e.g. every pipeline chunk of one side of a batch) by one launch of each
  * plan kernel.  jobs: device array of njobs records of fpm_spline_plan_job_bytes() (= 56) bytes,
  * {const int* src; const int* dst; const float* pseudo; long E, num_nodes, ws_off;
