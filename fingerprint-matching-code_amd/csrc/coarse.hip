@@ -24,6 +24,10 @@
 //      128) with multiplicity nd stands for them.
 //   4. sum exp2(L) Kp over each thread's accumulator positions, wave sums (DPP), the four waves
 //      through LDS; 4 bytes out.
+// An index that keeps a bf16 copy of its rows (the same RNE rounding, done once at enrolment) hands
+// that to the kernel's bf16 instantiation (fpm_coarse_score_rows16): the entry's tile is then copied
+// to the same LDS layout in 16-B vectors of 8 bf16, no multiply and no convert, half the bytes
+// fetched; the probe side and everything after the tile store are the same code, so are the bits.
 // The n0 x n_g block never reaches HBM.  Every order of summation is fixed by the pair alone (K
 // order of the MFMA chain, 16-lane DPP trees, the two row halves of a column, the accumulator walk),
 // so an entry's score is bit-identical whatever else shares the launch.  No spinning, no exchange
@@ -74,8 +78,27 @@ __device__ __forceinline__ void tile_store(unsigned char* tile, int tid, const f
     }
 }
 
+// the entry's K tile from bf16 rows: this thread's 4 vectors of 8 bf16 (rows (tid >> 3) + 32 m,
+// columns 8 (tid & 7) ..; a row is 1536 B, so every vector is 16-B aligned), zeros past n
+__device__ __forceinline__ void tile_load16(const bf16_t* __restrict__ base, int n, int k0, int tid, uint4 (&r)[4]) {
+    const int row0 = tid >> 3, c = 8 * (tid & 7);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int row = row0 + 32 * m;
+        r[m] = row < n ? *(const uint4*)(base + (long)row * CK + k0 + c) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+// as they are into the tile_store layout
+__device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const uint4 (&r)[4]) {
+    const int row0 = tid >> 3, c = 8 * (tid & 7);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) *(uint4*)(tile + (row0 + 32 * m) * CROW + c * 2) = r[m];
+}
+
+// YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment).
 // two workgroups per CU (LDS allows it): hold the registers to two waves per SIMD
-__global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void coarse_score_kernel(const float* __restrict__ y,
+template <typename YT>
+__global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void coarse_score_kernel(const YT* __restrict__ y,
                                                            const long* __restrict__ row_off,
                                                            const int* __restrict__ idx, int G,
                                                            const float* __restrict__ yp, int n0,
@@ -106,8 +129,17 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     // the Sinkhorn works on the transpose when n0 > n_g: its rows are the smaller side
     const bool tr = n0 > ng;
     const int R = tr ? ng : n0, C = tr ? n0 : ng;
-    const float* xa = tr ? y + r0 * CK : yp;         // rows side (MFMA A)
-    const float* xb = tr ? yp : y + r0 * CK;         // columns side (MFMA B)
+    constexpr bool F32 = sizeof(YT) == 4;
+    const YT* ye = y + r0 * CK;                      // the entry's rows
+    const float* xa = nullptr;                       // rows side (MFMA A)
+    const float* xb = nullptr;                       // columns side (MFMA B)
+    if constexpr (F32) {
+        xa = tr ? ye : yp;
+        xb = tr ? yp : ye;
+    }
+    // bf16 entry rows: the probe's tile is At and the entry's Bt, the other way round when transposed
+    unsigned char* Pt = tr ? Bt : At;
+    unsigned char* Et = tr ? At : Bt;
     const float* cf = coef + (long)b * CK;
     const int c4 = 4 * (tid & 15);
     const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
@@ -120,17 +152,33 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
     float4 ra[8], rb[8], sc;
-    tile_load(xa, R, 0, tid, ra);
-    tile_load(xb, C, 0, tid, rb);
+    uint4 re[4];
+    if constexpr (F32) {
+        tile_load(xa, R, 0, tid, ra);
+        tile_load(xb, C, 0, tid, rb);
+    } else {
+        tile_load(yp, n0, 0, tid, ra);
+        tile_load16(ye, ng, 0, tid, re);
+    }
     sc = *(const float4*)(cf + c4);
     const int fr = lane & 15, fq = lane >> 4;
     for (int kt = 0; kt < CK / CBK; ++kt) {
-        tile_store(At, tid, ra, tr ? one : sc);
-        tile_store(Bt, tid, rb, tr ? sc : one);
+        if constexpr (F32) {
+            tile_store(At, tid, ra, tr ? one : sc);
+            tile_store(Bt, tid, rb, tr ? sc : one);
+        } else {
+            tile_store(Pt, tid, ra, sc);
+            tile_store16(Et, tid, re);
+        }
         __syncthreads();
         if (kt + 1 < CK / CBK) {
-            tile_load(xa, R, (kt + 1) * CBK, tid, ra);
-            tile_load(xb, C, (kt + 1) * CBK, tid, rb);
+            if constexpr (F32) {
+                tile_load(xa, R, (kt + 1) * CBK, tid, ra);
+                tile_load(xb, C, (kt + 1) * CBK, tid, rb);
+            } else {
+                tile_load(yp, n0, (kt + 1) * CBK, tid, ra);
+                tile_load16(ye, ng, (kt + 1) * CBK, tid, re);
+            }
             sc = *(const float4*)(cf + (kt + 1) * CBK + c4);
         }
 #pragma unroll
@@ -285,8 +333,10 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 }
 }  // namespace
 
-extern "C" int fpm_coarse_score(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp,
-                                int n0, const float* coef, int iters, float tau, float* score, void* stream) {
+namespace {
+template <typename YT>
+int coarse_score_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                        const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* stream) {
     FPM_CHECK_ARG(G > 0 && B >= 0, "coarse_score: bad sizes (G %d, B %d)", G, B);
     FPM_CHECK_ARG(n0 >= 1 && n0 <= FPM_COARSE_NMAX, "coarse_score: probe of %d keypoints outside [1, COARSE_NMAX = %d]",
                   n0, FPM_COARSE_NMAX);
@@ -295,13 +345,27 @@ extern "C" int fpm_coarse_score(const float* y, const long* row_off, const int* 
                   "coarse_score: y, row_off, idx, yp, coef and score are required");
     if (B == 0) return 0;
     constexpr int lds = LDS_FLOATS * (int)sizeof(float);
-    if (hipFuncSetAttribute((const void*)coarse_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
+    if (hipFuncSetAttribute((const void*)coarse_score_kernel<YT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
         hipSuccess) {
         (void)hipGetLastError();
         fpm::set_error("coarse_score: %d bytes of LDS per workgroup refused", lds);
         return 1;
     }
-    hipLaunchKernelGGL(coarse_score_kernel, dim3((unsigned)B), dim3(CT), lds, (hipStream_t)stream, y, row_off, idx, G,
-                       yp, n0, coef, iters, tau, score);
-    return fpm::check_launch("fpm_coarse_score");
+    hipLaunchKernelGGL(coarse_score_kernel<YT>, dim3((unsigned)B), dim3(CT), lds, (hipStream_t)stream, y, row_off, idx,
+                       G, yp, n0, coef, iters, tau, score);
+    return fpm::check_launch(what);
+}
+}  // namespace
+
+extern "C" int fpm_coarse_score(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp,
+                                int n0, const float* coef, int iters, float tau, float* score, void* stream) {
+    return coarse_score_launch<float>("fpm_coarse_score", y, row_off, idx, G, B, yp, n0, coef, iters, tau, score,
+                                      stream);
+}
+
+extern "C" int fpm_coarse_score_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
+                                       const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                                       void* stream) {
+    return coarse_score_launch<bf16_t>("fpm_coarse_score_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0, coef,
+                                       iters, tau, score, stream);
 }

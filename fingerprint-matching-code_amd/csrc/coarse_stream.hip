@@ -100,8 +100,30 @@ __device__ __forceinline__ void tile_store(unsigned char* tile, int tid, const f
         *(uint2*)(tile + (row0 + 32 * m) * SROW + c * 2) = o;
     }
 }
+// the entry's K tile from bf16 rows (fpm_coarse_score_stream_rows16: an index that keeps a bf16 copy
+// of its rows, the same RNE rounding done once at enrolment): this thread's 2 vectors of 8 bf16 (rows
+// row_base + (tid >> 3) + 64 m, columns 8 (tid & 7) ..; a row is 1536 B, so every vector is 16-B
+// aligned), zeros past n
+__device__ __forceinline__ void tile_load16(const bf16_t* __restrict__ base, int n, int row_base, int k0, int tid,
+                                            uint4 (&r)[2]) {
+    const int row0 = row_base + (tid >> 3), c = 8 * (tid & 7);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int row = row0 + 64 * m;
+        r[m] = row < n ? *(const uint4*)(base + (long)row * SK + k0 + c) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+// as they are into the tile_store layout: no multiply, no convert
+__device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const uint4 (&r)[2]) {
+    const int row0 = tid >> 3, c = 8 * (tid & 7);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) *(uint4*)(tile + (row0 + 64 * m) * SROW + c * 2) = r[m];
+}
 
-__global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const float* __restrict__ y,
+// YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment); the
+// probe side and everything after the tile store are the same code, so are the bits
+template <typename YT>
+__global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const YT* __restrict__ y,
                                                                  const long* __restrict__ row_off,
                                                                  const int* __restrict__ idx, int G, int B,
                                                                  const float* __restrict__ yp, int n0,
@@ -142,7 +164,8 @@ __global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const float* __
             if (tid == 0) score[b] = __uint_as_float(0x7FC00000u);
             continue;
         }
-        const float* xe = y + r0 * SK;               // the entry's rows: MFMA A, tiles of 128
+        constexpr bool F32 = sizeof(YT) == 4;
+        const YT* xe = y + r0 * SK;                  // the entry's rows: MFMA A, tiles of 128
         const float* cf = coef + (long)b * SK;
         const int nd = C - R;                        // dummy rows (dummy_row = True)
         const float fnd = (float)nd;
@@ -158,19 +181,23 @@ __global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const float* __
                 const int c4 = 4 * (tid & 15);
                 const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
                 float4 ra[4], rb[8], s4;
-                tile_load<4>(xe, ng, te, 0, tid, ra);
+                uint4 re[2];                             // bf16 entry rows, in ra's place
+                if constexpr (F32) tile_load<4>(xe, ng, te, 0, tid, ra);
+                else tile_load16(xe, ng, te, 0, tid, re);
                 tile_load<8>(yp, n0, tp, 0, tid, rb);
                 s4 = *(const float4*)(cf + c4);
                 for (int kt = 0; kt < SK / SBK; ++kt) {
                     unsigned char* At = slds + (kt & 1) * SBUF;
                     unsigned char* Bt = At + ATILE;
-                    tile_store<4>(At, tid, ra, one);
+                    if constexpr (F32) tile_store<4>(At, tid, ra, one);
+                    else tile_store16(At, tid, re);
                     tile_store<8>(Bt, tid, rb, s4);
                     // one barrier per K tile: the other buffer was last read before the previous barrier
                     // (12 K tiles, an even count: the parity carries over from one block tile to the next)
                     __syncthreads();
                     if (kt + 1 < SK / SBK) {
-                        tile_load<4>(xe, ng, te, (kt + 1) * SBK, tid, ra);
+                        if constexpr (F32) tile_load<4>(xe, ng, te, (kt + 1) * SBK, tid, ra);
+                        else tile_load16(xe, ng, te, (kt + 1) * SBK, tid, re);
                         tile_load<8>(yp, n0, tp, (kt + 1) * SBK, tid, rb);
                         s4 = *(const float4*)(cf + (kt + 1) * SBK + c4);
                     }
@@ -417,9 +444,11 @@ extern "C" long fpm_coarse_score_stream_ws_bytes(int B, int n0, int ngmax) {
     return (long)(B < SGRID ? B : SGRID) * slot_floats_of(n0, ngmax) * (long)sizeof(float);
 }
 
-extern "C" int fpm_coarse_score_stream(const float* y, const long* row_off, const int* idx, int G, int B,
-                                       const float* yp, int n0, const float* coef, int iters, float tau, float* score,
-                                       void* ws, long ws_bytes, void* stream) {
+namespace {
+template <typename YT>
+int coarse_score_stream_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                               const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* ws,
+                               long ws_bytes, void* stream) {
     FPM_CHECK_ARG(G > 0 && B >= 0, "coarse_score_stream: bad sizes (G %d, B %d)", G, B);
     FPM_CHECK_ARG(n0 >= 1 && n0 <= FPM_COARSE_STREAM_NMAX,
                   "coarse_score_stream: probe of %d keypoints outside [1, COARSE_STREAM_NMAX = %d]", n0,
@@ -436,13 +465,28 @@ extern "C" int fpm_coarse_score_stream(const float* y, const long* row_off, cons
                   "coarse_score_stream: workspace of at least %ld bytes (16-byte aligned; "
                   "fpm_coarse_score_stream_ws_bytes) required, got %ld",
                   need, ws_bytes);
-    if (hipFuncSetAttribute((const void*)coarse_score_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)coarse_score_stream_kernel<YT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SLDS) != hipSuccess) {
         (void)hipGetLastError();
         fpm::set_error("coarse_score_stream: %d bytes of LDS per workgroup refused", SLDS);
         return 1;
     }
-    hipLaunchKernelGGL(coarse_score_stream_kernel, dim3((unsigned)grid), dim3(ST), SLDS, (hipStream_t)stream, y,
+    hipLaunchKernelGGL(coarse_score_stream_kernel<YT>, dim3((unsigned)grid), dim3(ST), SLDS, (hipStream_t)stream, y,
                        row_off, idx, G, B, yp, n0, coef, iters, tau, score, (float*)ws, slot_floats);
-    return fpm::check_launch("fpm_coarse_score_stream");
+    return fpm::check_launch(what);
+}
+}  // namespace
+
+extern "C" int fpm_coarse_score_stream(const float* y, const long* row_off, const int* idx, int G, int B,
+                                       const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                                       void* ws, long ws_bytes, void* stream) {
+    return coarse_score_stream_launch<float>("fpm_coarse_score_stream", y, row_off, idx, G, B, yp, n0, coef, iters,
+                                             tau, score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_score_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
+                                              const float* yp, int n0, const float* coef, int iters, float tau,
+                                              float* score, void* ws, long ws_bytes, void* stream) {
+    return coarse_score_stream_launch<bf16_t>("fpm_coarse_score_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B,
+                                              yp, n0, coef, iters, tau, score, ws, ws_bytes, stream);
 }

@@ -105,8 +105,29 @@ __device__ __forceinline__ void tile_store(unsigned char* tile, int tid, const f
         *(uint2*)(tile + (row0 + 64 * m) * WROW + c * 2) = o;
     }
 }
+// the entry's K tile from bf16 rows (fpm_coarse_score_wide_rows16: an index that keeps a bf16 copy of
+// its rows, the same RNE rounding done once at enrolment): this thread's 2 vectors of 8 bf16 (rows
+// (tid >> 2) + 128 m, columns 8 (tid & 3) ..; a row is 1536 B, so every vector is 16-B aligned),
+// zeros past n
+__device__ __forceinline__ void tile_load16(const bf16_t* __restrict__ base, int n, int k0, int tid, uint4 (&r)[2]) {
+    const int row0 = tid >> 2, c = 8 * (tid & 3);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int row = row0 + 128 * m;
+        r[m] = row < n ? *(const uint4*)(base + (long)row * WK + k0 + c) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+// as they are into the tile_store layout: no multiply, no convert
+__device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const uint4 (&r)[2]) {
+    const int row0 = tid >> 2, c = 8 * (tid & 3);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) *(uint4*)(tile + (row0 + 128 * m) * WROW + c * 2) = r[m];
+}
 
-__global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const float* __restrict__ y,
+// YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment); the
+// probe side and everything after the tile store are the same code, so are the bits
+template <typename YT>
+__global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restrict__ y,
                                                                const long* __restrict__ row_off,
                                                                const int* __restrict__ idx, int G, int B,
                                                                const float* __restrict__ yp, int n0,
@@ -140,8 +161,14 @@ __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const float* __re
         // the Sinkhorn works on the transpose when n0 > n_g: its rows are the smaller side
         const bool tr = n0 > ng;
         const int R = tr ? ng : n0, C = tr ? n0 : ng;
-        const float* xa = tr ? y + r0 * WK : yp;         // rows side (MFMA A)
-        const float* xb = tr ? yp : y + r0 * WK;         // columns side (MFMA B)
+        constexpr bool F32 = sizeof(YT) == 4;
+        const YT* ye = y + r0 * WK;                      // the entry's rows
+        const float* xa = nullptr;                       // rows side (MFMA A)
+        const float* xb = nullptr;                       // columns side (MFMA B)
+        if constexpr (F32) {
+            xa = tr ? ye : yp;
+            xb = tr ? yp : ye;
+        }
         const float* cf = coef + (long)b * WK;
         const int nd = C - R;                    // dummy rows (dummy_row = True)
         // a wave whose 64 x 128 part lies wholly outside the block holds nothing: it only reports empty
@@ -160,19 +187,35 @@ __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const float* __re
             const int tid = p.tid, fr = p.fr, fq = p.fq, c4 = 4 * (tid & 7);
             const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
             float4 ra[4], rb[4], sc;
-            tile_load(xa, R, 0, tid, ra);
-            tile_load(xb, C, 0, tid, rb);
+            uint4 re[2];                                 // bf16 entry rows: ra is the probe's tile, re the entry's
+            if constexpr (F32) {
+                tile_load(xa, R, 0, tid, ra);
+                tile_load(xb, C, 0, tid, rb);
+            } else {
+                tile_load(yp, n0, 0, tid, ra);
+                tile_load16(ye, ng, 0, tid, re);
+            }
             sc = *(const float4*)(cf + c4);
             for (int kt = 0; kt < WK / WBK; ++kt) {
                 unsigned char* At = wlds + (kt & 1) * WBUF;
                 unsigned char* Bt = At + WTILE;
-                tile_store(At, tid, ra, tr ? one : sc);
-                tile_store(Bt, tid, rb, tr ? sc : one);
+                if constexpr (F32) {
+                    tile_store(At, tid, ra, tr ? one : sc);
+                    tile_store(Bt, tid, rb, tr ? sc : one);
+                } else {                                 // the entry is the MFMA's A when transposed, B otherwise
+                    tile_store(tr ? Bt : At, tid, ra, sc);
+                    tile_store16(tr ? At : Bt, tid, re);
+                }
                 // one barrier per tile: the other buffer was last read before the previous barrier
                 __syncthreads();
                 if (kt + 1 < WK / WBK) {
-                    tile_load(xa, R, (kt + 1) * WBK, tid, ra);
-                    tile_load(xb, C, (kt + 1) * WBK, tid, rb);
+                    if constexpr (F32) {
+                        tile_load(xa, R, (kt + 1) * WBK, tid, ra);
+                        tile_load(xb, C, (kt + 1) * WBK, tid, rb);
+                    } else {
+                        tile_load(yp, n0, (kt + 1) * WBK, tid, ra);
+                        tile_load16(ye, ng, (kt + 1) * WBK, tid, re);
+                    }
                     sc = *(const float4*)(cf + (kt + 1) * WBK + c4);
                 }
                 bf16x8_t a[FM];
@@ -383,9 +426,11 @@ extern "C" long fpm_coarse_score_wide_ws_bytes(int B) {
     return (long)(B < WGRID ? B : WGRID) * SLOT_FLOATS * (long)sizeof(float);
 }
 
-extern "C" int fpm_coarse_score_wide(const float* y, const long* row_off, const int* idx, int G, int B,
-                                     const float* yp, int n0, const float* coef, int iters, float tau, float* score,
-                                     void* ws, long ws_bytes, void* stream) {
+namespace {
+template <typename YT>
+int coarse_score_wide_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                             const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* ws,
+                             long ws_bytes, void* stream) {
     FPM_CHECK_ARG(G > 0 && B >= 0, "coarse_score_wide: bad sizes (G %d, B %d)", G, B);
     FPM_CHECK_ARG(n0 >= 1 && n0 <= FPM_COARSE_WIDE_NMAX,
                   "coarse_score_wide: probe of %d keypoints outside [1, COARSE_WIDE_NMAX = %d]", n0,
@@ -397,14 +442,29 @@ extern "C" int fpm_coarse_score_wide(const float* y, const long* row_off, const 
     const long need = fpm_coarse_score_wide_ws_bytes(B);
     FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
                   "coarse_score_wide: workspace of %ld bytes (16-byte aligned) required, got %ld", need, ws_bytes);
-    if (hipFuncSetAttribute((const void*)coarse_score_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WLDS) !=
-        hipSuccess) {
+    if (hipFuncSetAttribute((const void*)coarse_score_wide_kernel<YT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            WLDS) != hipSuccess) {
         (void)hipGetLastError();
         fpm::set_error("coarse_score_wide: %d bytes of LDS per workgroup refused", WLDS);
         return 1;
     }
     const int grid = B < WGRID ? B : WGRID;
-    hipLaunchKernelGGL(coarse_score_wide_kernel, dim3((unsigned)grid), dim3(WT), WLDS, (hipStream_t)stream, y, row_off,
-                       idx, G, B, yp, n0, coef, iters, tau, score, (float*)ws);
-    return fpm::check_launch("fpm_coarse_score_wide");
+    hipLaunchKernelGGL(coarse_score_wide_kernel<YT>, dim3((unsigned)grid), dim3(WT), WLDS, (hipStream_t)stream, y,
+                       row_off, idx, G, B, yp, n0, coef, iters, tau, score, (float*)ws);
+    return fpm::check_launch(what);
+}
+}  // namespace
+
+extern "C" int fpm_coarse_score_wide(const float* y, const long* row_off, const int* idx, int G, int B,
+                                     const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                                     void* ws, long ws_bytes, void* stream) {
+    return coarse_score_wide_launch<float>("fpm_coarse_score_wide", y, row_off, idx, G, B, yp, n0, coef, iters, tau,
+                                           score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_score_wide_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
+                                            const float* yp, int n0, const float* coef, int iters, float tau,
+                                            float* score, void* ws, long ws_bytes, void* stream) {
+    return coarse_score_wide_launch<bf16_t>("fpm_coarse_score_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp,
+                                            n0, coef, iters, tau, score, ws, ws_bytes, stream);
 }

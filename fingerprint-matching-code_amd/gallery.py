@@ -16,6 +16,13 @@ over the selected entries, ``fpm_rank_select`` to the M best, and the forward ab
 
 Size of an index: 768 fp32 channels = 3 KB per keypoint (0.39 MB per template at n = 128, 0.4 GB per
 1024 such templates), plus the graph's edges (12 B each, ~6 per keypoint) and 2 KB of global feature.
+
+Layouts (``enroll(layout=...)``): the coarse score is defined on b = bf16(y_g), so a bf16 copy of the
+rows, rounded once at enrolment (``y16``), serves the coarse kernels with the same bits at half the
+bytes ("f32+bf16": the copy beside the fp32 rows).  The exact forward needs fp32 rows only for the
+M <= 1024 shortlisted entries, so "bf16+host" keeps them in pinned host memory and ``fetch``es those M
+entries per query (``fpm_rows_fetch``): 1.5 KB per keypoint on the device, twice the gallery per GPU,
+and every output of ``identify(shortlist=M)`` the same bits as from the "f32" layout.
 """
 import hashlib
 
@@ -28,15 +35,35 @@ from ._lib import FpmError
 from .batch import DeviceBatch, ORDER_MIN_NMAX, ORDER_ON, hilbert_order
 from .model import _CachedSide
 
-FORMAT = 1
+FORMAT = 1                    # a saved "f32" index; the other layouts write FORMAT_LAYOUTS
+FORMAT_LAYOUTS = 2
 SCORES = ("cls_prob", "cls_logits", "k_prob")
+LAYOUTS = ("f32", "f32+bf16", "bf16+host")
+ROW_BYTES = 4 * C.NODE_FEATURE_DIM
+# the fp32 rows one ``GalleryIndex.fetch`` stages on the device at most: those of the largest shortlist
+# the API allows (1.89 GB)
+FETCH_MAX_BYTES = ops.RANK_SELECT_KMAX * ops.COARSE_STREAM_NMAX * ROW_BYTES
+
+
+def _host_rows(shape, dev):
+    """An uninitialised fp32 host tensor for an index on ``dev``: pinned when that is a GPU (the
+    kernels read it through its device mapping), plain on a CPU "device"."""
+    return torch.empty(shape, dtype=torch.float32, pin_memory=torch.device(dev).type == "cuda")
 
 
 class GalleryIndex:
     """Data of an enrolled gallery of G graphs (a container; ``Net.enroll`` fills it):
 
-      y         (sum n, 768) fp32   SplineConv output rows, graph g at [row_off[g], row_off[g + 1])
-      row_off   (G + 1,) int64      device; ``row_off_host`` its host copy
+      y         (sum n, 768) fp32   SplineConv output rows, graph g at [row_off[g], row_off[g + 1]);
+                                    on the device, or ("bf16+host") in pinned host memory
+      y16       (sum n, 768) bf16   device; the same rows rounded to nearest even (``ops.cast_bf16``),
+                                    what the coarse kernels read; None in the "f32" layout
+      layout    "f32"               y on the device (3 KB per keypoint), no y16
+                "f32+bf16"          y and y16 on the device (4.5 KB per keypoint)
+                "bf16+host"         y16 on the device (1.5 KB per keypoint), y on the host: the coarse
+                                    pass reads y16, the exact forward ``fetch``es the rows it needs
+      row_off   (G + 1,) int64      device (the index's device, whatever the layout); ``row_off_host``
+                                    its host copy
       n         (G,) int32          keypoints per graph (host)
       src, dst  (sum E,) int32      each graph's edges, graph-local node ids, concatenated (device)
       pseudo    (sum E, 2) fp32     their pseudo-coordinates (device)
@@ -48,10 +75,23 @@ class GalleryIndex:
                                     SplineConv weights (``Net.identify`` refuses other weights)
     """
 
-    def __init__(self, y, row_off, n, src, dst, pseudo, edge_off, w, P, sc_mode, pack_gen, weights_id):
+    def __init__(self, y, row_off, n, src, dst, pseudo, edge_off, w, P, sc_mode, pack_gen, weights_id, y16=None,
+                 layout="f32"):
         if sc_mode not in ("f32", "bf16"):
             raise FpmError("GalleryIndex: sc_mode must be 'f32' or 'bf16'")
+        if layout not in LAYOUTS:
+            raise FpmError("GalleryIndex: layout must be one of %s" % (LAYOUTS,))
+        if (y16 is None) != (layout == "f32"):
+            raise FpmError("GalleryIndex: layout %r %s" % (layout, "has no y16" if layout == "f32" else "needs y16"))
+        if y16 is not None and (not isinstance(y16, torch.Tensor) or tuple(y16.shape) != tuple(y.shape)
+                                or y16.dtype != torch.bfloat16 or y16.device != row_off.device):
+            raise FpmError("GalleryIndex: inconsistent fields (y16 must be bfloat16 of y's shape on the index device)")
+        if layout == "bf16+host" and (y.is_cuda or (row_off.is_cuda and not y.is_pinned())):
+            raise FpmError("GalleryIndex: layout 'bf16+host' keeps y in host memory (pinned when the index is on a "
+                           "GPU)")
         self.y, self.src, self.dst, self.pseudo, self.w, self.P = y, src, dst, pseudo, w, P
+        self.y16, self.layout = y16, layout
+        self._stage = None          # fetch: (sel, staging buffer, row offsets device / host) of the last selection
         self.row_off = row_off
         self.row_off_host = row_off.cpu()
         self.n = torch.as_tensor(n, dtype=torch.int32).cpu()
@@ -73,30 +113,82 @@ class GalleryIndex:
 
     @property
     def device(self):
-        return self.y.device
+        return self.row_off.device
 
     def nbytes(self):
-        """Device bytes held (3 KB per keypoint of rows, plus edges and global features)."""
-        ts = [self.y, self.row_off, self.src, self.dst, self.pseudo, self.w] + ([] if self.P is None else [self.P])
+        """Device bytes held: the rows (3 KB per keypoint in the "f32" layout, 4.5 KB in "f32+bf16",
+        1.5 KB in "bf16+host"), plus edges and global features."""
+        ts = [self.row_off, self.src, self.dst, self.pseudo, self.w] + ([] if self.P is None else [self.P])
+        ts += ([] if self.layout == "bf16+host" else [self.y]) + ([] if self.y16 is None else [self.y16])
         return sum(t.numel() * t.element_size() for t in ts)
 
+    def host_nbytes(self):
+        """Host bytes held: the fp32 rows of the "bf16+host" layout (3 KB per keypoint), else 0."""
+        return self.y.numel() * self.y.element_size() if self.layout == "bf16+host" else 0
+
     def save(self, path):
-        """``torch.save`` of a dict of tensors and scalars (no pickled code objects)."""
+        """``torch.save`` of a dict of tensors and scalars (no pickled code objects).  An "f32" index
+        writes format 1, as ever; the other layouts write format 2, with ``layout`` and ``y16``."""
         d = dict(format=FORMAT, y=self.y.cpu(), row_off=self.row_off_host, n=self.n, src=self.src.cpu(),
                  dst=self.dst.cpu(), pseudo=self.pseudo.cpu(), edge_off=self.edge_off, w=self.w.cpu(),
                  sc_mode=self.sc_mode, pack_gen=self._pack_gen, weights_id=self.weights_id)
         if self.P is not None:
             d["P"] = self.P.cpu()
+        if self.layout != "f32":
+            d.update(format=FORMAT_LAYOUTS, layout=self.layout, y16=self.y16.cpu())
         torch.save(d, path)
 
     @staticmethod
     def load(path, device):
         d = torch.load(path, map_location="cpu", weights_only=True)
-        if d.get("format") != FORMAT:
-            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d" % (path, FORMAT))
+        if d.get("format") not in (FORMAT, FORMAT_LAYOUTS):
+            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d or %d"
+                           % (path, FORMAT, FORMAT_LAYOUTS))
         mv = lambda k: d[k].to(device)
-        return GalleryIndex(mv("y"), mv("row_off"), d["n"], mv("src"), mv("dst"), mv("pseudo"), d["edge_off"], mv("w"),
-                            mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"])
+        layout = d["layout"] if d["format"] == FORMAT_LAYOUTS else "f32"
+        if layout == "bf16+host":
+            y = _host_rows(d["y"].shape, device).copy_(d["y"])
+        else:
+            y = mv("y")
+        return GalleryIndex(y, mv("row_off"), d["n"], mv("src"), mv("dst"), mv("pseudo"), d["edge_off"], mv("w"),
+                            mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"],
+                            y16=mv("y16") if layout != "f32" else None, layout=layout)
+
+    def fetch(self, sel):
+        """The fp32 rows of the entries ``sel`` (host int64, in that order) of a "bf16+host" index, copied
+        from the host into a device staging buffer (``ops.rows_fetch``: one kernel reads the pinned
+        rows) -> (y_stage (sum of the selected n, 768) fp32 device, its row offsets (len(sel) + 1,)
+        int64 on the device, the same on the host): entry sel[m] at rows [off[m], off[m + 1]).  The
+        buffer is reused from call to call and grows as needed; a repeated selection is not copied
+        again.  Selections over FETCH_MAX_BYTES of rows are refused."""
+        if self.layout != "bf16+host":
+            raise FpmError("GalleryIndex.fetch: layout %r holds its fp32 rows on the device" % self.layout)
+        sel = torch.as_tensor(sel, dtype=torch.int64).view(-1).cpu()
+        if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= self.G:
+            raise FpmError("GalleryIndex.fetch: sel must name entries in [0, %d)" % self.G)
+        if self._stage is not None and torch.equal(self._stage[0], sel):
+            return self._stage[2:]
+        ng = self.n[sel].long()
+        total = int(ng.sum())
+        if total * ROW_BYTES > FETCH_MAX_BYTES:
+            raise FpmError("identify: the %d selected entries' fp32 rows take %d bytes on the device, over "
+                           "FETCH_MAX_BYTES = %d; an index with its rows on the host (layout 'bf16+host') runs "
+                           "the exact forward over a shortlist: pass shortlist=M, or a smaller select"
+                           % (sel.numel(), total * ROW_BYTES, FETCH_MAX_BYTES))
+        dev = self.device
+        buf = None if self._stage is None else self._stage[1]
+        self._stage = None
+        if buf is None or buf.shape[0] < total:
+            grow = 0 if buf is None else min(buf.shape[0] * 3 // 2, FETCH_MAX_BYTES // ROW_BYTES)
+            buf = None                                   # the old buffer goes before the new one comes
+            buf = torch.empty(max(total, grow), C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
+        off_h = torch.cat([torch.zeros(1, dtype=torch.int64), ng.cumsum(0)])
+        off_d = off_h.to(dev)
+        sel32 = sel.to(torch.int32)
+        ops.rows_fetch(self.y, self.row_off, sel32.to(dev), buf, off_d, idx_host=sel32, row_off_host=self.row_off_host,
+                       out_off_host=off_h)
+        self._stage = (sel, buf, buf[:total], off_d, off_h)
+        return self._stage[2:]
 
     def _selection(self, select):
         """Side 1 of a probe x gallery batch over the entries ``select`` (None: all), in that order,
@@ -208,11 +300,16 @@ def spline_weights_id(net):
     return net._sc_weights_id[1]
 
 
-def enroll(net, graphs, device, sc_mode=None, batch=256):
+def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32"):
     """``Net.enroll``: the two SplineConv layers over ``graphs`` (dicts as ``fpm.synth.make_graph``
-    returns: n, x, w, edge_index, pseudo, optionally P) in sub-batches of ``batch`` graphs -> GalleryIndex."""
+    returns: n, x, w, edge_index, pseudo, optionally P) in sub-batches of ``batch`` graphs -> GalleryIndex.
+    ``layout`` (LAYOUTS): where the rows are kept.  The bf16 copy is rounded per sub-batch on the device
+    (``ops.cast_bf16``: the coarse kernels' own rounding); for "bf16+host" each sub-batch's fp32 rows go
+    straight to the pinned host tensor, so the device holds the bf16 rows plus one sub-batch at most."""
     if net.training:
         raise FpmError("enroll: inference only (call net.eval())")
+    if layout not in LAYOUTS:
+        raise FpmError("enroll: layout must be one of %s" % (LAYOUTS,))
     dev = torch.device(device)
     sc_mode = sc_mode or ("f32" if net.dtype_mode == "f32" else "bf16")
     if sc_mode not in ("f32", "bf16") or (sc_mode == "bf16" and net.dtype_mode != "bf16"):
@@ -225,6 +322,13 @@ def enroll(net, graphs, device, sc_mode=None, batch=256):
     W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
     code = ops.F32 if f32 else ops.BF16
     ys, srcs, dsts, pss, cnts = [], [], [], [], []
+    total = sum(int(g["n"]) for g in graphs)
+    y16 = y_host = None
+    if layout != "f32":
+        y16 = torch.empty(total, C.NODE_FEATURE_DIM, device=dev, dtype=torch.bfloat16)
+    if layout == "bf16+host":
+        y_host = _host_rows((total, C.NODE_FEATURE_DIM), dev)
+    r0 = 0
     with torch.cuda.device(dev):
         for g0 in range(0, len(graphs), max(1, int(batch))):
             sub = graphs[g0:g0 + max(1, int(batch))]
@@ -240,7 +344,14 @@ def enroll(net, graphs, device, sc_mode=None, batch=256):
             ops.spline_conv(h, plan, E, nn_, nmax, nv, W1, wp["bias1"], yws, 1, xres=x0, out_f=y)
             # padded -> ragged rows, edges back to graph-local ids (off the hot path: torch indexing)
             keep = (torch.arange(nmax, device=dev)[None, :] < nv.view(-1, 1)).reshape(-1)
-            ys.append(y[keep])
+            yr = y[keep]
+            if y16 is not None:
+                ops.cast_bf16(yr, out=y16[r0:r0 + yr.shape[0]])
+            if y_host is not None:
+                y_host[r0:r0 + yr.shape[0]].copy_(yr, non_blocking=True)
+            else:
+                ys.append(yr)
+            r0 += int(yr.shape[0])
             shift = torch.repeat_interleave(torch.arange(Bs, device=dev) * nmax, torch.from_numpy(cnt).to(dev),
                                             output_size=E).to(torch.int32)
             srcs.append(src - shift)
@@ -254,8 +365,11 @@ def enroll(net, graphs, device, sc_mode=None, batch=256):
     P = None
     if all("P" in g for g in graphs):
         P = torch.from_numpy(np.concatenate([np.asarray(g["P"], dtype=np.float32).reshape(-1, 2) for g in graphs])).to(dev)
-    return GalleryIndex(torch.cat(ys), row_off.to(dev), n_all, torch.cat(srcs), torch.cat(dsts), torch.cat(pss),
-                        edge_off, w, P, sc_mode, net._pack_gen, spline_weights_id(net))
+    if y_host is not None:
+        torch.cuda.current_stream(dev).synchronize()       # the host rows are complete before they are read
+    return GalleryIndex(torch.cat(ys) if y_host is None else y_host, row_off.to(dev), n_all, torch.cat(srcs),
+                        torch.cat(dsts), torch.cat(pss), edge_off, w, P, sc_mode, net._pack_gen,
+                        spline_weights_id(net), y16=y16, layout=layout)
 
 
 def probe_batch(probe, index, select=None):
@@ -276,7 +390,14 @@ def probe_batch(probe, index, select=None):
     bt = _GalleryBatch(B, np.full(B, n0, np.int32), f["n"], [x0, x0.new_empty(0, C.NODE_FEATURE_DIM)], [w0, f["w"]],
                        [src0, f["src"]], [dst0, f["dst"]], [ps0, f["pseudo"]], dev, nmax=[n0, f["nmax"]],
                        edge_off=[eo0, f["edge_off"]], shared0=True)
-    bt.cached = _CachedSide(index.y, index.row_off, index.row_off_host, f["idx"], f["idx_host"])
+    if index.layout == "bf16+host":
+        # the selected entries' fp32 rows, staged on the device in selection order: pair b reads staged
+        # entry b (f["idx"], top_idx and short_idx keep speaking gallery entry numbers)
+        ys, off_d, off_h = index.fetch(sel)
+        ar = torch.arange(B, dtype=torch.int32)
+        bt.cached = _CachedSide(ys, off_d, off_h, ar.to(dev), ar)
+    else:
+        bt.cached = _CachedSide(index.y, index.row_off, index.row_off_host, f["idx"], f["idx_host"])
     bt.sc_mode = index.sc_mode
     bt.ord2 = f["ord2"]
     return bt, sel
@@ -368,7 +489,9 @@ def coarse_routes(n0, ng, coarse="any"):
 
 
 def _coarse_launch(route, index, sel_d, sel32, yp, cf, out, iters, tau):
-    _COARSE_OPS[route](index.y, index.row_off, sel_d, yp, cf, iters=iters, tau=tau, out=out, idx_host=sel32,
+    # the bf16 copy of the rows when the index keeps one: half the bytes, the same operands
+    rows = index.y if index.y16 is None else index.y16
+    _COARSE_OPS[route](rows, index.row_off, sel_d, yp, cf, iters=iters, tau=tau, out=out, idx_host=sel32,
                        row_off_host=index.row_off_host)
 
 

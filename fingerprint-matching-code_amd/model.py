@@ -1458,16 +1458,25 @@ class Net(nn.Module):
                                 chunk_timeline_ms=timeline)
         return res
 
-    def enroll(self, graphs, device, sc_mode=None, batch=256):
+    def enroll(self, graphs, device, sc_mode=None, batch=256, layout="f32"):
         """Enrol a gallery for 1:N identification (inference only): run the two SplineConv layers over
         ``graphs`` (dicts as ``fpm.synth.make_graph`` returns) once, in sub-batches of ``batch``, and
         keep their fp32 output rows -> ``fpm.gallery.GalleryIndex`` (3 KB per keypoint).  ``sc_mode``:
         the SplineConv arithmetic, "f32" or "bf16"; default "f32" for dtype="f32" nets, "bf16"
         otherwise.  A forward over the index uses the same arithmetic for the probe (``_sc_f32``), so
         a bf16 net that is to match its own small-box forwards (fp32 SplineConv on boxes of at most
-        ``sc_f32_nmax`` keypoints) enrols with sc_mode="f32"."""
+        ``sc_f32_nmax`` keypoints) enrols with sc_mode="f32".
+
+        ``layout``: where the index keeps its rows.  "f32" (the default): the fp32 rows on the device.
+        "f32+bf16": beside them a bf16 copy (4.5 KB per keypoint), which the coarse pass of
+        ``identify(shortlist=M)`` reads instead (half the bytes, the same scores bit for bit).
+        "bf16+host": the bf16 copy on the device (1.5 KB per keypoint: twice the gallery per GPU) and
+        the fp32 rows in pinned host memory (3 KB per keypoint of host RAM), written sub-batch by
+        sub-batch, so the device never holds the whole fp32 gallery; the exact forward copies the
+        rows of the entries it runs over to the device per query.  Every output of ``identify`` and
+        ``coarse_scores`` is the same bits whatever the layout."""
         from . import gallery
-        return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch)
+        return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch, layout=layout)
 
     def coarse_scores(self, probes, index, select=None, coarse="fused"):
         """The coarse first pass of a shortlisted identification: for each probe graph (one dict, or a
@@ -1513,7 +1522,13 @@ class Net(nn.Module):
         (len(select)).  ``coarse`` ("fused", "wide", "auto", "stream" or "any": see ``coarse_scores``)
         picks the coarse pass's kernel: the default takes boxes of at most 128 keypoints, "wide" and
         "auto" boxes of at most 256, "stream" and "any" boxes of at most 600 (every graph the matcher
-        takes); without a shortlist it is only checked: the full query has no size bound."""
+        takes); without a shortlist it is only checked: the full query has no size bound.
+
+        On a "bf16+host" index (``enroll(layout=...)``) the coarse pass reads the bf16 rows on the
+        device and the forward runs over the selected entries' fp32 rows, copied from pinned host
+        memory into a reused staging buffer (``GalleryIndex.fetch``): the same outputs bit for bit.
+        ``shortlist=M`` is the intended use there; without one the selection's rows must fit
+        ``gallery.FETCH_MAX_BYTES`` (1.89 GB, the largest shortlist's), larger ones are refused."""
         from . import gallery
         return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
                                 shortlist=shortlist, coarse=coarse)

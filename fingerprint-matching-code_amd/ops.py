@@ -2,9 +2,9 @@
 
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
-no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select`` and
-``coarse_score`` alone keep a plain-torch host path for CPU tensors: the statements of the ordering
-and of the coarse score, which the tests hold the kernels to).
+no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``,
+``coarse_score`` and ``rows_fetch`` alone keep a plain-torch host path for CPU tensors: the statements
+of the ordering, of the coarse score and of the ragged copy, which the tests hold the kernels to).
 """
 import ctypes
 
@@ -370,6 +370,68 @@ def rows_gather_scale(y, row_off, idx, nmax, coef=None, out_f=None, out_t=None, 
               int(split), _stream(y))
 
 
+def rows_fetch(src, row_off, idx, out, out_off, idx_host=None, row_off_host=None, out_off_host=None):
+    """Ragged row copy (fpm_rows_fetch): the rows of the entries idx[m] (int32 [M]) of ``src``
+    ((sum n_g, 768) fp32, graph g at rows [row_off[g], row_off[g + 1]), row_off int64 [G + 1]) packed
+    into ``out`` ((>= sum of the selected n_g, 768) fp32), entry m at rows [out_off[m], out_off[m + 1])
+    (out_off int64 [M + 1], rising from 0 by the selected n_g) -> out.
+
+    ``src`` is a device tensor, or a pinned host tensor, which the kernel reads through its device
+    mapping (the rows of a shortlist out of an index whose fp32 rows live on the host); row_off, idx,
+    out and out_off live on one device.  Checked on the host before anything is launched: dtypes,
+    contiguity, devices, every idx in [0, G), the offsets, ``out`` large enough (``idx_host`` /
+    ``row_off_host`` / ``out_off_host``: host copies, so the check needs no device synchronisation;
+    without them the device tensors are copied back).  All-CPU tensors take the torch statement of
+    the copy."""
+    for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64),
+                        ("out_off", out_off, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise _lib.FpmError("rows_fetch: %s must be a %s tensor (got %s)"
+                                % (name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise _lib.FpmError("rows_fetch: %s must be a contiguous 1-d tensor" % name)
+    for name, t in (("src", src), ("out", out)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
+                or not t.is_contiguous():
+            raise _lib.FpmError("rows_fetch: %s must be contiguous fp32 rows of 768 channels" % name)
+    for name, t in (("row_off", row_off), ("idx", idx), ("out_off", out_off)):
+        if t.device != out.device:
+            raise _lib.FpmError("rows_fetch: %s is on %s, out on %s" % (name, t.device, out.device))
+    if src.device != out.device and not (out.is_cuda and not src.is_cuda and src.is_pinned()):
+        raise _lib.FpmError("rows_fetch: src is on %s, out on %s (a host src must be pinned)"
+                            % (src.device, out.device))
+    G, M = int(row_off.numel()) - 1, int(idx.numel())
+    if G < 1:
+        raise _lib.FpmError("rows_fetch: empty gallery")
+    if out_off.numel() != M + 1:
+        raise _lib.FpmError("rows_fetch: out_off must hold %d offsets (got %d)" % (M + 1, out_off.numel()))
+    ih = torch.as_tensor(idx_host if idx_host is not None else idx.cpu()).view(-1).long()
+    oh = torch.as_tensor(row_off_host if row_off_host is not None else row_off.cpu()).view(-1).long()
+    if ih.numel() != M or oh.numel() != G + 1:
+        raise _lib.FpmError("rows_fetch: host copies of idx / row_off do not match the device tensors")
+    if int(oh[0]) != 0 or int(oh[-1]) != src.shape[0] or bool((oh[1:] < oh[:-1]).any()):
+        raise _lib.FpmError("rows_fetch: row_off must rise from 0 to the %d rows of src" % src.shape[0])
+    if M and (int(ih.min()) < 0 or int(ih.max()) >= G):
+        raise _lib.FpmError("rows_fetch: idx value outside [0, %d)" % G)
+    if M > 65535:
+        raise _lib.FpmError("rows_fetch: at most 65535 entries per call")
+    ng = oh[ih + 1] - oh[ih]
+    total = int(ng.sum())
+    if out.shape[0] < total:
+        raise _lib.FpmError("rows_fetch: out holds %d rows, the selection has %d" % (out.shape[0], total))
+    fh = torch.as_tensor(out_off_host if out_off_host is not None else out_off.cpu()).view(-1).long()
+    if not torch.equal(fh, torch.cat([torch.zeros(1, dtype=torch.int64), ng.cumsum(0)])):
+        raise _lib.FpmError("rows_fetch: out_off must rise from 0 by the selected entries' row counts")
+    if not out.is_cuda:
+        if M:
+            out[:total] = torch.cat([src[int(oh[g]):int(oh[g + 1])] for g in ih.tolist()])
+        return out
+    if M and total:
+        _lib.call("fpm_rows_fetch", _p(src), int(src.shape[0]), _p(row_off), _p(idx), G, M, int(ng.max()), _p(out),
+                  int(out.shape[0]), _p(out_off), _stream(out))
+    return out
+
+
 def rank_key(scores):
     """The 64-bit ranking key of fpm_rank_topk for a (P, G) fp32 tensor, as int64 whose signed order
     is the key's unsigned order shifted by 2^63: (order-preserving bits of the score) << 32 |
@@ -472,6 +534,11 @@ def _bf16_rne(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
 
+def _rows16(y):
+    """The suffix of a coarse kernel's entry point for the index rows ``y``: fp32, or their bf16 copy."""
+    return "_rows16" if y.dtype == torch.bfloat16 else ""
+
+
 def _coarse_score_host(y, row_off, idx, yp, coef, iters, tau, dtype):
     """The definition of the coarse score in plain torch (``dtype`` fp32 or fp64 arithmetic on the
     bf16-rounded operands): Kp = softplus(a b^T) - 0.5, pygmtools' log Sinkhorn with dummy rows,
@@ -511,7 +578,11 @@ def _coarse_score_op(op, bound, nmax, launch, y, row_off, idx, yp, coef, iters, 
                                 % (op, name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
         if t.dim() != 1 or not t.is_contiguous():
             raise _lib.FpmError("%s: %s must be a contiguous 1-d tensor" % (op, name))
-    for name, t in (("y", y), ("yp", yp), ("coef", coef)):
+    # y: the index's fp32 rows, or their bf16 copy (an index's y16: the rounding already done)
+    if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.bfloat16) or y.dim() != 2 \
+            or y.shape[1] != 768 or not y.is_contiguous():
+        raise _lib.FpmError("%s: y must be contiguous fp32 or bf16 rows of 768 channels" % op)
+    for name, t in (("yp", yp), ("coef", coef)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
                 or not t.is_contiguous():
             raise _lib.FpmError("%s: %s must be contiguous fp32 rows of 768 channels" % (op, name))
@@ -571,7 +642,10 @@ def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_ho
         P = Sinkhorn(Kp; dummy rows, iters, tau), score[b] = sum P o Kp / min(n0, n_g).
 
     y (sum n_g, 768) fp32 with row_off int64 [G + 1] and idx int32 [B] as ``rows_gather_scale`` takes
-    them; yp (n0, 768) fp32, the probe's SplineConv rows; coef (B, 768) fp32 (``coef_tanh``).  Checked
+    them, or the same rows as bf16 (``cast_bf16(y)``, an index's ``y16``: the kernel's bf16
+    instantiation, fpm_coarse_score_rows16, copies the entry's tile as it is, the same operands and the
+    same bits; so for ``coarse_score_wide`` and ``coarse_score_stream``); yp (n0, 768) fp32, the
+    probe's SplineConv rows; coef (B, 768) fp32 (``coef_tanh``).  Checked
     on the host before anything is launched: dtypes, contiguity and devices, every idx in [0, G),
     n0 and every selected n_g in [1, COARSE_NMAX = 128] (``idx_host`` / ``row_off_host``: host
     copies, so the check needs no device synchronisation).
@@ -579,8 +653,8 @@ def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_ho
     CPU tensors take the plain-torch statement of the definition, in ``dtype`` arithmetic
     (torch.float32, the default, or torch.float64) on the same bf16-rounded operands."""
     def launch(G, B, n0, iters, tau, out, ngmax):
-        _lib.call("fpm_coarse_score", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau, _p(out),
-                  _stream(y))
+        _lib.call("fpm_coarse_score" + _rows16(y), _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau,
+                  _p(out), _stream(y))
     return _coarse_score_op("coarse_score", "COARSE_NMAX", COARSE_NMAX, launch, y, row_off, idx, yp, coef, iters, tau,
                             out, idx_host, row_off_host, dtype)
 
@@ -597,8 +671,8 @@ def coarse_score_wide(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, i
     def launch(G, B, n0, iters, tau, out, ngmax):
         wsb = int(_lib.load().fpm_coarse_score_wide_ws_bytes(B))
         ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
-        _lib.call("fpm_coarse_score_wide", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau,
-                  _p(out), _p(ws), wsb, _stream(y))
+        _lib.call("fpm_coarse_score_wide" + _rows16(y), _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters,
+                  tau, _p(out), _p(ws), wsb, _stream(y))
     return _coarse_score_op("coarse_score_wide", "COARSE_WIDE_NMAX", COARSE_WIDE_NMAX, launch, y, row_off, idx, yp,
                             coef, iters, tau, out, idx_host, row_off_host, dtype)
 
@@ -616,8 +690,8 @@ def coarse_score_stream(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None,
     def launch(G, B, n0, iters, tau, out, ngmax):
         wsb = int(_lib.load().fpm_coarse_score_stream_ws_bytes(B, n0, ngmax))
         ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
-        _lib.call("fpm_coarse_score_stream", _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau,
-                  _p(out), _p(ws), wsb, _stream(y))
+        _lib.call("fpm_coarse_score_stream" + _rows16(y), _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef),
+                  iters, tau, _p(out), _p(ws), wsb, _stream(y))
     return _coarse_score_op("coarse_score_stream", "COARSE_STREAM_NMAX", COARSE_STREAM_NMAX, launch, y, row_off, idx,
                             yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
 

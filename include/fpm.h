@@ -251,6 +251,17 @@ int fpm_rows_bcast_scale(int dtype, const float* y, long rows, int B, const floa
  * G = 1 and n_0 = nmax.  B <= 65535. */
 int fpm_rows_gather_scale(int dtype, const float* y, const long* row_off, const int* idx, int G, int B, int nmax,
                           const float* coef, float* out_f, void* out_t, int split, void* stream);
+/* Ragged row copy (an index whose fp32 rows live in pinned host memory: the rows of a shortlist into a
+ * device staging buffer).  src: src_rows x 768 fp32 in any device-readable memory (a device
+ * allocation, or pinned host memory through its device mapping), graph g at rows
+ * [row_off[g], row_off[g + 1]) (row_off: G + 1 int64, device); idx: M int32 (device), M <= 65535;
+ * entry m's rows go to out rows [out_off[m], out_off[m + 1]) (out: out_rows x 768 fp32, device;
+ * out_off: M + 1 int64, device, out_off[m + 1] - out_off[m] = the entry's row count); nmax: the
+ * largest selected row count (the grid's extent).  src and out 16-byte aligned.  The caller checks
+ * idx and the offsets; an entry that violates them is not copied (nothing is read outside src or
+ * written outside out). */
+int fpm_rows_fetch(const float* src, long src_rows, const long* row_off, const int* idx, int G, int M, int nmax,
+                   float* out, long out_rows, const long* out_off, void* stream);
 /* vertex_attr_to_edge_attr (spline_conv.py:73-81): out[e] = x[src[e]] - x[dst[e]] */
 int fpm_edge_diff(const float* x, const int* src, const int* dst, long E, int D, float* out, void* stream);
 /* same, written into a padded per-pair layout and scaled: out[row[e]] = (x[src]-x[dst]) o c[pair[e]]
@@ -580,6 +591,20 @@ long fpm_coarse_score_stream_ws_bytes(int B, int n0, int ngmax);
 int fpm_coarse_score_stream(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp,
                             int n0, const float* coef, int iters, float tau, float* score, void* ws, long ws_bytes,
                             void* stream);
+/* The three kernels above over a bf16 copy of the index rows: y16 holds the (sum n_g) x 768 rows as
+ * bf16, rounded to nearest even from the fp32 rows (fpm_cast_bf16), 1536 B per row, the base 16-byte
+ * aligned.  Every other argument, every argument check and the workspace (the *_ws_bytes functions
+ * are shared) are those of the fp32 sibling.  The entry's tile is copied to LDS as it is (16-B
+ * vectors of 8 bf16, no multiply, no convert) where the sibling rounds the fp32 rows on the way in;
+ * the operands of the MFMA are therefore the same bits, and so is score[b]. */
+int fpm_coarse_score_rows16(const void* y16, const long* row_off, const int* idx, int G, int B, const float* yp,
+                            int n0, const float* coef, int iters, float tau, float* score, void* stream);
+int fpm_coarse_score_wide_rows16(const void* y16, const long* row_off, const int* idx, int G, int B, const float* yp,
+                                 int n0, const float* coef, int iters, float tau, float* score, void* ws,
+                                 long ws_bytes, void* stream);
+int fpm_coarse_score_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
+                                   const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                                   void* ws, long ws_bytes, void* stream);
 
 /* ---- profiling hooks: HIP-event timing of the dominant kernel (edge-message GEMM) ------------ */
 int fpm_profile_enable(int on);

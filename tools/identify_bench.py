@@ -9,6 +9,8 @@
     python tools/identify_bench.py --shortlist 64 --coarse stream --n 512 --large 4096
     python tools/identify_bench.py --shortlist 64 --coarse stream --n 256 --large 0 --append
                                                                        (-> profiles/identify_shortlist_stream.json)
+    python tools/identify_bench.py --shortlist 64 --layout f32,f32+bf16,bf16+host [--coarse auto --n 256] [--append]
+                                                                       (-> profiles/identify_compact.json)
 
 ``--shortlist M``: by the same protocol, the shortlisted query ``identify(shortlist=M)`` against the
 full ``identify`` in one process, at the C4 shape and at a larger gallery, with the coarse pass
@@ -20,6 +22,12 @@ same gallery, the number that decides which kernel small boxes take.
 ``identify`` is then the only other query there is) and adds that kernel alone on synthetic rows; at
 n <= 256 it also times the wide coarse pass and the wide kernel alone over the same gallery, stream
 against wide in one process: the number that decides which kernel boxes of up to 256 take.
+
+``--layout a,b,..`` (with ``--shortlist``): the index layouts against each other.  The gallery is enrolled
+once per layout in one process; per layout the device and host bytes held, the coarse pass (which reads
+the bf16 rows where the layout has them), the fetch of the shortlist's fp32 rows from pinned host memory
+("bf16+host"), the M-pair forward and the whole shortlisted query; the first layout is the baseline of
+the A/B verdicts.
 
 Shape: config C4 (one probe, n = 128 keypoints, a gallery of 1024), both dtypes.  Per dtype, in a
 fresh child process under its own time limit: one warm-up, then ``--reps`` (>= 5) timed forwards of
@@ -245,6 +253,87 @@ def child_shortlist(args):
     print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
 
 
+def child_layouts(args):
+    """``--shortlist M --layout a,b,..``: the same gallery enrolled once per index layout in this one
+    process; per layout the device / host bytes held, the coarse pass, the fetch of the M shortlisted
+    entries' rows (layouts with the fp32 rows on the host), the M-pair forward and the whole
+    shortlisted query.  The first layout listed is the baseline of the A/B margins (the project's
+    rule: the candidate's median against the baseline's best run less the baseline's spread)."""
+    import torch
+    import bench
+    import fpm
+    from fpm import params, synth
+    dev = torch.device("cuda", 0)
+    G, n, dtype, M, coarse = args.gallery, args.n, args.child, args.shortlist, args.coarse
+    layouts = args.layout.split(",")
+    probe = synth.make_graph(args.seed, 0, 0, n)
+    base = bench.make_gallery(args.seed, 1, min(G, args.distinct), n, args.gen_workers)
+    gallery = [base[i % len(base)] for i in range(G)]      # past --distinct graphs the gallery repeats them
+    net = fpm.Net(regression=True, backbone=False, dtype=dtype)
+    net.load_state_dict(params.init_params(args.seed))
+    res = dict(dtype=dtype, gallery=G, distinct_graphs=min(G, args.distinct), n=n, shortlist=M, reps=args.reps,
+               coarse=coarse, layouts={})
+    index = {}
+    for lay in layouts:
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        before = torch.cuda.memory_allocated(dev)
+        index[lay] = net.enroll(gallery, dev, layout=lay)
+        torch.cuda.synchronize()
+        ix = index[lay]
+        res["layouts"][lay] = dict(nbytes=ix.nbytes(), host_nbytes=ix.host_nbytes(),
+                                   enroll_peak_device_bytes=torch.cuda.max_memory_allocated(dev) - before,
+                                   templates_per_288_gb=int(288e9 / (ix.nbytes() / G)))
+    del gallery, base
+    res["sc_mode"] = index[layouts[0]].sc_mode
+    res["row_bytes"] = int(index[layouts[0]].y.numel()) * 4
+
+    def series(fn):
+        fn()
+        torch.cuda.synchronize()
+        return _ev(_timed(fn, args.reps))
+
+    def fresh(ix, fn):
+        # a new probe's shortlist: neither the selection's batch nor its staged rows are kept
+        ix._sel = ix._stage = None
+        return fn()
+    ref = None
+    for lay in layouts:
+        ix, r = index[lay], res["layouts"][lay]
+        short = net.identify(probe, ix, topk=10, shortlist=M, coarse=coarse)
+        torch.cuda.synchronize()
+        sidx = short["short_idx"].cpu().long()
+        ref = short if ref is None else ref
+        r["identical_to_%s" % layouts[0]] = all(bool(torch.equal(short[k], ref[k])) for k in
+                                                ("ss", "ds_mat", "perm_mat", "k_prob", "cls_prob", "top_idx",
+                                                 "top_score", "short_idx", "coarse_score", "coarse_all"))
+        r["coarse"] = series(lambda: net.coarse_scores(probe, ix, coarse=coarse))
+        read = res["row_bytes"] // (1 if ix.y16 is None else 2)
+        r["coarse"].update(index_bytes_read=read, index_tb_per_s=round(read / r["coarse"]["median_ms"] / 1e9, 3))
+        if lay == "bf16+host":
+            r["fetch"] = series(lambda: fresh(ix, lambda: ix.fetch(sidx)))
+            fb = int(ix.n[sidx].sum()) * 3072
+            r["fetch"].update(bytes=fb, gb_per_s=round(fb / r["fetch"]["median_ms"] / 1e6, 1),
+                              note="pinned host rows read by the kernel; events around one fetch: the offsets' "
+                                   "upload and the launch latency included")
+        r["forward_M"] = series(lambda: fresh(ix, lambda: net.identify(probe, ix, topk=10, select=sidx)))
+        r["shortlisted"] = series(lambda: fresh(ix, lambda: net.identify(probe, ix, topk=10, shortlist=M,
+                                                                         coarse=coarse)))
+        del short
+    b = res["layouts"][layouts[0]]
+    for lay in layouts[1:]:
+        r = res["layouts"][lay]
+        for part in ("coarse", "forward_M", "shortlisted"):
+            o, c = b[part], r[part]
+            r["ab_%s" % part] = dict(
+                baseline=layouts[0], speedup_median=round(o["median_ms"] / c["median_ms"], 3),
+                faster_margin_ms=round(o["min_ms"] - (o["max_ms"] - o["min_ms"]) - c["median_ms"], 3),
+                slower_margin_ms=round(c["min_ms"] - (c["max_ms"] - c["min_ms"]) - o["median_ms"], 3))
+            r["ab_%s" % part]["verdict"] = ("faster" if r["ab_%s" % part]["faster_margin_ms"] > 0 else
+                                            "slower" if r["ab_%s" % part]["slower_margin_ms"] > 0 else "within spread")
+    print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
+
+
 def main_shortlist(ap, args):
     lines = []
     shapes = [(args.gallery, dt) for dt in args.dtypes.split(",")]
@@ -253,7 +342,8 @@ def main_shortlist(ap, args):
     for G, dtype in shapes:
         cmd = [sys.executable, os.path.abspath(__file__), "--child", dtype, "--gallery", str(G), "--n", str(args.n),
                "--reps", str(args.reps), "--seed", str(args.seed), "--gen-workers", str(args.gen_workers),
-               "--shortlist", str(args.shortlist), "--distinct", str(args.distinct), "--coarse", args.coarse]
+               "--shortlist", str(args.shortlist), "--distinct", str(args.distinct), "--coarse", args.coarse,
+               "--layout", args.layout]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
         except subprocess.TimeoutExpired:
@@ -266,9 +356,13 @@ def main_shortlist(ap, args):
         print(json.dumps(lines[-1]), flush=True)
     name = {"fused": "identify_shortlist.json", "wide": "identify_shortlist_wide.json",
             "auto": "identify_shortlist_wide.json"}.get(args.coarse, "identify_shortlist_stream.json")
+    if args.layout != "f32":
+        name = "identify_compact.json"
     out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", name)
-    doc = dict(tool="tools/identify_bench.py --shortlist %d%s" % (args.shortlist, "" if args.coarse == "fused" else
-                                                                  " --coarse %s --n %d" % (args.coarse, args.n)),
+    doc = dict(tool="tools/identify_bench.py --shortlist %d%s%s" % (args.shortlist, "" if args.coarse == "fused" else
+                                                                    " --coarse %s --n %d" % (args.coarse, args.n),
+                                                                    "" if args.layout == "f32" else
+                                                                    " --layout %s" % args.layout),
                config="1 probe x gallery, n keypoints per graph; full = identify over every entry (the path before "
                       "the shortlist existed), shortlisted = coarse pass + rank_select + identify over the M entries",
                method="1 warm-up, `reps` queries each, HIP events around each query, median and min-max; both sides "
@@ -293,6 +387,11 @@ def main():
     ap.add_argument("--coarse", choices=("fused", "wide", "auto", "stream", "any"), default="fused",
                     help="--shortlist: the coarse pass's kernel (wide / auto: profiles/identify_shortlist_wide.json; "
                          "stream / any: profiles/identify_shortlist_stream.json)")
+    ap.add_argument("--layout", default="f32",
+                    help="--shortlist: the index layout(s), comma-separated (f32, f32+bf16, bf16+host).  Anything but "
+                         "the default 'f32' enrols the gallery once per layout in one process and records per layout "
+                         "the bytes held, the coarse pass, the fetch, the M-pair forward and the whole shortlisted "
+                         "query, the first layout the A/B baseline (profiles/identify_compact.json)")
     ap.add_argument("--append", action="store_true",
                     help="--shortlist: add the results to those the output file already holds (another --n)")
     ap.add_argument("--large", type=int, default=16384, help="--shortlist: a second, larger gallery (0: none)")
@@ -311,6 +410,8 @@ def main():
     if args.reps < 5:
         ap.error("--reps must be at least 5")
     if args.child:
+        if args.shortlist > 0 and args.layout != "f32":
+            return child_layouts(args)
         return child_shortlist(args) if args.shortlist > 0 else child(args)
     if args.shortlist > 0:
         return main_shortlist(ap, args)
