@@ -56,6 +56,12 @@ SIGNATURES = {
     "fpm_coarse_score_rows16": (I, [P, P, P, I, I, P, I, P, I, F, P, P]),
     "fpm_coarse_score_wide_rows16": (I, [P, P, P, I, I, P, I, P, I, F, P, P, L, P]),
     "fpm_coarse_score_stream_rows16": (I, [P, P, P, I, I, P, I, P, I, F, P, P, L, P]),
+    "fpm_coarse_pairs": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P]),
+    "fpm_coarse_pairs_wide": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P, L, P]),
+    "fpm_coarse_pairs_stream": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P, L, P]),
+    "fpm_coarse_pairs_rows16": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P]),
+    "fpm_coarse_pairs_wide_rows16": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P, L, P]),
+    "fpm_coarse_pairs_stream_rows16": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P, L, P]),
     "fpm_rows_fetch": (I, [P, L, P, P, I, I, I, P, L, P, P]),
     "fpm_edge_diff_padded":(I, [P, P, P, P, P, P, L, I, P, P]),
     "fpm_kron_gnn_layer_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),

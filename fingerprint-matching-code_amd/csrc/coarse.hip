@@ -33,6 +33,7 @@
 // so an entry's score is bit-identical whatever else shares the launch.  No spinning, no exchange
 // between workgroups.  LDS: 68.6 KB per workgroup, two workgroups per CU.
 #include "fpm_common.h"
+#include "coarse_probe.h"
 #include "fpm.h"
 
 namespace {
@@ -96,14 +97,18 @@ __device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const
 }
 
 // YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment).
+// PAIRS: the probe of pair b comes from a second row store (a pair list: coarse_probe.h); the lookup
+// below is the only code that differs.
 // two workgroups per CU (LDS allows it): hold the registers to two waves per SIMD
-template <typename YT>
+template <typename YT, bool PAIRS>
 __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void coarse_score_kernel(const YT* __restrict__ y,
                                                            const long* __restrict__ row_off,
                                                            const int* __restrict__ idx, int G,
                                                            const float* __restrict__ yp, int n0,
                                                            const float* __restrict__ coef, int iters, float tau,
-                                                           float* __restrict__ score) {
+                                                           float* __restrict__ score,
+                                                           const long* __restrict__ qrow_off,
+                                                           const int* __restrict__ qidx) {
     extern __shared__ float lds[];
     float* S = lds;
     float* cm = lds + S_FLOATS;              // [2][128] column partial maxima
@@ -119,6 +124,13 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     if (g >= 0 && g < G) {
         r0 = row_off[g];
         ngl = row_off[g + 1] - r0;
+    }
+    if constexpr (PAIRS) {                   // a pair list: yp is the probe row store and n0 its graph count
+        const float* yb;
+        int nb;
+        fpm::coarse_probe_of<true>(yp, n0, qrow_off, qidx, b, yb, nb);
+        yp = yb;
+        n0 = nb;
     }
     // the wrapper checks both on the host; never read outside y, never index past the 128 x 128 box
     if (ngl < 1 || ngl > CN || n0 < 1 || n0 > CN) {
@@ -334,6 +346,22 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 }  // namespace
 
 namespace {
+template <typename YT, bool PAIRS>
+int coarse_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                  const float* ypq, int n0q, const long* qrow_off, const int* qidx, const float* coef, int iters,
+                  float tau, float* score, void* stream) {
+    constexpr int lds = LDS_FLOATS * (int)sizeof(float);
+    if (hipFuncSetAttribute((const void*)coarse_score_kernel<YT, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            lds) != hipSuccess) {
+        (void)hipGetLastError();
+        fpm::set_error("coarse_score: %d bytes of LDS per workgroup refused", lds);
+        return 1;
+    }
+    hipLaunchKernelGGL((coarse_score_kernel<YT, PAIRS>), dim3((unsigned)B), dim3(CT), lds, (hipStream_t)stream, y, row_off,
+                       idx, G, ypq, n0q, coef, iters, tau, score, qrow_off, qidx);
+    return fpm::check_launch(what);
+}
+
 template <typename YT>
 int coarse_score_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
                         const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* stream) {
@@ -344,16 +372,24 @@ int coarse_score_launch(const char* what, const YT* y, const long* row_off, cons
     FPM_CHECK_ARG(y && row_off && idx && yp && coef && score,
                   "coarse_score: y, row_off, idx, yp, coef and score are required");
     if (B == 0) return 0;
-    constexpr int lds = LDS_FLOATS * (int)sizeof(float);
-    if (hipFuncSetAttribute((const void*)coarse_score_kernel<YT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess) {
-        (void)hipGetLastError();
-        fpm::set_error("coarse_score: %d bytes of LDS per workgroup refused", lds);
-        return 1;
-    }
-    hipLaunchKernelGGL(coarse_score_kernel<YT>, dim3((unsigned)B), dim3(CT), lds, (hipStream_t)stream, y, row_off, idx,
-                       G, yp, n0, coef, iters, tau, score);
-    return fpm::check_launch(what);
+    return coarse_launch<YT, false>(what, y, row_off, idx, G, B, yp, n0, nullptr, nullptr, coef, iters, tau, score, stream);
+}
+
+// the pair list: the one-probe refusals, the probe sizes read back from the device (coarse_probe.h)
+template <typename YT>
+int coarse_pairs_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                        const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
+                        float tau, float* score, void* stream) {
+    FPM_CHECK_ARG(G > 0 && Q > 0 && B >= 0, "coarse_pairs: bad sizes (G %d, Q %d, B %d)", G, Q, B);
+    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_pairs: iters >= 0 and tau > 0 required");
+    FPM_CHECK_ARG(y && row_off && idx && yq && qrow_off && qidx && coef && score,
+                  "coarse_pairs: y, row_off, idx, yq, qrow_off, qidx, coef and score are required");
+    if (B == 0) return 0;
+    long lo, hi;
+    if (fpm::coarse_pairs_probe_range(qrow_off, qidx, Q, B, stream, lo, hi)) return 1;
+    FPM_CHECK_ARG(lo >= 1 && hi <= FPM_COARSE_NMAX, "coarse_pairs: probe of %ld keypoints outside [1, COARSE_NMAX = %d]",
+                  hi > FPM_COARSE_NMAX ? hi : lo, FPM_COARSE_NMAX);
+    return coarse_launch<YT, true>(what, y, row_off, idx, G, B, yq, Q, qrow_off, qidx, coef, iters, tau, score, stream);
 }
 }  // namespace
 
@@ -368,4 +404,18 @@ extern "C" int fpm_coarse_score_rows16(const void* y16, const long* row_off, con
                                        void* stream) {
     return coarse_score_launch<bf16_t>("fpm_coarse_score_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0, coef,
                                        iters, tau, score, stream);
+}
+
+extern "C" int fpm_coarse_pairs(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
+                                const long* qrow_off, const int* qidx, int Q, const float* coef, int iters, float tau,
+                                float* score, void* stream) {
+    return coarse_pairs_launch<float>("fpm_coarse_pairs", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef, iters, tau,
+                                      score, stream);
+}
+
+extern "C" int fpm_coarse_pairs_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
+                                       const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
+                                       int iters, float tau, float* score, void* stream) {
+    return coarse_pairs_launch<bf16_t>("fpm_coarse_pairs_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq, qrow_off,
+                                       qidx, Q, coef, iters, tau, score, stream);
 }

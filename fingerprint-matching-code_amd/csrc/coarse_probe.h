@@ -1,0 +1,66 @@
+// The probe side of a coarse-score launch (coarse.hip, coarse_wide.hip, coarse_stream.hip), a
+// compile-time choice: one probe for every pair of the launch, or a pair list, in which the probe of
+// pair b is graph qidx[b] of a second ragged fp32 row store.  The kernels differ in this lookup alone.
+// Both instantiations share one argument list (the pair list's two extra pointers come last and are
+// never read by the one-probe code, which keeps its __restrict__ probe pointer), so the one-probe
+// kernels keep the registers and spills they had; the fused ones compile to the very same instructions.
+#pragma once
+#include <vector>
+
+#include "fpm_common.h"
+
+namespace fpm {
+// Pair b's probe rows and keypoint count.  One probe (PAIRS false): ypq is the probe's (n0, 768) rows and
+// n0q its keypoint count, as ever; qrow_off and qidx are not read.  A pair list: ypq is the probe row
+// store yq (sum n_q, 768), graph q at rows [qrow_off[q], qrow_off[q + 1]), n0q its graph count Q, and the
+// probe of pair b is graph qidx[b].  b is uniform over the workgroup, so the lookup is two scalar loads,
+// as idx[b] / row_off[g] are, and yp and n0 stay scalar.  A qidx outside [0, Q) gives n0 = 0, which the
+// kernel's bound check refuses (as it refuses n0 over its box) before yp is read.
+template <bool PAIRS>
+__device__ __forceinline__ void coarse_probe_of(const float* ypq, int n0q, const long* qrow_off, const int* qidx, int b,
+                                                const float*& yp, int& n0) {
+    if constexpr (PAIRS) {
+        const int q = qidx[b];
+        long q0 = 0, nql = 0;
+        if (q >= 0 && q < n0q) {
+            q0 = qrow_off[q];
+            nql = qrow_off[q + 1] - q0;
+        }
+        n0 = nql >= 1 && nql <= 0x7fffffffL ? (int)nql : 0;
+        yp = ypq + q0 * 768;
+    } else {
+        yp = ypq;
+        n0 = n0q;
+    }
+}
+
+// Host side of a pair-list entry point: the smallest and largest keypoint count among the probes that
+// qidx[0 .. B) names, so that a probe outside the kernel's box is refused by name before the launch, as
+// the one-probe entry points refuse their n0.  qidx and qrow_off are device memory: they are read back
+// on ``stream`` (B int32 + Q + 1 int64, one wait per launch).  A qidx outside [0, Q) is skipped: like a
+// bad idx it is the caller's to check, and the kernel gives that pair NaN.  Returns 1 on a HIP error.
+inline int coarse_pairs_probe_range(const long* qrow_off, const int* qidx, int Q, int B, void* stream, long& lo,
+                                    long& hi) {
+    std::vector<long> off((size_t)Q + 1);
+    std::vector<int> qi((size_t)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemcpyAsync(off.data(), qrow_off, off.size() * sizeof(long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(qi.data(), qidx, qi.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("coarse_pairs: reading qrow_off / qidx back failed");
+        return 1;
+    }
+    lo = 1;
+    hi = 1;
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        if (qi[b] < 0 || qi[b] >= Q) continue;
+        const long n = off[qi[b] + 1] - off[qi[b]];
+        lo = any && lo < n ? lo : n;
+        hi = any && hi > n ? hi : n;
+        any = true;
+    }
+    return 0;
+}
+}  // namespace fpm

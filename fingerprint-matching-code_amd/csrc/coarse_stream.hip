@@ -37,6 +37,7 @@
 // fixed by (R, C) alone, so a score is the same bits whatever shares the launch, whichever
 // workgroup computes it and however large the slots are.  LDS: 134.0 KB per workgroup.
 #include "fpm_common.h"
+#include "coarse_probe.h"
 #include "fpm.h"
 
 namespace {
@@ -121,15 +122,18 @@ __device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const
 }
 
 // YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment); the
-// probe side and everything after the tile store are the same code, so are the bits
-template <typename YT>
+// probe side and everything after the tile store are the same code, so are the bits.  PAIRS: the probe
+// of pair b comes from a second row store (a pair list: coarse_probe.h), looked up per pair of the
+// persistent walk; that lookup is the only code that differs
+template <typename YT, bool PAIRS>
 __global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const YT* __restrict__ y,
                                                                  const long* __restrict__ row_off,
                                                                  const int* __restrict__ idx, int G, int B,
-                                                                 const float* __restrict__ yp, int n0,
+                                                                 const float* __restrict__ ypq, int n0q,
                                                                  const float* __restrict__ coef, int iters, float tau,
                                                                  float* __restrict__ score, float* ws,
-                                                                 long slot_floats) {
+                                                                 long slot_floats, const long* __restrict__ qrow_off,
+                                                                 const int* __restrict__ qidx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char slds[];
     float* r1 = (float*)(slds + 2 * SBUF);   // [640] the first row step's lse
     float* u = r1 + SP;                      // [640] row potentials
@@ -152,6 +156,9 @@ __global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const YT* __res
             r0 = row_off[g];
             ngl = row_off[g + 1] - r0;
         }
+        const float* yp;
+        int n0;
+        fpm::coarse_probe_of<PAIRS>(ypq, n0q, qrow_off, qidx, b, yp, n0);
         // the wrapper checks both on the host; never read outside y, never index past the slot
         bool bad = ngl < 1 || ngl > SN || n0 < 1 || n0 > SN;
         const int ng = bad ? 1 : (int)ngl;
@@ -445,6 +452,28 @@ extern "C" long fpm_coarse_score_stream_ws_bytes(int B, int n0, int ngmax) {
 }
 
 namespace {
+// the slots are as large as the workspace allows; ``need``: the smallest that serves any pair at all
+template <typename YT, bool PAIRS>
+int coarse_stream_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                         const float* ypq, int n0q, const long* qrow_off, const int* qidx, long need, const float* coef,
+                         int iters, float tau, float* score, void* ws, long ws_bytes, void* stream) {
+    const int grid = B < SGRID ? B : SGRID;
+    const long slot_floats = ws_bytes > 0 ? (ws_bytes / (long)sizeof(float) / grid) & ~3L : 0;
+    FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
+                  "coarse_score_stream: workspace of at least %ld bytes (16-byte aligned; "
+                  "fpm_coarse_score_stream_ws_bytes) required, got %ld",
+                  need, ws_bytes);
+    if (hipFuncSetAttribute((const void*)coarse_score_stream_kernel<YT, PAIRS>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, SLDS) != hipSuccess) {
+        (void)hipGetLastError();
+        fpm::set_error("coarse_score_stream: %d bytes of LDS per workgroup refused", SLDS);
+        return 1;
+    }
+    hipLaunchKernelGGL((coarse_score_stream_kernel<YT, PAIRS>), dim3((unsigned)grid), dim3(ST), SLDS, (hipStream_t)stream,
+                       y, row_off, idx, G, B, ypq, n0q, coef, iters, tau, score, (float*)ws, slot_floats, qrow_off, qidx);
+    return fpm::check_launch(what);
+}
+
 template <typename YT>
 int coarse_score_stream_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
                                const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* ws,
@@ -457,23 +486,32 @@ int coarse_score_stream_launch(const char* what, const YT* y, const long* row_of
     FPM_CHECK_ARG(y && row_off && idx && yp && coef && score,
                   "coarse_score_stream: y, row_off, idx, yp, coef and score are required");
     if (B == 0) return 0;
-    // the slots are as large as the workspace allows; the smallest that serves any entry is ngmax = 1
-    const int grid = B < SGRID ? B : SGRID;
-    const long need = fpm_coarse_score_stream_ws_bytes(B, n0, 1);
-    const long slot_floats = ws_bytes > 0 ? (ws_bytes / (long)sizeof(float) / grid) & ~3L : 0;
-    FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
-                  "coarse_score_stream: workspace of at least %ld bytes (16-byte aligned; "
-                  "fpm_coarse_score_stream_ws_bytes) required, got %ld",
-                  need, ws_bytes);
-    if (hipFuncSetAttribute((const void*)coarse_score_stream_kernel<YT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            SLDS) != hipSuccess) {
-        (void)hipGetLastError();
-        fpm::set_error("coarse_score_stream: %d bytes of LDS per workgroup refused", SLDS);
-        return 1;
-    }
-    hipLaunchKernelGGL(coarse_score_stream_kernel<YT>, dim3((unsigned)grid), dim3(ST), SLDS, (hipStream_t)stream, y,
-                       row_off, idx, G, B, yp, n0, coef, iters, tau, score, (float*)ws, slot_floats);
-    return fpm::check_launch(what);
+    // the smallest workspace that serves any entry is ngmax = 1
+    return coarse_stream_launch<YT, false>(what, y, row_off, idx, G, B, yp, n0, nullptr, nullptr,
+                                           fpm_coarse_score_stream_ws_bytes(B, n0, 1), coef, iters, tau, score, ws,
+                                           ws_bytes, stream);
+}
+
+// the pair list: the one-probe refusals, the probe sizes read back from the device (coarse_probe.h).
+// The slots are sized by the caller from the largest probe and the largest entry of the launch
+// (fpm_coarse_score_stream_ws_bytes(B, n0max, ngmax)); a pair whose block does not fit its slot gets NaN
+template <typename YT>
+int coarse_pairs_stream_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                               const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
+                               int iters, float tau, float* score, void* ws, long ws_bytes, void* stream) {
+    FPM_CHECK_ARG(G > 0 && Q > 0 && B >= 0, "coarse_pairs_stream: bad sizes (G %d, Q %d, B %d)", G, Q, B);
+    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_pairs_stream: iters >= 0 and tau > 0 required");
+    FPM_CHECK_ARG(y && row_off && idx && yq && qrow_off && qidx && coef && score,
+                  "coarse_pairs_stream: y, row_off, idx, yq, qrow_off, qidx, coef and score are required");
+    if (B == 0) return 0;
+    long lo, hi;
+    if (fpm::coarse_pairs_probe_range(qrow_off, qidx, Q, B, stream, lo, hi)) return 1;
+    FPM_CHECK_ARG(lo >= 1 && hi <= FPM_COARSE_STREAM_NMAX,
+                  "coarse_pairs_stream: probe of %ld keypoints outside [1, COARSE_STREAM_NMAX = %d]",
+                  hi > FPM_COARSE_STREAM_NMAX ? hi : lo, FPM_COARSE_STREAM_NMAX);
+    return coarse_stream_launch<YT, true>(what, y, row_off, idx, G, B, yq, Q, qrow_off, qidx,
+                                          fpm_coarse_score_stream_ws_bytes(B, (int)hi, 1), coef, iters, tau, score, ws,
+                                          ws_bytes, stream);
 }
 }  // namespace
 
@@ -489,4 +527,19 @@ extern "C" int fpm_coarse_score_stream_rows16(const void* y16, const long* row_o
                                               float* score, void* ws, long ws_bytes, void* stream) {
     return coarse_score_stream_launch<bf16_t>("fpm_coarse_score_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B,
                                               yp, n0, coef, iters, tau, score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_pairs_stream(const float* y, const long* row_off, const int* idx, int G, int B,
+                                       const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
+                                       int iters, float tau, float* score, void* ws, long ws_bytes, void* stream) {
+    return coarse_pairs_stream_launch<float>("fpm_coarse_pairs_stream", y, row_off, idx, G, B, yq, qrow_off, qidx, Q,
+                                             coef, iters, tau, score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_pairs_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
+                                              const float* yq, const long* qrow_off, const int* qidx, int Q,
+                                              const float* coef, int iters, float tau, float* score, void* ws,
+                                              long ws_bytes, void* stream) {
+    return coarse_pairs_stream_launch<bf16_t>("fpm_coarse_pairs_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B,
+                                              yq, qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
 }

@@ -31,6 +31,7 @@
 // whichever workgroup computes it.  No spinning, no exchange between workgroups.  LDS: 93.0 KB per
 // workgroup, one workgroup per CU.
 #include "fpm_common.h"
+#include "coarse_probe.h"
 #include "fpm.h"
 
 namespace {
@@ -125,14 +126,18 @@ __device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const
 }
 
 // YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment); the
-// probe side and everything after the tile store are the same code, so are the bits
-template <typename YT>
+// probe side and everything after the tile store are the same code, so are the bits.  PAIRS: the probe
+// of pair b comes from a second row store (a pair list: coarse_probe.h), looked up per pair of the
+// persistent walk; that lookup is the only code that differs
+template <typename YT, bool PAIRS>
 __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restrict__ y,
                                                                const long* __restrict__ row_off,
                                                                const int* __restrict__ idx, int G, int B,
-                                                               const float* __restrict__ yp, int n0,
+                                                               const float* __restrict__ ypq, int n0q,
                                                                const float* __restrict__ coef, int iters, float tau,
-                                                               float* __restrict__ score, float* __restrict__ ws) {
+                                                               float* __restrict__ score, float* __restrict__ ws,
+                                                               const long* __restrict__ qrow_off,
+                                                               const int* __restrict__ qidx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wlds[];
     float* rm = (float*)(wlds + 2 * WBUF);   // [2][256] row partial maxima (per column wave)
     float* rs = rm + 2 * WN;                 // [2][256] row partial sums
@@ -152,6 +157,9 @@ __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restr
             r0 = row_off[g];
             ngl = row_off[g + 1] - r0;
         }
+        const float* yp;
+        int n0;
+        fpm::coarse_probe_of<PAIRS>(ypq, n0q, qrow_off, qidx, b, yp, n0);
         // the wrapper checks both on the host; never read outside y, never index past the 256 x 256 box
         if (ngl < 1 || ngl > WN || n0 < 1 || n0 > WN) {   // uniform over the workgroup
             if (threadIdx.x == 0) score[b] = __uint_as_float(0x7FC00000u);
@@ -427,6 +435,25 @@ extern "C" long fpm_coarse_score_wide_ws_bytes(int B) {
 }
 
 namespace {
+template <typename YT, bool PAIRS>
+int coarse_wide_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                       const float* ypq, int n0q, const long* qrow_off, const int* qidx, const float* coef, int iters,
+                       float tau, float* score, void* ws, long ws_bytes, void* stream) {
+    const long need = fpm_coarse_score_wide_ws_bytes(B);
+    FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
+                  "coarse_score_wide: workspace of %ld bytes (16-byte aligned) required, got %ld", need, ws_bytes);
+    if (hipFuncSetAttribute((const void*)coarse_score_wide_kernel<YT, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            WLDS) != hipSuccess) {
+        (void)hipGetLastError();
+        fpm::set_error("coarse_score_wide: %d bytes of LDS per workgroup refused", WLDS);
+        return 1;
+    }
+    const int grid = B < WGRID ? B : WGRID;
+    hipLaunchKernelGGL((coarse_score_wide_kernel<YT, PAIRS>), dim3((unsigned)grid), dim3(WT), WLDS, (hipStream_t)stream, y,
+                       row_off, idx, G, B, ypq, n0q, coef, iters, tau, score, (float*)ws, qrow_off, qidx);
+    return fpm::check_launch(what);
+}
+
 template <typename YT>
 int coarse_score_wide_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
                              const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* ws,
@@ -439,19 +466,27 @@ int coarse_score_wide_launch(const char* what, const YT* y, const long* row_off,
     FPM_CHECK_ARG(y && row_off && idx && yp && coef && score,
                   "coarse_score_wide: y, row_off, idx, yp, coef and score are required");
     if (B == 0) return 0;
-    const long need = fpm_coarse_score_wide_ws_bytes(B);
-    FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
-                  "coarse_score_wide: workspace of %ld bytes (16-byte aligned) required, got %ld", need, ws_bytes);
-    if (hipFuncSetAttribute((const void*)coarse_score_wide_kernel<YT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            WLDS) != hipSuccess) {
-        (void)hipGetLastError();
-        fpm::set_error("coarse_score_wide: %d bytes of LDS per workgroup refused", WLDS);
-        return 1;
-    }
-    const int grid = B < WGRID ? B : WGRID;
-    hipLaunchKernelGGL(coarse_score_wide_kernel<YT>, dim3((unsigned)grid), dim3(WT), WLDS, (hipStream_t)stream, y,
-                       row_off, idx, G, B, yp, n0, coef, iters, tau, score, (float*)ws);
-    return fpm::check_launch(what);
+    return coarse_wide_launch<YT, false>(what, y, row_off, idx, G, B, yp, n0, nullptr, nullptr, coef, iters, tau, score, ws,
+                                         ws_bytes, stream);
+}
+
+// the pair list: the one-probe refusals, the probe sizes read back from the device (coarse_probe.h)
+template <typename YT>
+int coarse_pairs_wide_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
+                             const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
+                             float tau, float* score, void* ws, long ws_bytes, void* stream) {
+    FPM_CHECK_ARG(G > 0 && Q > 0 && B >= 0, "coarse_pairs_wide: bad sizes (G %d, Q %d, B %d)", G, Q, B);
+    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_pairs_wide: iters >= 0 and tau > 0 required");
+    FPM_CHECK_ARG(y && row_off && idx && yq && qrow_off && qidx && coef && score,
+                  "coarse_pairs_wide: y, row_off, idx, yq, qrow_off, qidx, coef and score are required");
+    if (B == 0) return 0;
+    long lo, hi;
+    if (fpm::coarse_pairs_probe_range(qrow_off, qidx, Q, B, stream, lo, hi)) return 1;
+    FPM_CHECK_ARG(lo >= 1 && hi <= FPM_COARSE_WIDE_NMAX,
+                  "coarse_pairs_wide: probe of %ld keypoints outside [1, COARSE_WIDE_NMAX = %d]",
+                  hi > FPM_COARSE_WIDE_NMAX ? hi : lo, FPM_COARSE_WIDE_NMAX);
+    return coarse_wide_launch<YT, true>(what, y, row_off, idx, G, B, yq, Q, qrow_off, qidx, coef, iters, tau, score, ws,
+                                        ws_bytes, stream);
 }
 }  // namespace
 
@@ -467,4 +502,19 @@ extern "C" int fpm_coarse_score_wide_rows16(const void* y16, const long* row_off
                                             float* score, void* ws, long ws_bytes, void* stream) {
     return coarse_score_wide_launch<bf16_t>("fpm_coarse_score_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp,
                                             n0, coef, iters, tau, score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_pairs_wide(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
+                                     const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
+                                     float tau, float* score, void* ws, long ws_bytes, void* stream) {
+    return coarse_pairs_wide_launch<float>("fpm_coarse_pairs_wide", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef,
+                                           iters, tau, score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_pairs_wide_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
+                                            const float* yq, const long* qrow_off, const int* qidx, int Q,
+                                            const float* coef, int iters, float tau, float* score, void* ws,
+                                            long ws_bytes, void* stream) {
+    return coarse_pairs_wide_launch<bf16_t>("fpm_coarse_pairs_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
+                                            qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
 }

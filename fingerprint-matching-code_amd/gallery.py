@@ -23,6 +23,13 @@ bytes ("f32+bf16": the copy beside the fp32 rows).  The exact forward needs fp32
 M <= 1024 shortlisted entries, so "bf16+host" keeps them in pinned host memory and ``fetch``es those M
 entries per query (``fpm_rows_fetch``): 1.5 KB per keypoint on the device, twice the gallery per GPU,
 and every output of ``identify(shortlist=M)`` the same bits as from the "f32" layout.
+
+Probe sets (``Net.identify_many``, ``coarse_scores_many``, ``match_pairs``): the probes enrolled like a
+gallery, so that many probes are searched at once over (probe, entry) pair lists: the coarse kernels'
+pair-list instantiations (``ops.coarse_pairs``) score all pairs in bounded launches, and the exact
+forward runs in groups of probes (``probe_groups``) on batches whose two sides are both gathered from
+cached rows (``pair_batch``).  Every score and output is the bits of the one-probe path's for the same
+pair and padded box.
 """
 import hashlib
 
@@ -33,7 +40,7 @@ from . import config as C
 from . import ops
 from ._lib import FpmError
 from .batch import DeviceBatch, ORDER_MIN_NMAX, ORDER_ON, hilbert_order
-from .model import _CachedSide
+from .model import _CachedSide, _cached_sides
 
 FORMAT = 1                    # a saved "f32" index; the other layouts write FORMAT_LAYOUTS
 FORMAT_LAYOUTS = 2
@@ -203,6 +210,14 @@ class GalleryIndex:
                 raise FpmError("identify: select must name entries in [0, %d)" % G)
         if self._sel is not None and torch.equal(self._sel[0], sel):
             return self._sel
+        self._sel = (sel, self._gather(sel))
+        return self._sel
+
+    def _gather(self, sel):
+        """One side's batch fields of the pairs whose graph on that side is entry sel[b] (host int64,
+        checked by the caller; repeats are fine), as DeviceBatch.from_pairs lays that side out.  Reads
+        and writes no cache: ``_selection`` keeps the last one-probe selection, a pair batch
+        (``pair_batch``) gathers each side afresh."""
         dev = self.device
         B = int(sel.numel())
         n2 = self.n[sel]
@@ -226,8 +241,7 @@ class GalleryIndex:
             P2 = torch.zeros(B, nmax, 2, device=dev, dtype=torch.float32)
             P2[rows, loc] = self.P[loc + self.row_off[sel_d][rows]]
             f["ord2"] = hilbert_order(P2, n2, nmax)
-        self._sel = (sel, f)
-        return self._sel
+        return f
 
 
 class _GalleryBatch(DeviceBatch):
@@ -457,15 +471,29 @@ def _check_coarse(coarse, what):
 
 def coarse_routes(n0, ng, coarse="any"):
     """The kernel of each pair of a probe of ``n0`` keypoints and entries of ``ng`` keypoints (host
-    tensor), by number: 0 fused, 1 wide, 2 stream -> host int64 tensor.  "fused" / "wide" / "stream":
-    that kernel for every pair; "auto": fused when both sides fit COARSE_NMAX, wide otherwise; "any":
-    fused when both sides fit COARSE_NMAX, wide when both fit COARSE_WIDE_NMAX, stream otherwise.
-    The route depends on the pair alone.  Refuses what the route's largest kernel does not take."""
+    tensor), by number: 0 fused, 1 wide, 2 stream -> host int64 tensor.  ``n0``: one probe's count, or
+    (a pair list) a host tensor of ng's length, the probe's count of each pair.  "fused" / "wide" /
+    "stream": that kernel for every pair; "auto": fused when both sides fit COARSE_NMAX, wide otherwise;
+    "any": fused when both sides fit COARSE_NMAX, wide when both fit COARSE_WIDE_NMAX, stream otherwise.
+    The route depends on the pair alone (its larger side).  Refuses what the route's largest kernel
+    does not take."""
     _check_coarse(coarse, "coarse_scores")
-    n0 = int(n0)
     ng = torch.as_tensor(ng).view(-1).long().cpu()
-    top = max(n0, int(ng.max()))
-    low = min(n0, int(ng.min()))
+    n0 = torch.as_tensor(n0).view(-1).long().cpu()
+    if n0.numel() not in (1, ng.numel()):
+        raise FpmError("coarse_routes: n0 must be one count or one per pair (%d for %d pairs)" % (n0.numel(), ng.numel()))
+    _check_route_bounds(max(int(n0.max()), int(ng.max())), min(int(n0.min()), int(ng.min())), coarse)
+    if coarse in ("fused", "wide", "stream"):
+        return torch.full_like(ng, ("fused", "wide", "stream").index(coarse))
+    side = torch.maximum(ng, n0.expand_as(ng))                   # the pair's larger side
+    rt = (side > ops.COARSE_NMAX).long()
+    if coarse == "any":
+        rt += (side > ops.COARSE_WIDE_NMAX).long()
+    return rt
+
+
+def _check_route_bounds(top, low, coarse):
+    """The refusals of ``coarse_routes`` from the largest and the smallest graph of the query."""
     if coarse == "fused":
         if top > ops.COARSE_NMAX or low < 1:
             raise FpmError("coarse_scores: a graph of %d keypoints; the coarse pass takes boxes up to COARSE_NMAX = %d "
@@ -479,13 +507,6 @@ def coarse_routes(n0, ng, coarse="any"):
         raise FpmError("coarse_scores: a graph of %d keypoints; the streamed coarse pass takes boxes up to "
                        "COARSE_STREAM_NMAX = %d (identify without a shortlist has no such bound)"
                        % (top, ops.COARSE_STREAM_NMAX))
-    if coarse in ("fused", "wide", "stream"):
-        return torch.full_like(ng, ("fused", "wide", "stream").index(coarse))
-    side = torch.clamp(ng, min=n0)                               # the pair's larger side
-    rt = (side > ops.COARSE_NMAX).long()
-    if coarse == "any":
-        rt += (side > ops.COARSE_WIDE_NMAX).long()
-    return rt
 
 
 def _coarse_launch(route, index, sel_d, sel32, yp, cf, out, iters, tau):
@@ -601,3 +622,276 @@ def _identify_shortlist(net, probes, index, topk, select, score, chunks, shortli
         o["short_idx"], o["coarse_score"], o["coarse_all"] = short[i], csc[i], call[i]
         outs.append(o)
     return outs[0] if single else outs
+
+
+# ---- probe sets: many probes against an enrolled gallery at once -----------------------------------
+COARSE_PAIRS_CHUNK = 16384   # pairs per coarse launch: 48 MB of coefficient scratch, whatever the two sets
+_PAIR_KERNELS = ("fused", "wide", "stream")                      # ops.coarse_pairs' kernel by route number
+
+
+class _PairBatch(DeviceBatch):
+    """A batch over a pair list (q_b, g_b) of a probe set and a gallery index, laid out like
+    ``DeviceBatch.from_pairs``, except that no node features are staged on either side: x is empty and
+    ``cached`` is a pair of model._CachedSide, naming each pair's rows in the two indexes.  No shared
+    side: repeated probes and entries are ordinary pairs."""
+
+    def split_range(self, b0, b1):
+        if not 0 <= b0 < b1 <= self.B:
+            raise ValueError("split_range: bad pair range [%d, %d) of %d" % (b0, b1, self.B))
+        ws, ss, ds, ps = [], [], [], []
+        for side in range(2):
+            nm = self.nmax[side]
+            e0, e1 = int(self.edge_off[side][b0]), int(self.edge_off[side][b1])
+            ws.append(self.w[side][b0:b1])
+            ss.append((self.src[side][e0:e1] - b0 * nm).contiguous())
+            ds.append((self.dst[side][e0:e1] - b0 * nm).contiguous())
+            ps.append(self.pseudo[side][e0:e1])
+        eo = [self.edge_off[side][b0:b1 + 1] - self.edge_off[side][b0] for side in range(2)]
+        sub = _PairBatch(b1 - b0, self.n_host[0][b0:b1], self.n_host[1][b0:b1], list(self.x), ws, ss, ds, ps,
+                         self.device, nmax=self.nmax, edge_off=eo, shared0=False)
+        sub.pair_range = (b0, b1)
+        sub.ord2 = None if self.ord2 is None else self.ord2[b0:b1]
+        sub.cached = tuple(c.slice(b0, b1) for c in _cached_sides(self))
+        sub.sc_mode = self.sc_mode
+        return sub
+
+    def to(self, device, non_blocking=True):
+        if torch.device(device) != self.device:
+            raise FpmError("a pair batch stays on its indexes' device")
+        return self
+
+
+def _check_probe_set(probes, index, what):
+    """A probe set: an index enrolled from the probe graphs, its fp32 rows on the gallery's device,
+    made by the same SplineConv arithmetic and weights as the gallery."""
+    if not isinstance(probes, GalleryIndex):
+        raise FpmError("%s: probes must be a probe set: a GalleryIndex enrolled from the probe graphs (Net.enroll)"
+                       % what)
+    if probes.layout == "bf16+host":
+        raise FpmError("%s: the probe set's layout is 'bf16+host'; a probe set keeps its fp32 rows on the device "
+                       "(layout 'f32' or 'f32+bf16')" % what)
+    if probes.device != index.device:
+        raise FpmError("%s: the probe set is on device %s, the gallery on %s" % (what, probes.device, index.device))
+    if probes.sc_mode != index.sc_mode:
+        raise FpmError("%s: the probe set was enrolled with sc_mode %r, the gallery with %r"
+                       % (what, probes.sc_mode, index.sc_mode))
+    if probes.weights_id != index.weights_id:
+        raise FpmError("%s: the probe set and the gallery were enrolled with different SplineConv weights (weights_id); "
+                       "enroll them with the same net" % what)
+
+
+def _check_many(net, probes, index, what):
+    """The refusals shared by ``match_pairs``, ``coarse_scores_many`` and ``identify_many``: the probe
+    set's own (they need no net), then those of ``identify``."""
+    if not isinstance(index, GalleryIndex):
+        raise FpmError("%s: index must be a GalleryIndex (Net.enroll)" % what)
+    _check_probe_set(probes, index, what)
+    if net.training:
+        raise FpmError("%s: inference only (call net.eval()); training through an index is not supported" % what)
+    if net.use_graphs:
+        raise FpmError("%s: cached-gallery forwards are eager; switch HIP-graph replay (use_graphs) off" % what)
+    _check_query(net, index, what)
+
+
+def pair_batch(probes, index, pairs):
+    """The batch of the pair list ``pairs`` ((B, 2) host int64: probe number, entry number, both in
+    range) over a probe set and a gallery index -> _PairBatch.  On a "bf16+host" gallery the distinct
+    entries' fp32 rows are fetched and the pairs renumbered to the staging buffer."""
+    dev = index.device
+    q, g = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+    f0, f1 = probes._gather(q), index._gather(g)
+    B = int(q.numel())
+    empty = torch.empty(0, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
+    bt = _PairBatch(B, f0["n"], f1["n"], [empty, empty], [f0["w"], f1["w"]], [f0["src"], f1["src"]],
+                    [f0["dst"], f1["dst"]], [f0["pseudo"], f1["pseudo"]], dev, nmax=[f0["nmax"], f1["nmax"]],
+                    edge_off=[f0["edge_off"], f1["edge_off"]], shared0=False)
+    c0 = _CachedSide(probes.y, probes.row_off, probes.row_off_host, f0["idx"], f0["idx_host"])
+    if index.layout == "bf16+host":
+        uniq, inv = torch.unique(g, return_inverse=True)
+        ys, off_d, off_h = index.fetch(uniq)
+        inv32 = inv.to(torch.int32).contiguous()
+        c1 = _CachedSide(ys, off_d, off_h, inv32.to(dev), inv32)
+    else:
+        c1 = _CachedSide(index.y, index.row_off, index.row_off_host, f1["idx"], f1["idx_host"])
+    bt.cached = (c0, c1)
+    bt.sc_mode = index.sc_mode
+    bt.ord2 = f1["ord2"]
+    return bt
+
+
+def _run_pairs(net, probes, index, pairs, chunks):
+    keep = net.prologue_graph
+    net.prologue_graph = 0                  # eager prologue: no capture per pair batch
+    try:
+        with torch.cuda.device(index.device):
+            return net.run(pair_batch(probes, index, pairs), chunks=chunks)
+    finally:
+        net.prologue_graph = keep
+
+
+def match_pairs(net, probes, index, pairs, chunks=None):
+    """``Net.match_pairs``: see there."""
+    _check_many(net, probes, index, "match_pairs")
+    pairs = torch.as_tensor(pairs, dtype=torch.int64).cpu()
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0:
+        raise FpmError("match_pairs: pairs must be a non-empty list of (probe number, entry number)")
+    if int(pairs[:, 0].min()) < 0 or int(pairs[:, 0].max()) >= probes.G:
+        raise FpmError("match_pairs: a probe number outside [0, %d)" % probes.G)
+    if int(pairs[:, 1].min()) < 0 or int(pairs[:, 1].max()) >= index.G:
+        raise FpmError("match_pairs: an entry number outside [0, %d)" % index.G)
+    return _run_pairs(net, probes, index, pairs, chunks)
+
+
+def _coarse_pairs_order(p0, p1, Qs, Gs):
+    """The pairs at places [p0, p1) of the Qs x Gs coarse pass -> (probe position, entry position, where
+    their scores go in the flattened (Qs, Gs) result; None: the slice [p0, p1) itself).  Probe-major:
+    place p is pair (p // Gs, p % Gs).  Scores do not depend on the order; the entry-major alternative
+    (``tools/identify_bench.py --probes``: an entry's probes on one XCD) was A/B-tested once and not kept
+    (DESIGN 3a)."""
+    lin = torch.arange(p0, p1, dtype=torch.int64)
+    return torch.div(lin, Gs, rounding_mode="floor"), lin % Gs, None
+
+
+def coarse_scores_many(net, probes, index, probe_select=None, select=None, coarse="fused"):
+    """``Net.coarse_scores_many``: see there."""
+    _check_coarse(coarse, "coarse_scores_many")
+    _check_many(net, probes, index, "coarse_scores_many")
+    psel = _select_host(probes, probe_select, "coarse_scores_many (probe_select)")
+    sel = _select_host(index, select, "coarse_scores_many")
+    nq, ng = probes.n[psel].long(), index.n[sel].long()
+    _check_route_bounds(max(int(nq.max()), int(ng.max())), min(int(nq.min()), int(ng.min())), coarse)
+    dev = index.device
+    wp = net.packed(dev)
+    Qs, Gs = int(psel.numel()), int(sel.numel())
+    total = Qs * Gs
+    out = torch.empty(Qs, Gs, device=dev, dtype=torch.float32)
+    flat = out.view(-1)                      # pair (i, j) at i * Gs + j: a launch's pairs are one slice of it
+    rows = index.y if index.y16 is None else index.y16
+    step = max(1, int(COARSE_PAIRS_CHUNK))
+    coef = torch.empty(min(total, step), C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
+
+    def launch(route, q32, g32, cf, dst):
+        ops.coarse_pairs(rows, index.row_off, g32.to(dev), probes.y, probes.row_off, q32.to(dev), cf,
+                         kernel=_PAIR_KERNELS[route], iters=C.SK_ITER_NUM, tau=net.tau, out=dst, gidx_host=g32,
+                         qidx_host=q32, row_off_host=index.row_off_host, qrow_off_host=probes.row_off_host)
+
+    with torch.cuda.device(dev):
+        for p0 in range(0, total, step):
+            p1 = min(total, p0 + step)
+            qi, gi, where = _coarse_pairs_order(p0, p1, Qs, Gs)
+            dst = flat[p0:p1] if where is None else torch.empty(p1 - p0, device=dev, dtype=torch.float32)
+            q, g = psel[qi], sel[gi]
+            rt = coarse_routes(nq[qi], ng[gi], coarse)
+            # the forward's own coefficients of each pair (the one-probe pass computes the same rows)
+            gw = ops.global_weights(probes.w[q.to(dev)].contiguous(), index.w[g.to(dev)].contiguous())
+            cf = coef[:p1 - p0]
+            ops.coef_tanh(gw, wp["aff_wT"], wp["aff_b"], cf)
+            q32, g32 = q.to(torch.int32), g.to(torch.int32)
+            kinds = torch.unique(rt).tolist()
+            if len(kinds) == 1:
+                launch(kinds[0], q32, g32, cf, dst)
+            for route in kinds if len(kinds) > 1 else ():        # each kernel's pairs, the scores scattered back
+                pos = torch.nonzero(rt == route).view(-1)
+                pos_d = pos.to(dev)
+                part = torch.empty(int(pos.numel()), device=dev, dtype=torch.float32)
+                launch(route, q32[pos].contiguous(), g32[pos].contiguous(), cf[pos_d].contiguous(), part)
+                dst[pos_d] = part
+            if where is not None:
+                flat[where.to(dev)] = dst
+    return out
+
+
+def probe_groups(n_probe_host, pairs_per_probe, group_pairs):
+    """The groups of the exact stage of ``identify_many`` -> list of lists of probe positions.  Probes
+    are taken in stable ascending order of keypoint count (``n_probe_host``), so a group's padded box
+    stays tight; consecutive probes share a group while the group's pairs stay within ``group_pairs``
+    (``pairs_per_probe``: one count, or one per probe); a probe whose own pairs exceed ``group_pairs``
+    is a group alone.  Every probe is in exactly one group; deterministic."""
+    n = torch.as_tensor(n_probe_host).view(-1).long().cpu()
+    P = int(n.numel())
+    per = torch.as_tensor(pairs_per_probe).view(-1).long().cpu()
+    if per.numel() == 1:
+        per = per.expand(P)
+    if per.numel() != P:
+        raise FpmError("probe_groups: pairs_per_probe must be one count or one per probe")
+    cap = int(group_pairs)
+    if cap < 1 or (P and int(per.min()) < 1):
+        raise FpmError("probe_groups: group_pairs and every probe's pair count must be at least 1")
+    groups, cur, used = [], [], 0
+    for i in torch.argsort(n, stable=True).tolist():
+        k = int(per[i])
+        if cur and used + k > cap:
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += k
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
+                  coarse="fused", chunks=None, group_pairs=1024, exclude_self=False):
+    """``Net.identify_many``: see there."""
+    what = "identify_many"
+    _check_coarse(coarse, what)
+    if score not in SCORES:
+        raise FpmError("%s: score must be one of %s" % (what, SCORES))
+    if exclude_self and probes is not index:
+        raise FpmError("%s: exclude_self leaves out the pair (q, entry q) of an index searched against itself; "
+                       "pass the index as its own probe set (probes is index)" % what)
+    _check_many(net, probes, index, what)
+    psel = _select_host(probes, probe_select, "%s (probe_select)" % what)
+    sel = _select_host(index, select, what)
+    Qs, Gs = int(psel.numel()), int(sel.numel())
+    dev = index.device
+    if exclude_self and Gs < 2:
+        raise FpmError("%s: exclude_self needs at least two selected entries" % what)
+    short = csc = call = None
+    with torch.cuda.device(dev):
+        psel_d, sel_d = psel.to(dev), sel.to(dev)
+        own = (psel_d.view(-1, 1) == sel_d.view(1, -1)) if exclude_self else None
+        if shortlist is not None:
+            M = int(shortlist)
+            if not 1 <= M <= ops.RANK_SELECT_KMAX:
+                raise FpmError("%s: shortlist = %d outside [1, %d]" % (what, M, ops.RANK_SELECT_KMAX))
+            M = min(M, Gs - 1 if exclude_self else Gs)
+            call = coarse_scores_many(net, probes, index, probe_select=psel, select=sel, coarse=coarse)
+            ranked = call if own is None else call.masked_fill(own, float("-inf"))
+            pos, csc = ops.rank_select(ranked, M)
+            ent_d = sel_d[pos.long()]                            # (Qs, M) entry numbers, coarse-rank order
+            short = ent_d.to(torch.int32)
+        elif own is None:
+            ent_d = sel_d.view(1, Gs).expand(Qs, Gs)
+        else:
+            # every selected entry but the probe's own
+            if not bool((own.sum(1) == 1).all()):
+                raise FpmError("%s: exclude_self without a shortlist needs every probe of probe_select exactly once "
+                               "in select" % what)
+            ent_d = sel_d.view(1, Gs).expand(Qs, Gs)[~own].view(Qs, Gs - 1)
+        ent = ent_d.cpu()                                        # the pair lists shape the host-side batches: one copy
+    per = int(ent.shape[1])
+    groups = probe_groups(probes.n[psel], per, group_pairs)
+    outs = [None] * Qs
+    scores = torch.empty(Qs, per, device=dev, dtype=torch.float32)
+    for gi, grp in enumerate(groups):
+        gp = torch.tensor(grp, dtype=torch.int64)
+        pairs = torch.stack([psel[gp].view(-1, 1).expand(-1, per).reshape(-1), ent[gp].reshape(-1)], 1)
+        o = _run_pairs(net, probes, index, pairs, chunks)
+        Bg = int(pairs.shape[0])
+        for k, i in enumerate(grp):
+            b0, b1 = k * per, (k + 1) * per
+            d = {key: (v[b0:b1] if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == Bg else v)
+                 for key, v in o.items()}
+            d["group"] = (gi, b0, b1)
+            scores[i] = d[score].view(-1)
+            outs[i] = d
+    with torch.cuda.device(dev):
+        k = max(1, min(int(topk), per, 128))
+        ti, ts = ops.rank_topk(scores, k)
+        ti = torch.gather(ent_d, 1, ti.long()).to(torch.int32)
+    for i, d in enumerate(outs):
+        d["top_idx"], d["top_score"] = ti[i], ts[i]
+        if short is not None:
+            d["short_idx"], d["coarse_score"], d["coarse_all"] = short[i], csc[i], call[i]
+    return outs

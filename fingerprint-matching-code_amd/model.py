@@ -94,16 +94,26 @@ class _SharedProbe:
 
 
 class _CachedSide:
-    """Enrolled gallery (fpm.gallery): side 1's SplineConv output comes from an index's cached rows.
+    """Enrolled gallery (fpm.gallery): a side's SplineConv output comes from an index's cached rows.
     ``y`` / ``row_off``: the index's fp32 rows and graph row offsets (device; ``row_off_host`` its host
-    copy); ``idx`` (device int32) / ``idx_host``: the gallery entry of each pair of the (sub-)batch.
-    Handed to _spline_side as side 1's x_op; a pipeline chunk slices idx, never rows."""
+    copy); ``idx`` (device int32) / ``idx_host``: the index entry of each pair of the (sub-)batch.
+    Handed to _spline_side as that side's x_op; a pipeline chunk slices idx, never rows.  A batch's
+    ``cached`` is one _CachedSide (side 1: a probe x gallery batch) or a pair (side 0, side 1), either of
+    which may be None (a pair batch over a probe set and a gallery has both: ``_cached_sides``)."""
 
     def __init__(self, y, row_off, row_off_host, idx, idx_host):
         self.y, self.row_off, self.row_off_host, self.idx, self.idx_host = y, row_off, row_off_host, idx, idx_host
 
     def slice(self, b0, b1):
         return _CachedSide(self.y, self.row_off, self.row_off_host, self.idx[b0:b1], self.idx_host[b0:b1])
+
+
+def _cached_sides(bt):
+    """(side 0's, side 1's) _CachedSide of a batch, None where that side runs its own SplineConv."""
+    c = getattr(bt, "cached", None)
+    if c is None:
+        return (None, None)
+    return tuple(c) if isinstance(c, (tuple, list)) else (None, c)
 
 
 class _TailView:
@@ -887,8 +897,8 @@ class Net(nn.Module):
         dev = part.device
         x_ops = tuple(None if t is None else t if isinstance(t, _SharedProbe) else t[b0 * part.nmax[s]:b1 * part.nmax[s]]
                       for s, t in enumerate(xop or (None, None)))
-        if getattr(part, "cached", None) is not None:
-            x_ops = (x_ops[0], part.cached)        # this chunk's slice of the gallery selection
+        # a cached side: this chunk's slice of the index entries in place of operand rows
+        x_ops = tuple(x if c is None else c for x, c in zip(x_ops, _cached_sides(part)))
         r = self.run_gpu_stage(part, keep_feats, s_out=o["s"][b0:b1], ss_out=o["ss"][b0:b1],
                                gc=(gc[0][b0:b1], gc[1][b0:b1]), x_ops=x_ops, plans=plans,
                                ss64_out=o["ss64"][b0:b1] if "ss64" in o else None)
@@ -1024,7 +1034,8 @@ class Net(nn.Module):
         def side_work():
             xop_ = None
             if not self._sc_f32(bt) and cast:
-                xop_ = tuple(None if ((s == 0 and bt.shared0) or (s == 1 and getattr(bt, "cached", None) is not None))
+                cached = _cached_sides(bt)          # no cast (and no SplineConv) for a cached side
+                xop_ = tuple(None if ((s == 0 and bt.shared0) or cached[s] is not None)
                              else ops.cast_bf16(bt.x[s]) for s in range(2))
                 if bt.shared0 and bt.B > 1:
                     # the probe's SplineConv once per forward, not once per chunk
@@ -1532,6 +1543,56 @@ class Net(nn.Module):
         from . import gallery
         return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
                                 shortlist=shortlist, coarse=coarse)
+
+    # Probe sets: a *probe set* is a GalleryIndex enrolled from the probe graphs (``enroll``), with its
+    # fp32 rows on the device (layout "f32" or "f32+bf16"), on the gallery's device, enrolled with the
+    # gallery's sc_mode and SplineConv weights; each of these is refused by name otherwise.  The three
+    # methods below take the refusals of ``identify`` (training mode, use_graphs, stale weights).
+    def match_pairs(self, probes, index, pairs, chunks=None):
+        """The exact forward over an explicit list of (probe number, entry number) pairs of a probe set
+        and a gallery index, both sides' operand rows gathered from the cached SplineConv rows (no
+        SplineConv, no cast) -> the dict ``run`` returns.  Every output equals
+        ``run(DeviceBatch.from_pairs([(probe_graph[q], gallery_graph[g]) for q, g in pairs]))`` bit for
+        bit; repeated probes and entries and any order are fine.  On a "bf16+host" gallery the distinct
+        entries' fp32 rows are fetched first (refused over ``gallery.FETCH_MAX_BYTES``)."""
+        from . import gallery
+        return gallery.match_pairs(self, probes, index, pairs, chunks=chunks)
+
+    def coarse_scores_many(self, probes, index, probe_select=None, select=None, coarse="fused"):
+        """``coarse_scores`` of every probe of a probe set at once -> (len(probe_select), len(select))
+        fp32 on the device; row q equals ``coarse_scores(probe_graph[q], index, select, coarse)`` bit for
+        bit.  The (probe, entry) pairs run through the coarse kernels' pair-list instantiations
+        (``ops.coarse_pairs``) in launches of at most ``gallery.COARSE_PAIRS_CHUNK`` pairs, so the
+        scratch is bounded whatever the two sets; the route is chosen per pair (``coarse``: as
+        ``coarse_scores``, the pair's larger side decides)."""
+        from . import gallery
+        return gallery.coarse_scores_many(self, probes, index, probe_select=probe_select, select=select, coarse=coarse)
+
+    def identify_many(self, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
+                      coarse="fused", chunks=None, group_pairs=1024, exclude_self=False):
+        """1:N identification of a whole probe set -> a list of dicts, one per probe of ``probe_select``
+        (default all), in that order.  ``coarse_scores_many``, ``ops.rank_select`` to the ``shortlist``
+        best entries per probe, one host copy of all shortlists, then the exact forward in *groups* of
+        probes (``gallery.probe_groups``: probes in stable ascending order of keypoint count, packed
+        while a group's pairs stay within ``group_pairs``; a group's pairs are probe-major, each
+        probe's entries in coarse-rank order), and ``ops.rank_topk`` per probe.  Without a shortlist
+        every probe meets every selected entry.
+
+        A probe's dict: its slice of its group's ``run`` outputs (padded to the group's box; scalars
+        such as the losses are the group's), ``top_idx`` / ``top_score``, with a shortlist ``short_idx``
+        / ``coarse_score`` / ``coarse_all`` as ``identify`` returns them, and ``group``: (group number,
+        first pair, one past the last pair) of the probe in its group's pair list.  A group's outputs
+        equal ``match_pairs`` over its pair list, hence the uncached ``run(from_pairs(...))``, bit for
+        bit; like any batch a pair's bits depend on its padded box, and where the box is the same they
+        equal the one-probe ``identify``'s.
+
+        ``exclude_self`` (only with ``probes is index``: de-duplicating a gallery): the pair (q, entry
+        q) is left out: its coarse score counts as -inf in the ranking (``coarse_all`` keeps it) and
+        the shortlist is clamped to len(select) - 1."""
+        from . import gallery
+        return gallery.identify_many(self, probes, index, topk=topk, shortlist=shortlist, probe_select=probe_select,
+                                     select=select, score=score, coarse=coarse, chunks=chunks,
+                                     group_pairs=group_pairs, exclude_self=exclude_self)
 
     def image_features(self, images, Ps, ns, dev=None):
         """ngm.py:226-248 on the device: per side, node_layers/edge_layers (ResNet-18 convolutions

@@ -3,7 +3,7 @@
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
 no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``,
-``coarse_score`` and ``rows_fetch`` alone keep a plain-torch host path for CPU tensors: the statements
+``coarse_score`` / ``coarse_pairs`` and ``rows_fetch`` alone keep a plain-torch host path for CPU tensors: the statements
 of the ordering, of the coarse score and of the ragged copy, which the tests hold the kernels to).
 """
 import ctypes
@@ -694,6 +694,112 @@ def coarse_score_stream(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None,
                   iters, tau, _p(out), _p(ws), wsb, _stream(y))
     return _coarse_score_op("coarse_score_stream", "COARSE_STREAM_NMAX", COARSE_STREAM_NMAX, launch, y, row_off, idx,
                             yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
+
+
+_COARSE_PAIRS_KERNELS = {"fused": ("fpm_coarse_pairs", "COARSE_NMAX", COARSE_NMAX),
+                         "wide": ("fpm_coarse_pairs_wide", "COARSE_WIDE_NMAX", COARSE_WIDE_NMAX),
+                         "stream": ("fpm_coarse_pairs_stream", "COARSE_STREAM_NMAX", COARSE_STREAM_NMAX)}
+
+
+def coarse_pairs(y, row_off, gidx, yq, qrow_off, qidx, coef, kernel="fused", iters=10, tau=0.01, out=None,
+                 gidx_host=None, qidx_host=None, row_off_host=None, qrow_off_host=None, dtype=None):
+    """The coarse score over a pair list (fpm_coarse_pairs, _wide, _stream) -> (B,) fp32: pair b scores
+    probe qidx[b] of the probe row store yq (sum n_q, 768) fp32 / qrow_off int64 [Q + 1] against entry
+    gidx[b] of the index rows y / row_off (fp32, or their bf16 copy: the _rows16 entry points) with
+    coef[b], by the definition of ``coarse_score``.  ``kernel``: "fused" (boxes up to COARSE_NMAX),
+    "wide" (COARSE_WIDE_NMAX) or "stream" (COARSE_STREAM_NMAX): the pair-list instantiation of that
+    kernel, so score[b] is the same bits as ``coarse_score`` / ``_wide`` / ``_stream`` give for that
+    probe, entry and coefficient row, whatever the order of the list and whatever else is in it.
+
+    Checked on the host before anything is launched: dtypes, contiguity and devices, both index lists
+    of one length and in range, every named n_q and n_g in [1, the kernel's bound], coef (B, 768)
+    (``*_host``: host copies, so the checks need no device synchronisation).  CPU tensors take the
+    plain-torch statement of ``coarse_score`` pair by pair, in ``dtype`` arithmetic."""
+    op = "coarse_pairs"
+    if kernel not in _COARSE_PAIRS_KERNELS:
+        raise _lib.FpmError("%s: kernel must be one of %s" % (op, tuple(_COARSE_PAIRS_KERNELS)))
+    sym, bound, nmax = _COARSE_PAIRS_KERNELS[kernel]
+    for name, t, dt in (("gidx", gidx, torch.int32), ("qidx", qidx, torch.int32), ("row_off", row_off, torch.int64),
+                        ("qrow_off", qrow_off, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise _lib.FpmError("%s: %s must be a %s tensor (got %s)"
+                                % (op, name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise _lib.FpmError("%s: %s must be a contiguous 1-d tensor" % (op, name))
+    if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.bfloat16) or y.dim() != 2 \
+            or y.shape[1] != 768 or not y.is_contiguous():
+        raise _lib.FpmError("%s: y must be contiguous fp32 or bf16 rows of 768 channels" % op)
+    for name, t in (("yq", yq), ("coef", coef)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
+                or not t.is_contiguous():
+            raise _lib.FpmError("%s: %s must be contiguous fp32 rows of 768 channels" % (op, name))
+    for name, t in (("row_off", row_off), ("gidx", gidx), ("yq", yq), ("qrow_off", qrow_off), ("qidx", qidx),
+                    ("coef", coef), ("out", out)):
+        if t is not None and t.device != y.device:
+            raise _lib.FpmError("%s: %s is on %s, y on %s" % (op, name, t.device, y.device))
+    G, Q, B = int(row_off.numel()) - 1, int(qrow_off.numel()) - 1, int(gidx.numel())
+    if G < 1 or Q < 1:
+        raise _lib.FpmError("%s: empty gallery or empty probe set" % op)
+    if int(qidx.numel()) != B:
+        raise _lib.FpmError("%s: gidx names %d pairs, qidx %d" % (op, B, int(qidx.numel())))
+    _shape(coef, (B, 768), "%s coef" % op)
+    host = lambda h, t: torch.as_tensor(h if h is not None else t.cpu()).view(-1).long()
+    gh, qh, oh, qoh = host(gidx_host, gidx), host(qidx_host, qidx), host(row_off_host, row_off), host(qrow_off_host,
+                                                                                                      qrow_off)
+    if gh.numel() != B or qh.numel() != B or oh.numel() != G + 1 or qoh.numel() != Q + 1:
+        raise _lib.FpmError("%s: host copies of gidx / qidx / row_off / qrow_off do not match the device tensors" % op)
+    for name, o, rows in (("row_off", oh, y), ("qrow_off", qoh, yq)):
+        if int(o[0]) != 0 or int(o[-1]) != rows.shape[0] or bool((o[1:] < o[:-1]).any()):
+            raise _lib.FpmError("%s: %s must rise from 0 to the %d rows of its store" % (op, name, rows.shape[0]))
+    nqmax = ngmax = 0
+    if B:
+        if int(gh.min()) < 0 or int(gh.max()) >= G:
+            raise _lib.FpmError("%s: gidx value outside [0, %d)" % (op, G))
+        if int(qh.min()) < 0 or int(qh.max()) >= Q:
+            raise _lib.FpmError("%s: qidx value outside [0, %d)" % (op, Q))
+        ng, nq = oh[gh + 1] - oh[gh], qoh[qh + 1] - qoh[qh]
+        nqmax, ngmax = int(nq.max()), int(ng.max())
+        for what, n in (("probe", nq), ("selected entry", ng)):
+            if int(n.max()) > nmax or int(n.min()) < 1:
+                raise _lib.FpmError("%s: a %s of %d keypoints; the %s coarse pass takes 1 to %s = %d"
+                                    % (op, what, int(n.max()) if int(n.max()) > nmax else int(n.min()), kernel, bound,
+                                       nmax))
+    iters, tau = int(iters), float(tau)
+    if iters < 0 or not tau > 0:
+        raise _lib.FpmError("%s: iters >= 0 and tau > 0 required" % op)
+    if not y.is_cuda:
+        dtype = dtype or torch.float32
+        if dtype not in (torch.float32, torch.float64):
+            raise _lib.FpmError("%s: the host statement runs in float32 or float64" % op)
+        res = torch.empty(B, dtype=dtype)
+        for b in range(B):
+            q = int(qh[b])
+            res[b:b + 1] = _coarse_score_host(y, oh, gh[b:b + 1], yq[int(qoh[q]):int(qoh[q + 1])], coef[b:b + 1], iters,
+                                              tau, dtype)
+        if out is not None:
+            _shape(out, (B,), "%s out" % op)
+            out.copy_(res)
+            return out
+        return res
+    if dtype is not None:
+        raise _lib.FpmError("%s: dtype selects the host statement's arithmetic; the kernel is fp32" % op)
+    if out is None:
+        out = torch.empty(B, device=y.device, dtype=torch.float32)
+    _shape(out, (B,), "%s out" % op)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.FpmError("%s: out must be contiguous fp32" % op)
+    if not B:
+        return out
+    args = (_p(y), _p(row_off), _p(gidx), G, B, _p(yq), _p(qrow_off), _p(qidx), Q, _p(coef), iters, tau, _p(out))
+    if kernel == "fused":
+        _lib.call(sym + _rows16(y), *args, _stream(y))
+        return out
+    # the stream kernel's slots: the largest probe and the largest entry of the launch, from whichever pairs
+    wsb = int(_lib.load().fpm_coarse_score_wide_ws_bytes(B) if kernel == "wide"
+              else _lib.load().fpm_coarse_score_stream_ws_bytes(B, nqmax, ngmax))
+    ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
+    _lib.call(sym + _rows16(y), *args, _p(ws), wsb, _stream(y))
+    return out
 
 
 def edge_diff(x, src, dst):

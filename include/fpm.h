@@ -605,6 +605,38 @@ int fpm_coarse_score_wide_rows16(const void* y16, const long* row_off, const int
 int fpm_coarse_score_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                    const float* yp, int n0, const float* coef, int iters, float tau, float* score,
                                    void* ws, long ws_bytes, void* stream);
+/* Pair lists (a probe set against a gallery): the six kernels above with the probe chosen per pair.
+ * yq holds the fp32 SplineConv rows of Q probe graphs, (sum n_q) x 768, graph q at rows
+ * [qrow_off[q], qrow_off[q + 1]) (qrow_off: Q + 1 int64, device); qidx: B int32 (device), the probe of
+ * each pair.  Pair b scores probe qidx[b] against entry idx[b] with coef[b]: the per-pair lookup (two
+ * scalar loads, as for idx) is the only code that differs from the one-probe kernel, a compile-time
+ * instantiation of it, so score[b] is the same bits as the one-probe entry point gives for that probe,
+ * entry and coefficient row, whatever else shares the launch and in whatever order.  The argument
+ * checks are the sibling's; the probe sizes are device data, so the entry point reads qrow_off and qidx
+ * back on the stream (one small copy and one wait per launch) and refuses a named probe outside the
+ * kernel's [1, NMAX] before anything is launched.  idx, qidx and n_g are the caller's to check: a pair
+ * with an index out of range or an entry outside the box reads no rows and gets NaN.  Workspaces:
+ * fpm_coarse_score_wide_ws_bytes(B); fpm_coarse_score_stream_ws_bytes(B, n0max, ngmax) with the
+ * largest named probe and the largest selected entry (they may belong to different pairs), at least
+ * ..._ws_bytes(B, n0max, 1). */
+int fpm_coarse_pairs(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
+                     const long* qrow_off, const int* qidx, int Q, const float* coef, int iters, float tau,
+                     float* score, void* stream);
+int fpm_coarse_pairs_wide(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
+                          const long* qrow_off, const int* qidx, int Q, const float* coef, int iters, float tau,
+                          float* score, void* ws, long ws_bytes, void* stream);
+int fpm_coarse_pairs_stream(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
+                            const long* qrow_off, const int* qidx, int Q, const float* coef, int iters, float tau,
+                            float* score, void* ws, long ws_bytes, void* stream);
+int fpm_coarse_pairs_rows16(const void* y16, const long* row_off, const int* idx, int G, int B, const float* yq,
+                            const long* qrow_off, const int* qidx, int Q, const float* coef, int iters, float tau,
+                            float* score, void* stream);
+int fpm_coarse_pairs_wide_rows16(const void* y16, const long* row_off, const int* idx, int G, int B, const float* yq,
+                                 const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
+                                 float tau, float* score, void* ws, long ws_bytes, void* stream);
+int fpm_coarse_pairs_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
+                                   const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
+                                   int iters, float tau, float* score, void* ws, long ws_bytes, void* stream);
 
 /* ---- profiling hooks: HIP-event timing of the dominant kernel (edge-message GEMM) ------------ */
 int fpm_profile_enable(int on);

@@ -11,6 +11,15 @@
                                                                        (-> profiles/identify_shortlist_stream.json)
     python tools/identify_bench.py --shortlist 64 --layout f32,f32+bf16,bf16+host [--coarse auto --n 256] [--append]
                                                                        (-> profiles/identify_compact.json)
+    python tools/identify_bench.py --probes 16 --shortlist 64 [--coarse auto --n 256 --large 0] [--append]
+                                                                       (-> profiles/identify_many.json)
+
+``--probes Q`` (with ``--shortlist M``): a probe set.  The looped ``identify(list of Q probes, shortlist=M)``
+(one probe at a time: the path before probe sets) against ``identify_many`` over the same enrolled gallery
+in one process; per probe the whole query, the coarse pass (``coarse_scores`` looped against
+``coarse_scores_many``) and the exact stage (Q forwards of M pairs against the grouped forwards of
+``identify_many``'s own pair lists), with the A/B verdict of each; and once the coarse pass with the pairs
+of a launch in entry-major order (an entry's probes on one XCD) against the default probe-major order.
 
 ``--shortlist M``: by the same protocol, the shortlisted query ``identify(shortlist=M)`` against the
 full ``identify`` in one process, at the C4 shape and at a larger gallery, with the coarse pass
@@ -334,6 +343,103 @@ def child_layouts(args):
     print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
 
 
+def _entry_major(p0, p1, Qs, Gs):
+    """``gallery._coarse_pairs_order``'s alternative: blocks of 8 entries x Qs probes, place r of a
+    block is (probe r // 8, entry r % 8), so that with one workgroup per pair and workgroups dealt to
+    the 8 XCDs in turn an entry's probes run on one XCD (its rows in that XCD's L2)."""
+    import torch
+    lin = torch.arange(p0, p1, dtype=torch.int64)
+    blk = torch.div(lin, 8 * Qs, rounding_mode="floor")
+    ne = torch.clamp(Gs - 8 * blk, max=8)
+    r = lin - blk * 8 * Qs
+    qi, gi = torch.div(r, ne, rounding_mode="floor"), 8 * blk + r % ne
+    return qi, gi, qi * Gs + gi
+
+
+def child_probes(args):
+    """``--probes Q --shortlist M``: looped identify against identify_many, in this one process."""
+    import torch
+    import bench
+    import fpm
+    from fpm import gallery as gal_mod
+    from fpm import params, synth
+    dev = torch.device("cuda", 0)
+    G, n, dtype, M, coarse, Q = args.gallery, args.n, args.child, args.shortlist, args.coarse, args.probes
+    probes = [synth.make_graph(args.seed, p, 0, n) for p in range(Q)]
+    base = bench.make_gallery(args.seed, 1, min(G, args.distinct), n, args.gen_workers)
+    gallery = [base[i % len(base)] for i in range(G)]      # past --distinct graphs the gallery repeats them
+    net = fpm.Net(regression=True, backbone=False, dtype=dtype)
+    net.load_state_dict(params.init_params(args.seed))
+    index = net.enroll(gallery, dev)
+    pset = net.enroll(probes, dev)
+    torch.cuda.synchronize()
+    del gallery, base
+    res = dict(dtype=dtype, gallery=G, distinct_graphs=min(G, args.distinct), n=n, probes=Q, shortlist=M,
+               sc_mode=index.sc_mode, reps=args.reps, coarse=coarse, group_pairs=args.group_pairs)
+    loop = net.identify(probes, index, topk=10, shortlist=M, coarse=coarse)
+    many = net.identify_many(pset, index, topk=10, shortlist=M, coarse=coarse, group_pairs=args.group_pairs)
+    torch.cuda.synchronize()
+    bits = lambda t: t.contiguous().view(torch.int32)
+    res["same_shortlists"] = all(bool(torch.equal(a["short_idx"], b["short_idx"])) for a, b in zip(loop, many))
+    res["same_coarse_bits"] = all(bool(torch.equal(bits(a["coarse_all"]), bits(b["coarse_all"])))
+                                  for a, b in zip(loop, many))
+    res["same_top10"] = sum(a["top_idx"].tolist() == b["top_idx"].tolist() for a, b in zip(loop, many))
+    short = [a["short_idx"].cpu().long() for a in loop]
+    groups = gal_mod.probe_groups(pset.n, M, args.group_pairs)
+    res["groups"] = [len(g) for g in groups]
+    lists = [torch.stack([torch.tensor(g).view(-1, 1).expand(-1, short[0].numel()).reshape(-1),
+                          torch.cat([short[i] for i in g])], 1) for g in groups]
+    del loop, many
+
+    def series(fn):
+        # one warm-up of this very call, then the timed runs; per probe
+        fn()
+        torch.cuda.synchronize()
+        r = _ev(_timed(fn, args.reps))
+        r["per_probe_ms"] = "%.3f (%.3f - %.3f)" % (r["median_ms"] / Q, r["min_ms"] / Q, r["max_ms"] / Q)
+        return r
+
+    def exact_loop():
+        for p, s_ in zip(probes, short):
+            net.identify(p, index, topk=10, select=s_)
+
+    def exact_many():
+        for pairs in lists:
+            gal_mod._run_pairs(net, pset, index, pairs, None)
+    parts = dict(
+        query=(lambda: net.identify(probes, index, topk=10, shortlist=M, coarse=coarse),
+               lambda: net.identify_many(pset, index, topk=10, shortlist=M, coarse=coarse,
+                                         group_pairs=args.group_pairs)),
+        coarse_pass=(lambda: net.coarse_scores(probes, index, coarse=coarse),
+                     lambda: net.coarse_scores_many(pset, index, coarse=coarse)),
+        exact_stage=(exact_loop, exact_many))
+
+    def verdict(o, c):
+        # the project's A/B rule: the candidate's median against the baseline's best run less its spread
+        faster = o["min_ms"] - (o["max_ms"] - o["min_ms"]) - c["median_ms"]
+        slower = c["min_ms"] - (c["max_ms"] - c["min_ms"]) - o["median_ms"]
+        return dict(speedup_median=round(o["median_ms"] / c["median_ms"], 3), faster_margin_ms=round(faster, 3),
+                    slower_margin_ms=round(slower, 3),
+                    verdict="faster" if faster > 0 else "slower" if slower > 0 else "within spread")
+    for name, (old, new) in parts.items():
+        o, c = series(old), series(new)
+        res[name] = dict(looped=o, many=c, ab=verdict(o, c))
+    # the one kernel-side A/B: the pair order within a coarse launch
+    ref = net.coarse_scores_many(pset, index, coarse=coarse)
+    keep = gal_mod._coarse_pairs_order
+    gal_mod._coarse_pairs_order = _entry_major
+    try:
+        alt = net.coarse_scores_many(pset, index, coarse=coarse)
+        res["pair_order_same_bits"] = bool(torch.equal(bits(alt), bits(ref)))
+        em = series(lambda: net.coarse_scores_many(pset, index, coarse=coarse))
+    finally:
+        gal_mod._coarse_pairs_order = keep
+    pm = series(lambda: net.coarse_scores_many(pset, index, coarse=coarse))
+    res["pair_order"] = dict(probe_major=pm, entry_major=em, ab=verdict(pm, em),
+                             note="entry-major also scatters its scores back (one indexed copy per launch)")
+    print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
+
+
 def main_shortlist(ap, args):
     lines = []
     shapes = [(args.gallery, dt) for dt in args.dtypes.split(",")]
@@ -343,7 +449,7 @@ def main_shortlist(ap, args):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", dtype, "--gallery", str(G), "--n", str(args.n),
                "--reps", str(args.reps), "--seed", str(args.seed), "--gen-workers", str(args.gen_workers),
                "--shortlist", str(args.shortlist), "--distinct", str(args.distinct), "--coarse", args.coarse,
-               "--layout", args.layout]
+               "--layout", args.layout, "--probes", str(args.probes), "--group-pairs", str(args.group_pairs)]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
         except subprocess.TimeoutExpired:
@@ -358,13 +464,20 @@ def main_shortlist(ap, args):
             "auto": "identify_shortlist_wide.json"}.get(args.coarse, "identify_shortlist_stream.json")
     if args.layout != "f32":
         name = "identify_compact.json"
+    if args.probes:
+        name = "identify_many.json"
     out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", name)
-    doc = dict(tool="tools/identify_bench.py --shortlist %d%s%s" % (args.shortlist, "" if args.coarse == "fused" else
+    doc = dict(tool="tools/identify_bench.py%s --shortlist %d%s%s" % (" --probes %d" % args.probes if args.probes else "",
+                                                                      args.shortlist, "" if args.coarse == "fused" else
                                                                     " --coarse %s --n %d" % (args.coarse, args.n),
                                                                     "" if args.layout == "f32" else
                                                                     " --layout %s" % args.layout),
                config="1 probe x gallery, n keypoints per graph; full = identify over every entry (the path before "
-                      "the shortlist existed), shortlisted = coarse pass + rank_select + identify over the M entries",
+                      "the shortlist existed), shortlisted = coarse pass + rank_select + identify over the M entries"
+                      if not args.probes else
+                      "%d probes x gallery, n keypoints per graph; looped = identify(list, shortlist=M), one probe at a "
+                      "time; many = identify_many over the enrolled probe set; ms are per call, per_probe_ms per probe"
+                      % args.probes,
                method="1 warm-up, `reps` queries each, HIP events around each query, median and min-max; both sides "
                       "in one process; a fresh process per shape",
                results=lines)
@@ -392,6 +505,10 @@ def main():
                          "the default 'f32' enrols the gallery once per layout in one process and records per layout "
                          "the bytes held, the coarse pass, the fetch, the M-pair forward and the whole shortlisted "
                          "query, the first layout the A/B baseline (profiles/identify_compact.json)")
+    ap.add_argument("--probes", type=int, default=0,
+                    help="--shortlist: Q > 0 probes: the looped identify against identify_many "
+                         "(profiles/identify_many.json)")
+    ap.add_argument("--group-pairs", type=int, default=1024, help="--probes: identify_many's group_pairs")
     ap.add_argument("--append", action="store_true",
                     help="--shortlist: add the results to those the output file already holds (another --n)")
     ap.add_argument("--large", type=int, default=16384, help="--shortlist: a second, larger gallery (0: none)")
@@ -409,7 +526,11 @@ def main():
     args = ap.parse_args()
     if args.reps < 5:
         ap.error("--reps must be at least 5")
+    if args.probes and not args.shortlist > 0:
+        ap.error("--probes goes with --shortlist M")
     if args.child:
+        if args.probes:
+            return child_probes(args)
         if args.shortlist > 0 and args.layout != "f32":
             return child_layouts(args)
         return child_shortlist(args) if args.shortlist > 0 else child(args)
