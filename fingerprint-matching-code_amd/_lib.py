@@ -48,20 +48,8 @@ SIGNATURES = {
     "fpm_rank_topk": (I, [P, L, I, I, I, P, P, P]),
     "fpm_rank_select_ws_bytes": (L, [I]),
     "fpm_rank_select": (I, [P, L, I, I, I, P, P, P, L, P]),
-    "fpm_coarse_score": (I, [P, P, P, I, I, P, I, P, I, F, P, P]),
     "fpm_coarse_score_wide_ws_bytes": (L, [I]),
-    "fpm_coarse_score_wide": (I, [P, P, P, I, I, P, I, P, I, F, P, P, L, P]),
     "fpm_coarse_score_stream_ws_bytes": (L, [I, I, I]),
-    "fpm_coarse_score_stream": (I, [P, P, P, I, I, P, I, P, I, F, P, P, L, P]),
-    "fpm_coarse_score_rows16": (I, [P, P, P, I, I, P, I, P, I, F, P, P]),
-    "fpm_coarse_score_wide_rows16": (I, [P, P, P, I, I, P, I, P, I, F, P, P, L, P]),
-    "fpm_coarse_score_stream_rows16": (I, [P, P, P, I, I, P, I, P, I, F, P, P, L, P]),
-    "fpm_coarse_pairs": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P]),
-    "fpm_coarse_pairs_wide": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P, L, P]),
-    "fpm_coarse_pairs_stream": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P, L, P]),
-    "fpm_coarse_pairs_rows16": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P]),
-    "fpm_coarse_pairs_wide_rows16": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P, L, P]),
-    "fpm_coarse_pairs_stream_rows16": (I, [P, P, P, I, I, P, P, P, I, P, I, F, P, P, L, P]),
     "fpm_rows_fetch": (I, [P, L, P, P, I, I, I, P, L, P, P]),
     "fpm_edge_diff_padded":(I, [P, P, P, P, P, P, L, I, P, P]),
     "fpm_kron_gnn_layer_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
@@ -138,6 +126,15 @@ SIGNATURES = {
     "fpm_profile_read": (I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                              ctypes.POINTER(I)]),
 }
+
+# The coarse kernels' entry points (fpm_coarse_{score,pairs}[_wide|_stream][_rows16]): one probe (yp, n0) or
+# a pair list (yq, qrow_off, qidx, Q) after (y, row_off, idx, G, B), then (coef, iters, tau, score), the
+# wide and streamed kernels' (ws, ws_bytes), and the stream.
+for _op, _probe in (("score", [P, I]), ("pairs", [P, P, P, I])):
+    for _kernel, _ws in (("", []), ("_wide", [P, L]), ("_stream", [P, L])):
+        for _rows in ("", "_rows16"):
+            SIGNATURES["fpm_coarse_%s%s%s" % (_op, _kernel, _rows)] = (
+                I, [P, P, P, I, I] + _probe + [P, I, F, P] + _ws + [P])
 
 _lib = None
 

@@ -99,21 +99,26 @@ class DeviceBatch:
             raise ValueError("split_range() needs per-pair edge offsets")
         if not 0 <= b0 < b1 <= self.B:
             raise ValueError("split_range: bad pair range [%d, %d) of %d" % (b0, b1, self.B))
-        xs, ws, ss, ds, ps = [], [], [], [], []
+        ws, ss, ds, ps = [], [], [], []
         for side in range(2):
             nm = self.nmax[side]
             e0, e1 = int(self.edge_off[side][b0]), int(self.edge_off[side][b1])
-            xs.append(self.x[side][b0 * nm:b1 * nm])
             ws.append(self.w[side][b0:b1])
             ss.append((self.src[side][e0:e1] - b0 * nm).contiguous())
             ds.append((self.dst[side][e0:e1] - b0 * nm).contiguous())
             ps.append(self.pseudo[side][e0:e1])
         eo = [self.edge_off[side][b0:b1 + 1] - self.edge_off[side][b0] for side in range(2)]
-        sub = DeviceBatch(b1 - b0, self.n_host[0][b0:b1], self.n_host[1][b0:b1], xs, ws, ss, ds, ps, self.device,
-                          nmax=self.nmax, edge_off=eo, shared0=self.shared0)
+        sub = type(self)(b1 - b0, self.n_host[0][b0:b1], self.n_host[1][b0:b1], None, ws, ss, ds, ps, self.device,
+                         nmax=self.nmax, edge_off=eo, shared0=self.shared0)
         sub.pair_range = (b0, b1)
         sub.ord2 = None if self.ord2 is None else self.ord2[b0:b1]
+        self._carry(sub, b0, b1)
         return sub
+
+    def _carry(self, sub, b0, b1):
+        """``split_range``'s one step a subclass replaces: the node features of pairs [b0, b1) onto
+        ``sub`` (here views of the padded rows), and whatever else the sub-batch keeps of this batch."""
+        sub.x = [self.x[side][b0 * self.nmax[side]:b1 * self.nmax[side]] for side in range(2)]
 
     def to(self, device, non_blocking=True):
         """The same batch on another device (peer copies of features, edges and counts); keeps the

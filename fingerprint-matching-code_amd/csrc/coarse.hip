@@ -34,6 +34,7 @@
 // between workgroups.  LDS: 68.6 KB per workgroup, two workgroups per CU.
 #include "fpm_common.h"
 #include "coarse_probe.h"
+#include "coarse_tile.h"
 #include "fpm.h"
 
 namespace {
@@ -48,53 +49,9 @@ constexpr int S_FLOATS = (CN + 1) * SLD; // rows 0..127 and the dummy row 128
 constexpr int LDS_FLOATS = S_FLOATS + 4 * CN + 4;
 static_assert(2 * CTILE <= S_FLOATS * 4, "the operand tiles share L's space");
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, fpm::dpp_f<0xB1>(v));
-    v = fmaxf(v, fpm::dpp_f<0x4E>(v));
-    v = fmaxf(v, fpm::dpp_f<0x141>(v));
-    return fmaxf(v, fpm::dpp_f<0x140>(v));
-}
-
-// one side's K tile: this thread's 8 float4 (rows (tid >> 4) + 16 m, columns 4 (tid & 15) ..)
-__device__ __forceinline__ void tile_load(const float* __restrict__ base, int n, int k0, int tid, float4 (&r)[8]) {
-    const int row0 = tid >> 4, c = 4 * (tid & 15);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        const int row = row0 + 16 * m;
-        r[m] = row < n ? *(const float4*)(base + (long)row * CK + k0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-// scale (one fp32 multiply; the unscaled side multiplies by 1, exactly), round to bf16, into LDS
-__device__ __forceinline__ void tile_store(unsigned char* tile, int tid, const float4 (&r)[8], float4 s) {
-    const int row0 = tid >> 4, c = 4 * (tid & 15);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        uint2 o;
-        o.x = fpm::f2bf2(__fmul_rn(r[m].x, s.x), __fmul_rn(r[m].y, s.y));
-        o.y = fpm::f2bf2(__fmul_rn(r[m].z, s.z), __fmul_rn(r[m].w, s.w));
-        *(uint2*)(tile + (row0 + 16 * m) * CROW + c * 2) = o;
-    }
-}
-
-// the entry's K tile from bf16 rows: this thread's 4 vectors of 8 bf16 (rows (tid >> 3) + 32 m,
-// columns 8 (tid & 7) ..; a row is 1536 B, so every vector is 16-B aligned), zeros past n
-__device__ __forceinline__ void tile_load16(const bf16_t* __restrict__ base, int n, int k0, int tid, uint4 (&r)[4]) {
-    const int row0 = tid >> 3, c = 8 * (tid & 7);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int row = row0 + 32 * m;
-        r[m] = row < n ? *(const uint4*)(base + (long)row * CK + k0 + c) : make_uint4(0u, 0u, 0u, 0u);
-    }
-}
-// as they are into the tile_store layout
-__device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const uint4 (&r)[4]) {
-    const int row0 = tid >> 3, c = 8 * (tid & 7);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) *(uint4*)(tile + (row0 + 32 * m) * CROW + c * 2) = r[m];
-}
+using namespace fpm::coarse;
+// a K tile: 8 float4 (128 rows) or 4 vectors of 8 bf16 per thread (coarse_tile.h)
+using KTile = Tile<CT, CBK, CROW>;
 
 // YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment).
 // PAIRS: the probe of pair b comes from a second row store (a pair list: coarse_probe.h); the lookup
@@ -166,30 +123,30 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     float4 ra[8], rb[8], sc;
     uint4 re[4];
     if constexpr (F32) {
-        tile_load(xa, R, 0, tid, ra);
-        tile_load(xb, C, 0, tid, rb);
+        KTile::load(xa, R, 0, 0, tid, ra);
+        KTile::load(xb, C, 0, 0, tid, rb);
     } else {
-        tile_load(yp, n0, 0, tid, ra);
-        tile_load16(ye, ng, 0, tid, re);
+        KTile::load(yp, n0, 0, 0, tid, ra);
+        KTile::load16(ye, ng, 0, 0, tid, re);
     }
     sc = *(const float4*)(cf + c4);
     const int fr = lane & 15, fq = lane >> 4;
     for (int kt = 0; kt < CK / CBK; ++kt) {
         if constexpr (F32) {
-            tile_store(At, tid, ra, tr ? one : sc);
-            tile_store(Bt, tid, rb, tr ? sc : one);
+            KTile::store(At, tid, ra, tr ? one : sc);
+            KTile::store(Bt, tid, rb, tr ? sc : one);
         } else {
-            tile_store(Pt, tid, ra, sc);
-            tile_store16(Et, tid, re);
+            KTile::store(Pt, tid, ra, sc);
+            KTile::store16(Et, tid, re);
         }
         __syncthreads();
         if (kt + 1 < CK / CBK) {
             if constexpr (F32) {
-                tile_load(xa, R, (kt + 1) * CBK, tid, ra);
-                tile_load(xb, C, (kt + 1) * CBK, tid, rb);
+                KTile::load(xa, R, 0, (kt + 1) * CBK, tid, ra);
+                KTile::load(xb, C, 0, (kt + 1) * CBK, tid, rb);
             } else {
-                tile_load(yp, n0, (kt + 1) * CBK, tid, ra);
-                tile_load16(ye, ng, (kt + 1) * CBK, tid, re);
+                KTile::load(yp, n0, 0, (kt + 1) * CBK, tid, ra);
+                KTile::load16(ye, ng, 0, (kt + 1) * CBK, tid, re);
             }
             sc = *(const float4*)(cf + (kt + 1) * CBK + c4);
         }
@@ -346,76 +303,51 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 }  // namespace
 
 namespace {
-template <typename YT, bool PAIRS>
-int coarse_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                  const float* ypq, int n0q, const long* qrow_off, const int* qidx, const float* coef, int iters,
-                  float tau, float* score, void* stream) {
-    constexpr int lds = LDS_FLOATS * (int)sizeof(float);
-    if (hipFuncSetAttribute((const void*)coarse_score_kernel<YT, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            lds) != hipSuccess) {
-        (void)hipGetLastError();
-        fpm::set_error("coarse_score: %d bytes of LDS per workgroup refused", lds);
-        return 1;
+// the traits of fpm::coarse_score_entry / coarse_pairs_entry (coarse_probe.h); no workspace
+struct Fused {
+    static constexpr const char *score_op = "coarse_score", *pairs_op = "coarse_pairs", *bound = "COARSE_NMAX";
+    static constexpr int nmax = FPM_COARSE_NMAX;
+    template <typename YT, bool PAIRS>
+    static int launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B, const float* ypq,
+                      int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
+                      float* score, void* ws, long ws_bytes, void* stream) {
+        constexpr int lds = LDS_FLOATS * (int)sizeof(float);
+        if (hipFuncSetAttribute((const void*)coarse_score_kernel<YT, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                lds) != hipSuccess) {
+            (void)hipGetLastError();
+            fpm::set_error("coarse_score: %d bytes of LDS per workgroup refused", lds);
+            return 1;
+        }
+        hipLaunchKernelGGL((coarse_score_kernel<YT, PAIRS>), dim3((unsigned)B), dim3(CT), lds, (hipStream_t)stream, y,
+                           row_off, idx, G, ypq, n0q, coef, iters, tau, score, qrow_off, qidx);
+        return fpm::check_launch(what);
     }
-    hipLaunchKernelGGL((coarse_score_kernel<YT, PAIRS>), dim3((unsigned)B), dim3(CT), lds, (hipStream_t)stream, y, row_off,
-                       idx, G, ypq, n0q, coef, iters, tau, score, qrow_off, qidx);
-    return fpm::check_launch(what);
-}
-
-template <typename YT>
-int coarse_score_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                        const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* stream) {
-    FPM_CHECK_ARG(G > 0 && B >= 0, "coarse_score: bad sizes (G %d, B %d)", G, B);
-    FPM_CHECK_ARG(n0 >= 1 && n0 <= FPM_COARSE_NMAX, "coarse_score: probe of %d keypoints outside [1, COARSE_NMAX = %d]",
-                  n0, FPM_COARSE_NMAX);
-    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_score: iters >= 0 and tau > 0 required");
-    FPM_CHECK_ARG(y && row_off && idx && yp && coef && score,
-                  "coarse_score: y, row_off, idx, yp, coef and score are required");
-    if (B == 0) return 0;
-    return coarse_launch<YT, false>(what, y, row_off, idx, G, B, yp, n0, nullptr, nullptr, coef, iters, tau, score, stream);
-}
-
-// the pair list: the one-probe refusals, the probe sizes read back from the device (coarse_probe.h)
-template <typename YT>
-int coarse_pairs_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                        const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
-                        float tau, float* score, void* stream) {
-    FPM_CHECK_ARG(G > 0 && Q > 0 && B >= 0, "coarse_pairs: bad sizes (G %d, Q %d, B %d)", G, Q, B);
-    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_pairs: iters >= 0 and tau > 0 required");
-    FPM_CHECK_ARG(y && row_off && idx && yq && qrow_off && qidx && coef && score,
-                  "coarse_pairs: y, row_off, idx, yq, qrow_off, qidx, coef and score are required");
-    if (B == 0) return 0;
-    long lo, hi;
-    if (fpm::coarse_pairs_probe_range(qrow_off, qidx, Q, B, stream, lo, hi)) return 1;
-    FPM_CHECK_ARG(lo >= 1 && hi <= FPM_COARSE_NMAX, "coarse_pairs: probe of %ld keypoints outside [1, COARSE_NMAX = %d]",
-                  hi > FPM_COARSE_NMAX ? hi : lo, FPM_COARSE_NMAX);
-    return coarse_launch<YT, true>(what, y, row_off, idx, G, B, yq, Q, qrow_off, qidx, coef, iters, tau, score, stream);
-}
+};
 }  // namespace
 
 extern "C" int fpm_coarse_score(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp,
                                 int n0, const float* coef, int iters, float tau, float* score, void* stream) {
-    return coarse_score_launch<float>("fpm_coarse_score", y, row_off, idx, G, B, yp, n0, coef, iters, tau, score,
-                                      stream);
+    return fpm::coarse_score_entry<Fused>("fpm_coarse_score", y, row_off, idx, G, B, yp, n0, coef, iters, tau, score,
+                                          nullptr, 0, stream);
 }
 
 extern "C" int fpm_coarse_score_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                        const float* yp, int n0, const float* coef, int iters, float tau, float* score,
                                        void* stream) {
-    return coarse_score_launch<bf16_t>("fpm_coarse_score_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0, coef,
-                                       iters, tau, score, stream);
+    return fpm::coarse_score_entry<Fused>("fpm_coarse_score_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0,
+                                          coef, iters, tau, score, nullptr, 0, stream);
 }
 
 extern "C" int fpm_coarse_pairs(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
                                 const long* qrow_off, const int* qidx, int Q, const float* coef, int iters, float tau,
                                 float* score, void* stream) {
-    return coarse_pairs_launch<float>("fpm_coarse_pairs", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef, iters, tau,
-                                      score, stream);
+    return fpm::coarse_pairs_entry<Fused>("fpm_coarse_pairs", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef, iters,
+                                          tau, score, nullptr, 0, stream);
 }
 
 extern "C" int fpm_coarse_pairs_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                        const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
                                        int iters, float tau, float* score, void* stream) {
-    return coarse_pairs_launch<bf16_t>("fpm_coarse_pairs_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq, qrow_off,
-                                       qidx, Q, coef, iters, tau, score, stream);
+    return fpm::coarse_pairs_entry<Fused>("fpm_coarse_pairs_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
+                                          qrow_off, qidx, Q, coef, iters, tau, score, nullptr, 0, stream);
 }

@@ -38,6 +38,7 @@
 // workgroup computes it and however large the slots are.  LDS: 134.0 KB per workgroup.
 #include "fpm_common.h"
 #include "coarse_probe.h"
+#include "coarse_tile.h"
 #include "fpm.h"
 
 namespace {
@@ -58,67 +59,15 @@ constexpr int SLDS = 2 * SBUF + RED_FLOATS * 4;
 constexpr int RW = 4;                        // rows in flight per wave in a row step
 constexpr int CU = 8;                        // rows in flight per thread in a column step
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// softplus = max(x, 0) + log1p(exp(-|x|)) on the native base-2 transcendentals, with log1p's classic
-// correction for the rounding of 1 + t (coarse_wide.hip's, measured there against float64)
-__device__ __forceinline__ float softplus_native(float x) {
-    const float t = fpm::fast_exp2(-fabsf(x) * fpm::LOG2E_F);
-    const float u = 1.f + t;
-    const float c = (t - (u - 1.f)) * __builtin_amdgcn_rcpf(u);
-    return fmaxf(x, 0.f) + (fpm::fast_log2(u) * fpm::LN2_F + c);
-}
-// a finite stand-in for the maximum of an all -inf set (exp2(-inf - 0) = 0: an empty sum)
-__device__ __forceinline__ float finite_max(float m) { return m == -INFINITY ? 0.f : m; }
+using namespace fpm::coarse;
+// a K tile: 4 (entry, 128 rows) or 8 (probe, 256 rows) float4, or 2 vectors of 8 bf16, per thread
+// (coarse_tile.h)
+using KTile = Tile<ST, SBK, SROW>;
 
 // L_ij from Kp_ij: every rounding spelled out (no contraction), so every reader rebuilds the same
 // bits: L1 = fl(fl(Kp s) - r1) is the in-place first step's value, then the two potentials
 __device__ __forceinline__ float lval(float kp, float s, float r1, float u, float v) {
     return __fsub_rn(__fsub_rn(__fsub_rn(__fmul_rn(kp, s), r1), u), v);
-}
-
-// one side's K tile: NM float4 per thread (rows row_base + (tid >> 4) + 32 m, columns 4 (tid & 15) ..)
-template <int NM>
-__device__ __forceinline__ void tile_load(const float* __restrict__ base, int n, int row_base, int k0, int tid,
-                                          float4 (&r)[NM]) {
-    const int row0 = row_base + (tid >> 4), c = 4 * (tid & 15);
-#pragma unroll
-    for (int m = 0; m < NM; ++m) {
-        const int row = row0 + 32 * m;
-        r[m] = row < n ? *(const float4*)(base + (long)row * SK + k0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-// scale (one fp32 multiply; the unscaled side multiplies by 1, exactly), round to bf16, into LDS
-template <int NM>
-__device__ __forceinline__ void tile_store(unsigned char* tile, int tid, const float4 (&r)[NM], float4 s) {
-    const int row0 = tid >> 4, c = 4 * (tid & 15);
-#pragma unroll
-    for (int m = 0; m < NM; ++m) {
-        uint2 o;
-        o.x = fpm::f2bf2(__fmul_rn(r[m].x, s.x), __fmul_rn(r[m].y, s.y));
-        o.y = fpm::f2bf2(__fmul_rn(r[m].z, s.z), __fmul_rn(r[m].w, s.w));
-        *(uint2*)(tile + (row0 + 32 * m) * SROW + c * 2) = o;
-    }
-}
-// the entry's K tile from bf16 rows (fpm_coarse_score_stream_rows16: an index that keeps a bf16 copy
-// of its rows, the same RNE rounding done once at enrolment): this thread's 2 vectors of 8 bf16 (rows
-// row_base + (tid >> 3) + 64 m, columns 8 (tid & 7) ..; a row is 1536 B, so every vector is 16-B
-// aligned), zeros past n
-__device__ __forceinline__ void tile_load16(const bf16_t* __restrict__ base, int n, int row_base, int k0, int tid,
-                                            uint4 (&r)[2]) {
-    const int row0 = row_base + (tid >> 3), c = 8 * (tid & 7);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int row = row0 + 64 * m;
-        r[m] = row < n ? *(const uint4*)(base + (long)row * SK + k0 + c) : make_uint4(0u, 0u, 0u, 0u);
-    }
-}
-// as they are into the tile_store layout: no multiply, no convert
-__device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const uint4 (&r)[2]) {
-    const int row0 = tid >> 3, c = 8 * (tid & 7);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) *(uint4*)(tile + (row0 + 64 * m) * SROW + c * 2) = r[m];
 }
 
 // YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment); the
@@ -189,23 +138,23 @@ __global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const YT* __res
                 const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
                 float4 ra[4], rb[8], s4;
                 uint4 re[2];                             // bf16 entry rows, in ra's place
-                if constexpr (F32) tile_load<4>(xe, ng, te, 0, tid, ra);
-                else tile_load16(xe, ng, te, 0, tid, re);
-                tile_load<8>(yp, n0, tp, 0, tid, rb);
+                if constexpr (F32) KTile::load(xe, ng, te, 0, tid, ra);
+                else KTile::load16(xe, ng, te, 0, tid, re);
+                KTile::load(yp, n0, tp, 0, tid, rb);
                 s4 = *(const float4*)(cf + c4);
                 for (int kt = 0; kt < SK / SBK; ++kt) {
                     unsigned char* At = slds + (kt & 1) * SBUF;
                     unsigned char* Bt = At + ATILE;
-                    if constexpr (F32) tile_store<4>(At, tid, ra, one);
-                    else tile_store16(At, tid, re);
-                    tile_store<8>(Bt, tid, rb, s4);
+                    if constexpr (F32) KTile::store(At, tid, ra, one);
+                    else KTile::store16(At, tid, re);
+                    KTile::store(Bt, tid, rb, s4);
                     // one barrier per K tile: the other buffer was last read before the previous barrier
                     // (12 K tiles, an even count: the parity carries over from one block tile to the next)
                     __syncthreads();
                     if (kt + 1 < SK / SBK) {
-                        if constexpr (F32) tile_load<4>(xe, ng, te, (kt + 1) * SBK, tid, ra);
-                        else tile_load16(xe, ng, te, (kt + 1) * SBK, tid, re);
-                        tile_load<8>(yp, n0, tp, (kt + 1) * SBK, tid, rb);
+                        if constexpr (F32) KTile::load(xe, ng, te, (kt + 1) * SBK, tid, ra);
+                        else KTile::load16(xe, ng, te, (kt + 1) * SBK, tid, re);
+                        KTile::load(yp, n0, tp, (kt + 1) * SBK, tid, rb);
                         s4 = *(const float4*)(cf + (kt + 1) * SBK + c4);
                     }
 #pragma unroll
@@ -452,94 +401,65 @@ extern "C" long fpm_coarse_score_stream_ws_bytes(int B, int n0, int ngmax) {
 }
 
 namespace {
-// the slots are as large as the workspace allows; ``need``: the smallest that serves any pair at all
-template <typename YT, bool PAIRS>
-int coarse_stream_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                         const float* ypq, int n0q, const long* qrow_off, const int* qidx, long need, const float* coef,
-                         int iters, float tau, float* score, void* ws, long ws_bytes, void* stream) {
-    const int grid = B < SGRID ? B : SGRID;
-    const long slot_floats = ws_bytes > 0 ? (ws_bytes / (long)sizeof(float) / grid) & ~3L : 0;
-    FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
-                  "coarse_score_stream: workspace of at least %ld bytes (16-byte aligned; "
-                  "fpm_coarse_score_stream_ws_bytes) required, got %ld",
-                  need, ws_bytes);
-    if (hipFuncSetAttribute((const void*)coarse_score_stream_kernel<YT, PAIRS>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, SLDS) != hipSuccess) {
-        (void)hipGetLastError();
-        fpm::set_error("coarse_score_stream: %d bytes of LDS per workgroup refused", SLDS);
-        return 1;
+// the traits of fpm::coarse_score_entry / coarse_pairs_entry (coarse_probe.h).  The slots are as large as
+// the workspace allows; ``need`` is the smallest that serves any pair at all: the largest probe of the
+// launch against an entry of one keypoint.  The caller sizes them from the largest probe and the largest
+// entry (fpm_coarse_score_stream_ws_bytes(B, n0max, ngmax)); a pair whose block does not fit its slot gets
+// NaN
+struct Stream {
+    static constexpr const char *score_op = "coarse_score_stream", *pairs_op = "coarse_pairs_stream",
+                                *bound = "COARSE_STREAM_NMAX";
+    static constexpr int nmax = FPM_COARSE_STREAM_NMAX;
+    template <typename YT, bool PAIRS>
+    static int launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B, const float* ypq,
+                      int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
+                      float* score, void* ws, long ws_bytes, void* stream) {
+        const int grid = B < SGRID ? B : SGRID;
+        const long need = fpm_coarse_score_stream_ws_bytes(B, n0max, 1);
+        const long slot_floats = ws_bytes > 0 ? (ws_bytes / (long)sizeof(float) / grid) & ~3L : 0;
+        FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
+                      "coarse_score_stream: workspace of at least %ld bytes (16-byte aligned; "
+                      "fpm_coarse_score_stream_ws_bytes) required, got %ld",
+                      need, ws_bytes);
+        if (hipFuncSetAttribute((const void*)coarse_score_stream_kernel<YT, PAIRS>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, SLDS) != hipSuccess) {
+            (void)hipGetLastError();
+            fpm::set_error("coarse_score_stream: %d bytes of LDS per workgroup refused", SLDS);
+            return 1;
+        }
+        hipLaunchKernelGGL((coarse_score_stream_kernel<YT, PAIRS>), dim3((unsigned)grid), dim3(ST), SLDS,
+                           (hipStream_t)stream, y, row_off, idx, G, B, ypq, n0q, coef, iters, tau, score, (float*)ws,
+                           slot_floats, qrow_off, qidx);
+        return fpm::check_launch(what);
     }
-    hipLaunchKernelGGL((coarse_score_stream_kernel<YT, PAIRS>), dim3((unsigned)grid), dim3(ST), SLDS, (hipStream_t)stream,
-                       y, row_off, idx, G, B, ypq, n0q, coef, iters, tau, score, (float*)ws, slot_floats, qrow_off, qidx);
-    return fpm::check_launch(what);
-}
-
-template <typename YT>
-int coarse_score_stream_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                               const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* ws,
-                               long ws_bytes, void* stream) {
-    FPM_CHECK_ARG(G > 0 && B >= 0, "coarse_score_stream: bad sizes (G %d, B %d)", G, B);
-    FPM_CHECK_ARG(n0 >= 1 && n0 <= FPM_COARSE_STREAM_NMAX,
-                  "coarse_score_stream: probe of %d keypoints outside [1, COARSE_STREAM_NMAX = %d]", n0,
-                  FPM_COARSE_STREAM_NMAX);
-    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_score_stream: iters >= 0 and tau > 0 required");
-    FPM_CHECK_ARG(y && row_off && idx && yp && coef && score,
-                  "coarse_score_stream: y, row_off, idx, yp, coef and score are required");
-    if (B == 0) return 0;
-    // the smallest workspace that serves any entry is ngmax = 1
-    return coarse_stream_launch<YT, false>(what, y, row_off, idx, G, B, yp, n0, nullptr, nullptr,
-                                           fpm_coarse_score_stream_ws_bytes(B, n0, 1), coef, iters, tau, score, ws,
-                                           ws_bytes, stream);
-}
-
-// the pair list: the one-probe refusals, the probe sizes read back from the device (coarse_probe.h).
-// The slots are sized by the caller from the largest probe and the largest entry of the launch
-// (fpm_coarse_score_stream_ws_bytes(B, n0max, ngmax)); a pair whose block does not fit its slot gets NaN
-template <typename YT>
-int coarse_pairs_stream_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                               const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
-                               int iters, float tau, float* score, void* ws, long ws_bytes, void* stream) {
-    FPM_CHECK_ARG(G > 0 && Q > 0 && B >= 0, "coarse_pairs_stream: bad sizes (G %d, Q %d, B %d)", G, Q, B);
-    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_pairs_stream: iters >= 0 and tau > 0 required");
-    FPM_CHECK_ARG(y && row_off && idx && yq && qrow_off && qidx && coef && score,
-                  "coarse_pairs_stream: y, row_off, idx, yq, qrow_off, qidx, coef and score are required");
-    if (B == 0) return 0;
-    long lo, hi;
-    if (fpm::coarse_pairs_probe_range(qrow_off, qidx, Q, B, stream, lo, hi)) return 1;
-    FPM_CHECK_ARG(lo >= 1 && hi <= FPM_COARSE_STREAM_NMAX,
-                  "coarse_pairs_stream: probe of %ld keypoints outside [1, COARSE_STREAM_NMAX = %d]",
-                  hi > FPM_COARSE_STREAM_NMAX ? hi : lo, FPM_COARSE_STREAM_NMAX);
-    return coarse_stream_launch<YT, true>(what, y, row_off, idx, G, B, yq, Q, qrow_off, qidx,
-                                          fpm_coarse_score_stream_ws_bytes(B, (int)hi, 1), coef, iters, tau, score, ws,
-                                          ws_bytes, stream);
-}
+};
 }  // namespace
 
 extern "C" int fpm_coarse_score_stream(const float* y, const long* row_off, const int* idx, int G, int B,
                                        const float* yp, int n0, const float* coef, int iters, float tau, float* score,
                                        void* ws, long ws_bytes, void* stream) {
-    return coarse_score_stream_launch<float>("fpm_coarse_score_stream", y, row_off, idx, G, B, yp, n0, coef, iters,
-                                             tau, score, ws, ws_bytes, stream);
+    return fpm::coarse_score_entry<Stream>("fpm_coarse_score_stream", y, row_off, idx, G, B, yp, n0, coef, iters, tau,
+                                           score, ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_score_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                               const float* yp, int n0, const float* coef, int iters, float tau,
                                               float* score, void* ws, long ws_bytes, void* stream) {
-    return coarse_score_stream_launch<bf16_t>("fpm_coarse_score_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B,
-                                              yp, n0, coef, iters, tau, score, ws, ws_bytes, stream);
+    return fpm::coarse_score_entry<Stream>("fpm_coarse_score_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp,
+                                           n0, coef, iters, tau, score, ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_pairs_stream(const float* y, const long* row_off, const int* idx, int G, int B,
                                        const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
                                        int iters, float tau, float* score, void* ws, long ws_bytes, void* stream) {
-    return coarse_pairs_stream_launch<float>("fpm_coarse_pairs_stream", y, row_off, idx, G, B, yq, qrow_off, qidx, Q,
-                                             coef, iters, tau, score, ws, ws_bytes, stream);
+    return fpm::coarse_pairs_entry<Stream>("fpm_coarse_pairs_stream", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef,
+                                           iters, tau, score, ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_pairs_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                               const float* yq, const long* qrow_off, const int* qidx, int Q,
                                               const float* coef, int iters, float tau, float* score, void* ws,
                                               long ws_bytes, void* stream) {
-    return coarse_pairs_stream_launch<bf16_t>("fpm_coarse_pairs_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B,
-                                              yq, qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
+    return fpm::coarse_pairs_entry<Stream>("fpm_coarse_pairs_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
+                                           qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
 }

@@ -32,6 +32,7 @@
 // workgroup, one workgroup per CU.
 #include "fpm_common.h"
 #include "coarse_probe.h"
+#include "coarse_tile.h"
 #include "fpm.h"
 
 namespace {
@@ -50,28 +51,9 @@ constexpr long SLOT_FLOATS = (long)WN * WN;  // Kp of one pair
 constexpr int RED_FLOATS = 4 * WN + 8 * WN + WN + 8;
 constexpr int WLDS = 2 * WBUF + RED_FLOATS * 4;
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, fpm::dpp_f<0xB1>(v));
-    v = fmaxf(v, fpm::dpp_f<0x4E>(v));
-    v = fmaxf(v, fpm::dpp_f<0x141>(v));
-    return fmaxf(v, fpm::dpp_f<0x140>(v));
-}
-// softplus = max(x, 0) + log1p(exp(-|x|)) on the native base-2 transcendentals, with log1p's classic
-// correction for the rounding of 1 + t.  The libm pair (fpm::softplus_f) is ~150 instructions per
-// element, 128 elements per thread: it was a third of this kernel's time.  Measured against float64
-// over N(0, 0.05 .. 4) arguments: mean error 2.7e-8 .. 4.2e-8, the libm pair's 2.4e-8 .. 4.4e-8 (the
-// result's own rounding dominates both).  x > 20: t < 2^-28, the sum rounds to x, torch's threshold.
-__device__ __forceinline__ float softplus_native(float x) {
-    const float t = fpm::fast_exp2(-fabsf(x) * fpm::LOG2E_F);
-    const float u = 1.f + t;
-    const float c = (t - (u - 1.f)) * __builtin_amdgcn_rcpf(u);
-    return fmaxf(x, 0.f) + (fpm::fast_log2(u) * fpm::LN2_F + c);
-}
-// a finite stand-in for the maximum of an all -inf set (exp2(-inf - 0) = 0: an empty sum)
-__device__ __forceinline__ float finite_max(float m) { return m == -INFINITY ? 0.f : m; }
+using namespace fpm::coarse;
+// a K tile: 4 float4 (256 rows) or 2 vectors of 8 bf16 per thread (coarse_tile.h)
+using KTile = Tile<WT, WBK, WROW>;
 
 // This thread's coordinates from a thread index the optimiser cannot see through.  The kernel is one
 // loop over pairs; every index and address below is invariant in it, and hoisted out of it they
@@ -84,45 +66,6 @@ __device__ __forceinline__ Pos fresh_pos() {
     int t = threadIdx.x;
     asm volatile("" : "+v"(t));
     return Pos{t, t & 63, t & 15, (t >> 4) & 3};
-}
-
-// one side's K tile: this thread's 4 float4 (rows (tid >> 3) + 64 m, columns 4 (tid & 7) ..)
-__device__ __forceinline__ void tile_load(const float* __restrict__ base, int n, int k0, int tid, float4 (&r)[4]) {
-    const int row0 = tid >> 3, c = 4 * (tid & 7);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int row = row0 + 64 * m;
-        r[m] = row < n ? *(const float4*)(base + (long)row * WK + k0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-// scale (one fp32 multiply; the unscaled side multiplies by 1, exactly), round to bf16, into LDS
-__device__ __forceinline__ void tile_store(unsigned char* tile, int tid, const float4 (&r)[4], float4 s) {
-    const int row0 = tid >> 3, c = 4 * (tid & 7);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        uint2 o;
-        o.x = fpm::f2bf2(__fmul_rn(r[m].x, s.x), __fmul_rn(r[m].y, s.y));
-        o.y = fpm::f2bf2(__fmul_rn(r[m].z, s.z), __fmul_rn(r[m].w, s.w));
-        *(uint2*)(tile + (row0 + 64 * m) * WROW + c * 2) = o;
-    }
-}
-// the entry's K tile from bf16 rows (fpm_coarse_score_wide_rows16: an index that keeps a bf16 copy of
-// its rows, the same RNE rounding done once at enrolment): this thread's 2 vectors of 8 bf16 (rows
-// (tid >> 2) + 128 m, columns 8 (tid & 3) ..; a row is 1536 B, so every vector is 16-B aligned),
-// zeros past n
-__device__ __forceinline__ void tile_load16(const bf16_t* __restrict__ base, int n, int k0, int tid, uint4 (&r)[2]) {
-    const int row0 = tid >> 2, c = 8 * (tid & 3);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int row = row0 + 128 * m;
-        r[m] = row < n ? *(const uint4*)(base + (long)row * WK + k0 + c) : make_uint4(0u, 0u, 0u, 0u);
-    }
-}
-// as they are into the tile_store layout: no multiply, no convert
-__device__ __forceinline__ void tile_store16(unsigned char* tile, int tid, const uint4 (&r)[2]) {
-    const int row0 = tid >> 2, c = 8 * (tid & 3);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) *(uint4*)(tile + (row0 + 128 * m) * WROW + c * 2) = r[m];
 }
 
 // YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment); the
@@ -197,32 +140,32 @@ __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restr
             float4 ra[4], rb[4], sc;
             uint4 re[2];                                 // bf16 entry rows: ra is the probe's tile, re the entry's
             if constexpr (F32) {
-                tile_load(xa, R, 0, tid, ra);
-                tile_load(xb, C, 0, tid, rb);
+                KTile::load(xa, R, 0, 0, tid, ra);
+                KTile::load(xb, C, 0, 0, tid, rb);
             } else {
-                tile_load(yp, n0, 0, tid, ra);
-                tile_load16(ye, ng, 0, tid, re);
+                KTile::load(yp, n0, 0, 0, tid, ra);
+                KTile::load16(ye, ng, 0, 0, tid, re);
             }
             sc = *(const float4*)(cf + c4);
             for (int kt = 0; kt < WK / WBK; ++kt) {
                 unsigned char* At = wlds + (kt & 1) * WBUF;
                 unsigned char* Bt = At + WTILE;
                 if constexpr (F32) {
-                    tile_store(At, tid, ra, tr ? one : sc);
-                    tile_store(Bt, tid, rb, tr ? sc : one);
+                    KTile::store(At, tid, ra, tr ? one : sc);
+                    KTile::store(Bt, tid, rb, tr ? sc : one);
                 } else {                                 // the entry is the MFMA's A when transposed, B otherwise
-                    tile_store(tr ? Bt : At, tid, ra, sc);
-                    tile_store16(tr ? At : Bt, tid, re);
+                    KTile::store(tr ? Bt : At, tid, ra, sc);
+                    KTile::store16(tr ? At : Bt, tid, re);
                 }
                 // one barrier per tile: the other buffer was last read before the previous barrier
                 __syncthreads();
                 if (kt + 1 < WK / WBK) {
                     if constexpr (F32) {
-                        tile_load(xa, R, (kt + 1) * WBK, tid, ra);
-                        tile_load(xb, C, (kt + 1) * WBK, tid, rb);
+                        KTile::load(xa, R, 0, (kt + 1) * WBK, tid, ra);
+                        KTile::load(xb, C, 0, (kt + 1) * WBK, tid, rb);
                     } else {
-                        tile_load(yp, n0, (kt + 1) * WBK, tid, ra);
-                        tile_load16(ye, ng, (kt + 1) * WBK, tid, re);
+                        KTile::load(yp, n0, 0, (kt + 1) * WBK, tid, ra);
+                        KTile::load16(ye, ng, 0, (kt + 1) * WBK, tid, re);
                     }
                     sc = *(const float4*)(cf + (kt + 1) * WBK + c4);
                 }
@@ -435,86 +378,58 @@ extern "C" long fpm_coarse_score_wide_ws_bytes(int B) {
 }
 
 namespace {
-template <typename YT, bool PAIRS>
-int coarse_wide_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                       const float* ypq, int n0q, const long* qrow_off, const int* qidx, const float* coef, int iters,
-                       float tau, float* score, void* ws, long ws_bytes, void* stream) {
-    const long need = fpm_coarse_score_wide_ws_bytes(B);
-    FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
-                  "coarse_score_wide: workspace of %ld bytes (16-byte aligned) required, got %ld", need, ws_bytes);
-    if (hipFuncSetAttribute((const void*)coarse_score_wide_kernel<YT, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            WLDS) != hipSuccess) {
-        (void)hipGetLastError();
-        fpm::set_error("coarse_score_wide: %d bytes of LDS per workgroup refused", WLDS);
-        return 1;
+// the traits of fpm::coarse_score_entry / coarse_pairs_entry (coarse_probe.h); one slot per workgroup
+struct Wide {
+    static constexpr const char *score_op = "coarse_score_wide", *pairs_op = "coarse_pairs_wide",
+                                *bound = "COARSE_WIDE_NMAX";
+    static constexpr int nmax = FPM_COARSE_WIDE_NMAX;
+    template <typename YT, bool PAIRS>
+    static int launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B, const float* ypq,
+                      int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
+                      float* score, void* ws, long ws_bytes, void* stream) {
+        const long need = fpm_coarse_score_wide_ws_bytes(B);
+        FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
+                      "coarse_score_wide: workspace of %ld bytes (16-byte aligned) required, got %ld", need, ws_bytes);
+        if (hipFuncSetAttribute((const void*)coarse_score_wide_kernel<YT, PAIRS>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, WLDS) != hipSuccess) {
+            (void)hipGetLastError();
+            fpm::set_error("coarse_score_wide: %d bytes of LDS per workgroup refused", WLDS);
+            return 1;
+        }
+        const int grid = B < WGRID ? B : WGRID;
+        hipLaunchKernelGGL((coarse_score_wide_kernel<YT, PAIRS>), dim3((unsigned)grid), dim3(WT), WLDS,
+                           (hipStream_t)stream, y, row_off, idx, G, B, ypq, n0q, coef, iters, tau, score, (float*)ws,
+                           qrow_off, qidx);
+        return fpm::check_launch(what);
     }
-    const int grid = B < WGRID ? B : WGRID;
-    hipLaunchKernelGGL((coarse_score_wide_kernel<YT, PAIRS>), dim3((unsigned)grid), dim3(WT), WLDS, (hipStream_t)stream, y,
-                       row_off, idx, G, B, ypq, n0q, coef, iters, tau, score, (float*)ws, qrow_off, qidx);
-    return fpm::check_launch(what);
-}
-
-template <typename YT>
-int coarse_score_wide_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                             const float* yp, int n0, const float* coef, int iters, float tau, float* score, void* ws,
-                             long ws_bytes, void* stream) {
-    FPM_CHECK_ARG(G > 0 && B >= 0, "coarse_score_wide: bad sizes (G %d, B %d)", G, B);
-    FPM_CHECK_ARG(n0 >= 1 && n0 <= FPM_COARSE_WIDE_NMAX,
-                  "coarse_score_wide: probe of %d keypoints outside [1, COARSE_WIDE_NMAX = %d]", n0,
-                  FPM_COARSE_WIDE_NMAX);
-    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_score_wide: iters >= 0 and tau > 0 required");
-    FPM_CHECK_ARG(y && row_off && idx && yp && coef && score,
-                  "coarse_score_wide: y, row_off, idx, yp, coef and score are required");
-    if (B == 0) return 0;
-    return coarse_wide_launch<YT, false>(what, y, row_off, idx, G, B, yp, n0, nullptr, nullptr, coef, iters, tau, score, ws,
-                                         ws_bytes, stream);
-}
-
-// the pair list: the one-probe refusals, the probe sizes read back from the device (coarse_probe.h)
-template <typename YT>
-int coarse_pairs_wide_launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B,
-                             const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
-                             float tau, float* score, void* ws, long ws_bytes, void* stream) {
-    FPM_CHECK_ARG(G > 0 && Q > 0 && B >= 0, "coarse_pairs_wide: bad sizes (G %d, Q %d, B %d)", G, Q, B);
-    FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "coarse_pairs_wide: iters >= 0 and tau > 0 required");
-    FPM_CHECK_ARG(y && row_off && idx && yq && qrow_off && qidx && coef && score,
-                  "coarse_pairs_wide: y, row_off, idx, yq, qrow_off, qidx, coef and score are required");
-    if (B == 0) return 0;
-    long lo, hi;
-    if (fpm::coarse_pairs_probe_range(qrow_off, qidx, Q, B, stream, lo, hi)) return 1;
-    FPM_CHECK_ARG(lo >= 1 && hi <= FPM_COARSE_WIDE_NMAX,
-                  "coarse_pairs_wide: probe of %ld keypoints outside [1, COARSE_WIDE_NMAX = %d]",
-                  hi > FPM_COARSE_WIDE_NMAX ? hi : lo, FPM_COARSE_WIDE_NMAX);
-    return coarse_wide_launch<YT, true>(what, y, row_off, idx, G, B, yq, Q, qrow_off, qidx, coef, iters, tau, score, ws,
-                                        ws_bytes, stream);
-}
+};
 }  // namespace
 
 extern "C" int fpm_coarse_score_wide(const float* y, const long* row_off, const int* idx, int G, int B,
                                      const float* yp, int n0, const float* coef, int iters, float tau, float* score,
                                      void* ws, long ws_bytes, void* stream) {
-    return coarse_score_wide_launch<float>("fpm_coarse_score_wide", y, row_off, idx, G, B, yp, n0, coef, iters, tau,
-                                           score, ws, ws_bytes, stream);
+    return fpm::coarse_score_entry<Wide>("fpm_coarse_score_wide", y, row_off, idx, G, B, yp, n0, coef, iters, tau, score,
+                                         ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_score_wide_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                             const float* yp, int n0, const float* coef, int iters, float tau,
                                             float* score, void* ws, long ws_bytes, void* stream) {
-    return coarse_score_wide_launch<bf16_t>("fpm_coarse_score_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp,
-                                            n0, coef, iters, tau, score, ws, ws_bytes, stream);
+    return fpm::coarse_score_entry<Wide>("fpm_coarse_score_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0,
+                                         coef, iters, tau, score, ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_pairs_wide(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
                                      const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
                                      float tau, float* score, void* ws, long ws_bytes, void* stream) {
-    return coarse_pairs_wide_launch<float>("fpm_coarse_pairs_wide", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef,
-                                           iters, tau, score, ws, ws_bytes, stream);
+    return fpm::coarse_pairs_entry<Wide>("fpm_coarse_pairs_wide", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef,
+                                         iters, tau, score, ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_pairs_wide_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                             const float* yq, const long* qrow_off, const int* qidx, int Q,
                                             const float* coef, int iters, float tau, float* score, void* ws,
                                             long ws_bytes, void* stream) {
-    return coarse_pairs_wide_launch<bf16_t>("fpm_coarse_pairs_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
-                                            qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
+    return fpm::coarse_pairs_entry<Wide>("fpm_coarse_pairs_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
+                                         qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
 }

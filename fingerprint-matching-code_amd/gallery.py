@@ -31,6 +31,7 @@ forward runs in groups of probes (``probe_groups``) on batches whose two sides a
 cached rows (``pair_batch``).  Every score and output is the bits of the one-probe path's for the same
 pair and padded box.
 """
+import contextlib
 import hashlib
 
 import numpy as np
@@ -40,7 +41,7 @@ from . import config as C
 from . import ops
 from ._lib import FpmError
 from .batch import DeviceBatch, ORDER_MIN_NMAX, ORDER_ON, hilbert_order
-from .model import _CachedSide, _cached_sides
+from .model import _CachedSide
 
 FORMAT = 1                    # a saved "f32" index; the other layouts write FORMAT_LAYOUTS
 FORMAT_LAYOUTS = 2
@@ -201,13 +202,7 @@ class GalleryIndex:
         """Side 1 of a probe x gallery batch over the entries ``select`` (None: all), in that order,
         as DeviceBatch.from_pairs lays it out: (sel host int64, dict of batch fields).  Independent
         of the probe, so the last selection's data is kept for the next query."""
-        G = self.G
-        if select is None:
-            sel = torch.arange(G, dtype=torch.int64)
-        else:
-            sel = torch.as_tensor(select, dtype=torch.int64).view(-1).cpu()
-            if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= G:
-                raise FpmError("identify: select must name entries in [0, %d)" % G)
+        sel = _select_host(self, select, "identify")
         if self._sel is not None and torch.equal(self._sel[0], sel):
             return self._sel
         self._sel = (sel, self._gather(sel))
@@ -244,36 +239,23 @@ class GalleryIndex:
         return f
 
 
-class _GalleryBatch(DeviceBatch):
-    """A probe x gallery batch whose side 1 lives in a GalleryIndex: laid out like
-    ``DeviceBatch.from_probe_gallery`` (shared side 0), except that no node features are staged:
-    x[0] is the probe's rows once (every sub-batch sees the same rows), x[1] is empty, and ``cached``
-    (model._CachedSide) names the index rows of each pair.  ``sc_mode``: the index's SplineConv
-    arithmetic, which the forward follows (Net._sc_f32)."""
+class _CachedBatch(DeviceBatch):
+    """A batch one or both of whose sides live in a GalleryIndex: laid out like ``DeviceBatch.from_pairs``,
+    except that a cached side stages no node features: ``cached`` (a pair of model._CachedSide, None for a
+    side with features of its own) names the index rows of each pair, and x is carried whole into every
+    sub-batch.  A probe x gallery batch (``probe_batch``: shared side 0) has x[0] the probe's rows once,
+    x[1] empty and side 1 cached; a pair batch (``pair_batch``: no shared side, repeated probes and entries
+    are ordinary pairs) has both sides cached and x empty.  ``sc_mode``: the index's SplineConv arithmetic,
+    which the forward follows (Net._sc_f32)."""
 
-    def split_range(self, b0, b1):
-        if not 0 <= b0 < b1 <= self.B:
-            raise ValueError("split_range: bad pair range [%d, %d) of %d" % (b0, b1, self.B))
-        ws, ss, ds, ps = [], [], [], []
-        for side in range(2):
-            nm = self.nmax[side]
-            e0, e1 = int(self.edge_off[side][b0]), int(self.edge_off[side][b1])
-            ws.append(self.w[side][b0:b1])
-            ss.append((self.src[side][e0:e1] - b0 * nm).contiguous())
-            ds.append((self.dst[side][e0:e1] - b0 * nm).contiguous())
-            ps.append(self.pseudo[side][e0:e1])
-        eo = [self.edge_off[side][b0:b1 + 1] - self.edge_off[side][b0] for side in range(2)]
-        sub = _GalleryBatch(b1 - b0, self.n_host[0][b0:b1], self.n_host[1][b0:b1], list(self.x), ws, ss, ds, ps,
-                            self.device, nmax=self.nmax, edge_off=eo, shared0=True)
-        sub.pair_range = (b0, b1)
-        sub.ord2 = None if self.ord2 is None else self.ord2[b0:b1]
-        sub.cached = self.cached.slice(b0, b1)
+    def _carry(self, sub, b0, b1):
+        sub.x = list(self.x)
+        sub.cached = tuple(c and c.slice(b0, b1) for c in self.cached)
         sub.sc_mode = self.sc_mode
-        return sub
 
     def to(self, device, non_blocking=True):
         if torch.device(device) != self.device:
-            raise FpmError("a gallery batch stays on its index's device")
+            raise FpmError("a batch over cached index rows stays on its index's device")
         return self
 
 
@@ -387,7 +369,7 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32"):
 
 
 def probe_batch(probe, index, select=None):
-    """The probe x gallery batch of one probe graph over ``index`` -> (_GalleryBatch, sel host int64)."""
+    """The probe x gallery batch of one probe graph over ``index`` -> (_CachedBatch, sel host int64)."""
     dev = index.device
     sel, f = index._selection(select)
     B, n0 = int(sel.numel()), int(probe["n"])
@@ -401,17 +383,17 @@ def probe_batch(probe, index, select=None):
     ps0 = ps.view(1, e0, 2).expand(B, e0, 2).reshape(-1, 2).contiguous()
     w0 = torch.from_numpy(np.asarray(probe["w"], dtype=np.float32)).to(dev).view(1, -1).expand(B, -1).contiguous()
     eo0 = torch.arange(B + 1, dtype=torch.int64) * e0
-    bt = _GalleryBatch(B, np.full(B, n0, np.int32), f["n"], [x0, x0.new_empty(0, C.NODE_FEATURE_DIM)], [w0, f["w"]],
-                       [src0, f["src"]], [dst0, f["dst"]], [ps0, f["pseudo"]], dev, nmax=[n0, f["nmax"]],
-                       edge_off=[eo0, f["edge_off"]], shared0=True)
+    bt = _CachedBatch(B, np.full(B, n0, np.int32), f["n"], [x0, x0.new_empty(0, C.NODE_FEATURE_DIM)], [w0, f["w"]],
+                      [src0, f["src"]], [dst0, f["dst"]], [ps0, f["pseudo"]], dev, nmax=[n0, f["nmax"]],
+                      edge_off=[eo0, f["edge_off"]], shared0=True)
     if index.layout == "bf16+host":
         # the selected entries' fp32 rows, staged on the device in selection order: pair b reads staged
         # entry b (f["idx"], top_idx and short_idx keep speaking gallery entry numbers)
         ys, off_d, off_h = index.fetch(sel)
         ar = torch.arange(B, dtype=torch.int32)
-        bt.cached = _CachedSide(ys, off_d, off_h, ar.to(dev), ar)
+        bt.cached = (None, _CachedSide(ys, off_d, off_h, ar.to(dev), ar))
     else:
-        bt.cached = _CachedSide(index.y, index.row_off, index.row_off_host, f["idx"], f["idx_host"])
+        bt.cached = (None, _CachedSide(index.y, index.row_off, index.row_off_host, f["idx"], f["idx_host"]))
     bt.sc_mode = index.sc_mode
     bt.ord2 = f["ord2"]
     return bt, sel
@@ -461,7 +443,24 @@ def _select_host(index, select, what):
 
 
 COARSE_ROUTES = ("fused", "wide", "auto", "stream", "any")
-_COARSE_OPS = (ops.coarse_score, ops.coarse_score_wide, ops.coarse_score_stream)     # by route number
+
+
+def _check_shortlist(shortlist, what):
+    M = int(shortlist)
+    if not 1 <= M <= ops.RANK_SELECT_KMAX:
+        raise FpmError("%s: shortlist = %d outside [1, %d]" % (what, M, ops.RANK_SELECT_KMAX))
+    return M
+
+
+@contextlib.contextmanager
+def _eager_prologue(net):
+    """Cached-row forwards run their prologue eagerly: no HIP-graph capture per query batch."""
+    keep = net.prologue_graph
+    net.prologue_graph = 0
+    try:
+        yield
+    finally:
+        net.prologue_graph = keep
 
 
 def _check_coarse(coarse, what):
@@ -471,8 +470,9 @@ def _check_coarse(coarse, what):
 
 def coarse_routes(n0, ng, coarse="any"):
     """The kernel of each pair of a probe of ``n0`` keypoints and entries of ``ng`` keypoints (host
-    tensor), by number: 0 fused, 1 wide, 2 stream -> host int64 tensor.  ``n0``: one probe's count, or
-    (a pair list) a host tensor of ng's length, the probe's count of each pair.  "fused" / "wide" /
+    tensor), by number (its place in ``ops.COARSE_KERNELS``): 0 fused, 1 wide, 2 stream -> host int64
+    tensor.  ``n0``: one probe's count, or (a pair list) a host tensor of ng's length, the probe's count of
+    each pair.  "fused" / "wide" /
     "stream": that kernel for every pair; "auto": fused when both sides fit COARSE_NMAX, wide otherwise;
     "any": fused when both sides fit COARSE_NMAX, wide when both fit COARSE_WIDE_NMAX, stream otherwise.
     The route depends on the pair alone (its larger side).  Refuses what the route's largest kernel
@@ -484,7 +484,7 @@ def coarse_routes(n0, ng, coarse="any"):
         raise FpmError("coarse_routes: n0 must be one count or one per pair (%d for %d pairs)" % (n0.numel(), ng.numel()))
     _check_route_bounds(max(int(n0.max()), int(ng.max())), min(int(n0.min()), int(ng.min())), coarse)
     if coarse in ("fused", "wide", "stream"):
-        return torch.full_like(ng, ("fused", "wide", "stream").index(coarse))
+        return torch.full_like(ng, ops.COARSE_KERNELS.index(coarse))
     side = torch.maximum(ng, n0.expand_as(ng))                   # the pair's larger side
     rt = (side > ops.COARSE_NMAX).long()
     if coarse == "any":
@@ -509,41 +509,48 @@ def _check_route_bounds(top, low, coarse):
                        % (top, ops.COARSE_STREAM_NMAX))
 
 
-def _coarse_launch(route, index, sel_d, sel32, yp, cf, out, iters, tau):
-    # the bf16 copy of the rows when the index keeps one: half the bytes, the same operands
-    rows = index.y if index.y16 is None else index.y16
-    _COARSE_OPS[route](rows, index.row_off, sel_d, yp, cf, iters=iters, tau=tau, out=out, idx_host=sel32,
-                       row_off_host=index.row_off_host)
+def _launch_by_route(rt, cf, dst, launch):
+    """One chunk of a coarse pass, its pairs' routes ``rt`` (``coarse_routes``, host), coefficient rows ``cf``
+    and scores ``dst`` (device): ``launch(kernel, pos, pos_d, cf, dst)`` scores the chunk's pairs at positions
+    ``pos`` (a host index, ``pos_d`` the same on the device) with ``kernel`` of ``ops.COARSE_KERNELS``.  One
+    launch over the whole chunk (the index is the full slice: views, no copies) when every pair takes the
+    same kernel; else each kernel's pairs with their coefficient rows gathered, the scores scattered back."""
+    kinds = torch.unique(rt).tolist()
+    if len(kinds) == 1:
+        launch(ops.COARSE_KERNELS[kinds[0]], slice(None), slice(None), cf, dst)
+        return
+    for route in kinds:
+        pos = torch.nonzero(rt == route).view(-1)
+        pos_d = pos.to(cf.device)
+        part = torch.empty(int(pos.numel()), device=cf.device, dtype=torch.float32)
+        launch(ops.COARSE_KERNELS[route], pos, pos_d, cf[pos_d].contiguous(), part)
+        dst[pos_d] = part
 
 
 def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk, coarse="fused"):
     """One probe's coarse scores over the entries ``sel`` into ``out`` (len(sel),).  ``coarse``: the
-    route (``coarse_routes``; host copy of n: no synchronisation).  A chunk whose pairs take more than
-    one kernel is split: each part's entries and coefficient rows, the scores scattered back."""
+    route (``coarse_routes``; host copy of n: no synchronisation)."""
     rt = coarse_routes(int(probe["n"]), index.n[sel], coarse)
     ps = _ProbeSide(probe, index)
     yp = net._probe_rows(wp, ps)
     sel32 = sel.to(torch.int32)
+    # the bf16 copy of the rows when the index keeps one: half the bytes, the same operands
+    rows = index.y if index.y16 is None else index.y16
     B = int(sel.numel())
     step = max(1, int(chunk))
     coef = torch.empty(min(B, step), C.NODE_FEATURE_DIM, device=index.device, dtype=torch.float32)
     w0 = ps.w0.expand(min(B, step), -1).contiguous()
     for b0 in range(0, B, step):
         b1 = min(B, b0 + step)
+
+        def launch(kernel, pos, pos_d, cf, dst):
+            ops._coarse_score_op(kernel, rows, index.row_off, sel_d[b0:b1][pos_d].contiguous(), yp, cf, C.SK_ITER_NUM,
+                                 net.tau, dst, sel32[b0:b1][pos], index.row_off_host, None)
+
         gw = ops.global_weights(w0[:b1 - b0], index.w[sel_d[b0:b1].long()])
         cf = coef[:b1 - b0]
         ops.coef_tanh(gw, wp["aff_wT"], wp["aff_b"], cf)
-        kinds = torch.unique(rt[b0:b1]).tolist()
-        if len(kinds) == 1:
-            _coarse_launch(kinds[0], index, sel_d[b0:b1], sel32[b0:b1], yp, cf, out[b0:b1], C.SK_ITER_NUM, net.tau)
-            continue
-        for route in kinds:
-            pos = torch.nonzero(rt[b0:b1] == route).view(-1)
-            pos_d = pos.to(index.device)
-            part = torch.empty(int(pos.numel()), device=index.device, dtype=torch.float32)
-            _coarse_launch(route, index, sel_d[b0:b1][pos_d].contiguous(), sel32[b0:b1][pos],
-                           yp, cf[pos_d].contiguous(), part, C.SK_ITER_NUM, net.tau)
-            out[b0:b1][pos_d] = part
+        _launch_by_route(rt[b0:b1], cf, out[b0:b1], launch)
 
 
 def coarse_scores(net, probes, index, select=None, chunk=COARSE_CHUNK, coarse="fused"):
@@ -579,32 +586,25 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
     single = isinstance(probes, dict)
     plist = [probes] if single else list(probes)
     outs, sel = [], None
-    keep = net.prologue_graph
-    net.prologue_graph = 0                  # eager prologue: no capture per query batch
-    try:
-        with torch.cuda.device(index.device):
-            for p in plist:
-                bt, sel = probe_batch(p, index, select)
-                outs.append(net.run(bt, chunks=chunks))
-            if outs:
-                k = max(1, min(int(topk), int(sel.numel()), 128))
-                sc = torch.stack([o[score].view(-1) for o in outs])
-                ti, ts = ops.rank_topk(sc, k)
-                sel_d = index._sel[1]["idx"]
-                ti = sel_d[ti.long()]
-                for i, o in enumerate(outs):
-                    o["top_idx"], o["top_score"] = ti[i], ts[i]
-    finally:
-        net.prologue_graph = keep
+    with _eager_prologue(net), torch.cuda.device(index.device):
+        for p in plist:
+            bt, sel = probe_batch(p, index, select)
+            outs.append(net.run(bt, chunks=chunks))
+        if outs:
+            k = max(1, min(int(topk), int(sel.numel()), 128))
+            sc = torch.stack([o[score].view(-1) for o in outs])
+            ti, ts = ops.rank_topk(sc, k)
+            sel_d = index._sel[1]["idx"]
+            ti = sel_d[ti.long()]
+            for i, o in enumerate(outs):
+                o["top_idx"], o["top_score"] = ti[i], ts[i]
     return outs[0] if single else outs
 
 
 def _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist, coarse="fused"):
     """``identify(shortlist=M)``: per probe the coarse pass over ``select``, the M best entries
     (``ops.rank_select``), and the plain ``identify`` over exactly those, in coarse-rank order."""
-    M = int(shortlist)
-    if not 1 <= M <= ops.RANK_SELECT_KMAX:
-        raise FpmError("identify: shortlist = %d outside [1, %d]" % (M, ops.RANK_SELECT_KMAX))
+    M = _check_shortlist(shortlist, "identify")
     sel = _select_host(index, select, "identify")
     M = min(M, int(sel.numel()))
     single = isinstance(probes, dict)
@@ -626,39 +626,6 @@ def _identify_shortlist(net, probes, index, topk, select, score, chunks, shortli
 
 # ---- probe sets: many probes against an enrolled gallery at once -----------------------------------
 COARSE_PAIRS_CHUNK = 16384   # pairs per coarse launch: 48 MB of coefficient scratch, whatever the two sets
-_PAIR_KERNELS = ("fused", "wide", "stream")                      # ops.coarse_pairs' kernel by route number
-
-
-class _PairBatch(DeviceBatch):
-    """A batch over a pair list (q_b, g_b) of a probe set and a gallery index, laid out like
-    ``DeviceBatch.from_pairs``, except that no node features are staged on either side: x is empty and
-    ``cached`` is a pair of model._CachedSide, naming each pair's rows in the two indexes.  No shared
-    side: repeated probes and entries are ordinary pairs."""
-
-    def split_range(self, b0, b1):
-        if not 0 <= b0 < b1 <= self.B:
-            raise ValueError("split_range: bad pair range [%d, %d) of %d" % (b0, b1, self.B))
-        ws, ss, ds, ps = [], [], [], []
-        for side in range(2):
-            nm = self.nmax[side]
-            e0, e1 = int(self.edge_off[side][b0]), int(self.edge_off[side][b1])
-            ws.append(self.w[side][b0:b1])
-            ss.append((self.src[side][e0:e1] - b0 * nm).contiguous())
-            ds.append((self.dst[side][e0:e1] - b0 * nm).contiguous())
-            ps.append(self.pseudo[side][e0:e1])
-        eo = [self.edge_off[side][b0:b1 + 1] - self.edge_off[side][b0] for side in range(2)]
-        sub = _PairBatch(b1 - b0, self.n_host[0][b0:b1], self.n_host[1][b0:b1], list(self.x), ws, ss, ds, ps,
-                         self.device, nmax=self.nmax, edge_off=eo, shared0=False)
-        sub.pair_range = (b0, b1)
-        sub.ord2 = None if self.ord2 is None else self.ord2[b0:b1]
-        sub.cached = tuple(c.slice(b0, b1) for c in _cached_sides(self))
-        sub.sc_mode = self.sc_mode
-        return sub
-
-    def to(self, device, non_blocking=True):
-        if torch.device(device) != self.device:
-            raise FpmError("a pair batch stays on its indexes' device")
-        return self
 
 
 def _check_probe_set(probes, index, what):
@@ -695,16 +662,16 @@ def _check_many(net, probes, index, what):
 
 def pair_batch(probes, index, pairs):
     """The batch of the pair list ``pairs`` ((B, 2) host int64: probe number, entry number, both in
-    range) over a probe set and a gallery index -> _PairBatch.  On a "bf16+host" gallery the distinct
+    range) over a probe set and a gallery index -> _CachedBatch.  On a "bf16+host" gallery the distinct
     entries' fp32 rows are fetched and the pairs renumbered to the staging buffer."""
     dev = index.device
     q, g = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
     f0, f1 = probes._gather(q), index._gather(g)
     B = int(q.numel())
     empty = torch.empty(0, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
-    bt = _PairBatch(B, f0["n"], f1["n"], [empty, empty], [f0["w"], f1["w"]], [f0["src"], f1["src"]],
-                    [f0["dst"], f1["dst"]], [f0["pseudo"], f1["pseudo"]], dev, nmax=[f0["nmax"], f1["nmax"]],
-                    edge_off=[f0["edge_off"], f1["edge_off"]], shared0=False)
+    bt = _CachedBatch(B, f0["n"], f1["n"], [empty, empty], [f0["w"], f1["w"]], [f0["src"], f1["src"]],
+                      [f0["dst"], f1["dst"]], [f0["pseudo"], f1["pseudo"]], dev, nmax=[f0["nmax"], f1["nmax"]],
+                      edge_off=[f0["edge_off"], f1["edge_off"]], shared0=False)
     c0 = _CachedSide(probes.y, probes.row_off, probes.row_off_host, f0["idx"], f0["idx_host"])
     if index.layout == "bf16+host":
         uniq, inv = torch.unique(g, return_inverse=True)
@@ -720,13 +687,8 @@ def pair_batch(probes, index, pairs):
 
 
 def _run_pairs(net, probes, index, pairs, chunks):
-    keep = net.prologue_graph
-    net.prologue_graph = 0                  # eager prologue: no capture per pair batch
-    try:
-        with torch.cuda.device(index.device):
-            return net.run(pair_batch(probes, index, pairs), chunks=chunks)
-    finally:
-        net.prologue_graph = keep
+    with _eager_prologue(net), torch.cuda.device(index.device):
+        return net.run(pair_batch(probes, index, pairs), chunks=chunks)
 
 
 def match_pairs(net, probes, index, pairs, chunks=None):
@@ -770,11 +732,6 @@ def coarse_scores_many(net, probes, index, probe_select=None, select=None, coars
     step = max(1, int(COARSE_PAIRS_CHUNK))
     coef = torch.empty(min(total, step), C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
 
-    def launch(route, q32, g32, cf, dst):
-        ops.coarse_pairs(rows, index.row_off, g32.to(dev), probes.y, probes.row_off, q32.to(dev), cf,
-                         kernel=_PAIR_KERNELS[route], iters=C.SK_ITER_NUM, tau=net.tau, out=dst, gidx_host=g32,
-                         qidx_host=q32, row_off_host=index.row_off_host, qrow_off_host=probes.row_off_host)
-
     with torch.cuda.device(dev):
         for p0 in range(0, total, step):
             p1 = min(total, p0 + step)
@@ -787,15 +744,14 @@ def coarse_scores_many(net, probes, index, probe_select=None, select=None, coars
             cf = coef[:p1 - p0]
             ops.coef_tanh(gw, wp["aff_wT"], wp["aff_b"], cf)
             q32, g32 = q.to(torch.int32), g.to(torch.int32)
-            kinds = torch.unique(rt).tolist()
-            if len(kinds) == 1:
-                launch(kinds[0], q32, g32, cf, dst)
-            for route in kinds if len(kinds) > 1 else ():        # each kernel's pairs, the scores scattered back
-                pos = torch.nonzero(rt == route).view(-1)
-                pos_d = pos.to(dev)
-                part = torch.empty(int(pos.numel()), device=dev, dtype=torch.float32)
-                launch(route, q32[pos].contiguous(), g32[pos].contiguous(), cf[pos_d].contiguous(), part)
-                dst[pos_d] = part
+
+            def launch(kernel, pos, pos_d, cf, dst):
+                qk, gk = q32[pos].contiguous(), g32[pos].contiguous()
+                ops.coarse_pairs(rows, index.row_off, gk.to(dev), probes.y, probes.row_off, qk.to(dev), cf,
+                                 kernel=kernel, iters=C.SK_ITER_NUM, tau=net.tau, out=dst, gidx_host=gk,
+                                 qidx_host=qk, row_off_host=index.row_off_host, qrow_off_host=probes.row_off_host)
+
+            _launch_by_route(rt, cf, dst, launch)
             if where is not None:
                 flat[where.to(dev)] = dst
     return out
@@ -852,10 +808,7 @@ def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None
         psel_d, sel_d = psel.to(dev), sel.to(dev)
         own = (psel_d.view(-1, 1) == sel_d.view(1, -1)) if exclude_self else None
         if shortlist is not None:
-            M = int(shortlist)
-            if not 1 <= M <= ops.RANK_SELECT_KMAX:
-                raise FpmError("%s: shortlist = %d outside [1, %d]" % (what, M, ops.RANK_SELECT_KMAX))
-            M = min(M, Gs - 1 if exclude_self else Gs)
+            M = min(_check_shortlist(shortlist, what), Gs - 1 if exclude_self else Gs)
             call = coarse_scores_many(net, probes, index, probe_select=psel, select=sel, coarse=coarse)
             ranked = call if own is None else call.masked_fill(own, float("-inf"))
             pos, csc = ops.rank_select(ranked, M)

@@ -98,8 +98,8 @@ class _CachedSide:
     ``y`` / ``row_off``: the index's fp32 rows and graph row offsets (device; ``row_off_host`` its host
     copy); ``idx`` (device int32) / ``idx_host``: the index entry of each pair of the (sub-)batch.
     Handed to _spline_side as that side's x_op; a pipeline chunk slices idx, never rows.  A batch's
-    ``cached`` is one _CachedSide (side 1: a probe x gallery batch) or a pair (side 0, side 1), either of
-    which may be None (a pair batch over a probe set and a gallery has both: ``_cached_sides``)."""
+    ``cached`` is the pair (side 0's, side 1's), None for a side that runs its own SplineConv (a probe x
+    gallery batch caches side 1, a pair batch over a probe set and a gallery both: ``_cached_sides``)."""
 
     def __init__(self, y, row_off, row_off_host, idx, idx_host):
         self.y, self.row_off, self.row_off_host, self.idx, self.idx_host = y, row_off, row_off_host, idx, idx_host
@@ -109,11 +109,8 @@ class _CachedSide:
 
 
 def _cached_sides(bt):
-    """(side 0's, side 1's) _CachedSide of a batch, None where that side runs its own SplineConv."""
-    c = getattr(bt, "cached", None)
-    if c is None:
-        return (None, None)
-    return tuple(c) if isinstance(c, (tuple, list)) else (None, c)
+    """A batch's ``cached`` pair; (None, None) for a batch that has none."""
+    return getattr(bt, "cached", None) or (None, None)
 
 
 class _TailView:

@@ -534,11 +534,6 @@ def _bf16_rne(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
 
-def _rows16(y):
-    """The suffix of a coarse kernel's entry point for the index rows ``y``: fp32, or their bf16 copy."""
-    return "_rows16" if y.dtype == torch.bfloat16 else ""
-
-
 def _coarse_score_host(y, row_off, idx, yp, coef, iters, tau, dtype):
     """The definition of the coarse score in plain torch (``dtype`` fp32 or fp64 arithmetic on the
     bf16-rounded operands): Kp = softplus(a b^T) - 0.5, pygmtools' log Sinkhorn with dummy rows,
@@ -566,38 +561,114 @@ def _coarse_score_host(y, row_off, idx, yp, coef, iters, tau, dtype):
     return out
 
 
-def _coarse_score_op(op, bound, nmax, launch, y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host,
-                     dtype):
-    """The host-side checks and dispatch shared by ``coarse_score``, ``coarse_score_wide`` and
-    ``coarse_score_stream``: ``op`` names the operation in every message, ``bound`` / ``nmax`` the size
-    limit of its kernel; ``launch(G, B, n0, iters, tau, out, ngmax)`` (ngmax: the largest selected
-    n_g) runs the kernel once everything has been checked."""
-    for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)):
+# The coarse kernels by route name (``gallery.coarse_routes`` numbers them in this order): the C symbol of the
+# one-probe and of the pair-list entry point, the size bound's name and value, and how many of
+# (B, n0max, ngmax) the kernel's ``<one-probe symbol>_ws_bytes`` takes (0: no workspace).
+_COARSE_KERNELS = {"fused": ("fpm_coarse_score", "fpm_coarse_pairs", "COARSE_NMAX", COARSE_NMAX, 0),
+                   "wide": ("fpm_coarse_score_wide", "fpm_coarse_pairs_wide", "COARSE_WIDE_NMAX", COARSE_WIDE_NMAX, 1),
+                   "stream": ("fpm_coarse_score_stream", "fpm_coarse_pairs_stream", "COARSE_STREAM_NMAX",
+                              COARSE_STREAM_NMAX, 3)}
+COARSE_KERNELS = tuple(_COARSE_KERNELS)
+
+
+def _coarse_call(kernel, pairs, y, args, B, n0max, ngmax):
+    """Launch ``kernel``'s one-probe or pair-list (``pairs``) entry point for the index rows ``y`` (fp32, or
+    their bf16 copy: the _rows16 symbols) with ``args``, its workspace (sized from the launch's largest probe
+    and largest entry, allocated here on the caller's stream) and the stream."""
+    one, many, _, _, nws = _COARSE_KERNELS[kernel]
+    ws = ()
+    if nws:
+        wsb = int(getattr(_lib.load(), one + "_ws_bytes")(*(B, n0max, ngmax)[:nws]))
+        buf = torch.empty(wsb, device=y.device, dtype=torch.uint8)
+        ws = (_p(buf), wsb)
+    _lib.call((many if pairs else one) + ("_rows16" if y.dtype == torch.bfloat16 else ""), *args, *ws, _stream(y))
+
+
+# The checks that ``coarse_score*`` and ``coarse_pairs`` make alike; ``op`` names the caller in the message.
+def _check_index_tensors(op, named):
+    for name, t, dt in named:
         if not isinstance(t, torch.Tensor) or t.dtype != dt:
             raise _lib.FpmError("%s: %s must be a %s tensor (got %s)"
                                 % (op, name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
         if t.dim() != 1 or not t.is_contiguous():
             raise _lib.FpmError("%s: %s must be a contiguous 1-d tensor" % (op, name))
+
+
+def _check_coarse_rows(op, y, named):
     # y: the index's fp32 rows, or their bf16 copy (an index's y16: the rounding already done)
     if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.bfloat16) or y.dim() != 2 \
             or y.shape[1] != 768 or not y.is_contiguous():
         raise _lib.FpmError("%s: y must be contiguous fp32 or bf16 rows of 768 channels" % op)
-    for name, t in (("yp", yp), ("coef", coef)):
+    for name, t in named:
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
                 or not t.is_contiguous():
             raise _lib.FpmError("%s: %s must be contiguous fp32 rows of 768 channels" % (op, name))
-    for name, t in (("row_off", row_off), ("idx", idx), ("yp", yp), ("coef", coef), ("out", out)):
+
+
+def _check_on_device_of(op, y, named):
+    for name, t in named:
         if t is not None and t.device != y.device:
             raise _lib.FpmError("%s: %s is on %s, y on %s" % (op, name, t.device, y.device))
+
+
+def _host_copy(host, t):
+    return torch.as_tensor(host if host is not None else t.cpu()).view(-1).long()
+
+
+def _offsets_rise(off, rows):
+    """Host offsets ``off`` rise from 0 to the row count of ``rows``."""
+    return int(off[0]) == 0 and int(off[-1]) == rows.shape[0] and not bool((off[1:] < off[:-1]).any())
+
+
+def _check_iters_tau(op, iters, tau):
+    iters, tau = int(iters), float(tau)
+    if iters < 0 or not tau > 0:
+        raise _lib.FpmError("%s: iters >= 0 and tau > 0 required" % op)
+    return iters, tau
+
+
+def _host_dtype(op, dtype):
+    dtype = dtype or torch.float32
+    if dtype not in (torch.float32, torch.float64):
+        raise _lib.FpmError("%s: the host statement runs in float32 or float64" % op)
+    return dtype
+
+
+def _coarse_out(op, y, B, out, dtype, res=None):
+    """The (B,) result: ``res`` (the host statement's, CPU tensors) copied to ``out`` if there is one; else
+    ``out``, checked or allocated, for the kernel to fill."""
+    if res is not None:
+        if out is None:
+            return res
+        _shape(out, (B,), "%s out" % op)
+        return out.copy_(res)
+    if dtype is not None:
+        raise _lib.FpmError("%s: dtype selects the host statement's arithmetic; the kernel is fp32" % op)
+    if out is None:
+        out = torch.empty(B, device=y.device, dtype=torch.float32)
+    _shape(out, (B,), "%s out" % op)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.FpmError("%s: out must be contiguous fp32" % op)
+    return out
+
+
+def _coarse_score_op(kernel, y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype):
+    """``coarse_score``, ``coarse_score_wide`` and ``coarse_score_stream``: the host-side checks, then
+    ``kernel``'s one-probe entry point (``_COARSE_KERNELS``; its symbol without "fpm_" names the operation
+    in every message)."""
+    sym, _, bound, nmax, _ = _COARSE_KERNELS[kernel]
+    op = sym[len("fpm_"):]
+    _check_index_tensors(op, (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)))
+    _check_coarse_rows(op, y, (("yp", yp), ("coef", coef)))
+    _check_on_device_of(op, y, (("row_off", row_off), ("idx", idx), ("yp", yp), ("coef", coef), ("out", out)))
     G, B, n0 = int(row_off.numel()) - 1, int(idx.numel()), int(yp.shape[0])
     if G < 1:
         raise _lib.FpmError("%s: empty gallery" % op)
     _shape(coef, (B, 768), "%s coef" % op)
-    ih = torch.as_tensor(idx_host if idx_host is not None else idx.cpu()).view(-1).long()
-    oh = torch.as_tensor(row_off_host if row_off_host is not None else row_off.cpu()).view(-1).long()
+    ih, oh = _host_copy(idx_host, idx), _host_copy(row_off_host, row_off)
     if ih.numel() != B or oh.numel() != G + 1:
         raise _lib.FpmError("%s: host copies of idx / row_off do not match the device tensors" % op)
-    if int(oh[0]) != 0 or int(oh[-1]) != y.shape[0] or bool((oh[1:] < oh[:-1]).any()):
+    if not _offsets_rise(oh, y):
         raise _lib.FpmError("%s: row_off must rise from 0 to the %d rows of y" % (op, y.shape[0]))
     if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
         raise _lib.FpmError("%s: idx value outside [0, %d)" % (op, G))
@@ -608,28 +679,14 @@ def _coarse_score_op(op, bound, nmax, launch, y, row_off, idx, yp, coef, iters, 
         if int(ng.max()) > nmax or int(ng.min()) < 1:
             raise _lib.FpmError("%s: a selected entry has n_g = %d; the coarse pass takes 1 to "
                                 "%s = %d" % (op, int(ng.max()) if int(ng.max()) > nmax else int(ng.min()), bound, nmax))
-    iters, tau = int(iters), float(tau)
-    if iters < 0 or not tau > 0:
-        raise _lib.FpmError("%s: iters >= 0 and tau > 0 required" % op)
+    iters, tau = _check_iters_tau(op, iters, tau)
     if not y.is_cuda:
-        dtype = dtype or torch.float32
-        if dtype not in (torch.float32, torch.float64):
-            raise _lib.FpmError("%s: the host statement runs in float32 or float64" % op)
-        res = _coarse_score_host(y, oh, ih, yp, coef, iters, tau, dtype)
-        if out is not None:
-            _shape(out, (B,), "%s out" % op)
-            out.copy_(res)
-            return out
-        return res
-    if dtype is not None:
-        raise _lib.FpmError("%s: dtype selects the host statement's arithmetic; the kernel is fp32" % op)
-    if out is None:
-        out = torch.empty(B, device=y.device, dtype=torch.float32)
-    _shape(out, (B,), "%s out" % op)
-    if out.dtype != torch.float32 or not out.is_contiguous():
-        raise _lib.FpmError("%s: out must be contiguous fp32" % op)
+        dtype = _host_dtype(op, dtype)
+        return _coarse_out(op, y, B, out, dtype, _coarse_score_host(y, oh, ih, yp, coef, iters, tau, dtype))
+    out = _coarse_out(op, y, B, out, dtype)
     if B:
-        launch(G, B, n0, iters, tau, out, int(ng.max()))
+        _coarse_call(kernel, False, y, (_p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau, _p(out)),
+                     B, n0, int(ng.max()))
     return out
 
 
@@ -652,11 +709,7 @@ def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_ho
 
     CPU tensors take the plain-torch statement of the definition, in ``dtype`` arithmetic
     (torch.float32, the default, or torch.float64) on the same bf16-rounded operands."""
-    def launch(G, B, n0, iters, tau, out, ngmax):
-        _lib.call("fpm_coarse_score" + _rows16(y), _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau,
-                  _p(out), _stream(y))
-    return _coarse_score_op("coarse_score", "COARSE_NMAX", COARSE_NMAX, launch, y, row_off, idx, yp, coef, iters, tau,
-                            out, idx_host, row_off_host, dtype)
+    return _coarse_score_op("fused", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
 
 
 def coarse_score_wide(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
@@ -668,13 +721,7 @@ def coarse_score_wide(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, i
     Its sums run in another order than ``coarse_score``'s, so the two agree to rounding, not bit for
     bit, on boxes both take.  CPU tensors take the same plain-torch statement as ``coarse_score``
     (which has no size bound of its own)."""
-    def launch(G, B, n0, iters, tau, out, ngmax):
-        wsb = int(_lib.load().fpm_coarse_score_wide_ws_bytes(B))
-        ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
-        _lib.call("fpm_coarse_score_wide" + _rows16(y), _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters,
-                  tau, _p(out), _p(ws), wsb, _stream(y))
-    return _coarse_score_op("coarse_score_wide", "COARSE_WIDE_NMAX", COARSE_WIDE_NMAX, launch, y, row_off, idx, yp,
-                            coef, iters, tau, out, idx_host, row_off_host, dtype)
+    return _coarse_score_op("wide", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
 
 
 def coarse_score_stream(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
@@ -687,18 +734,7 @@ def coarse_score_stream(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None,
     place, the others on potentials.  It agrees with ``coarse_score`` and ``coarse_score_wide`` to
     rounding, not bit for bit, on boxes they take.  CPU tensors take the same plain-torch statement
     (which has no size bound of its own)."""
-    def launch(G, B, n0, iters, tau, out, ngmax):
-        wsb = int(_lib.load().fpm_coarse_score_stream_ws_bytes(B, n0, ngmax))
-        ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
-        _lib.call("fpm_coarse_score_stream" + _rows16(y), _p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef),
-                  iters, tau, _p(out), _p(ws), wsb, _stream(y))
-    return _coarse_score_op("coarse_score_stream", "COARSE_STREAM_NMAX", COARSE_STREAM_NMAX, launch, y, row_off, idx,
-                            yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
-
-
-_COARSE_PAIRS_KERNELS = {"fused": ("fpm_coarse_pairs", "COARSE_NMAX", COARSE_NMAX),
-                         "wide": ("fpm_coarse_pairs_wide", "COARSE_WIDE_NMAX", COARSE_WIDE_NMAX),
-                         "stream": ("fpm_coarse_pairs_stream", "COARSE_STREAM_NMAX", COARSE_STREAM_NMAX)}
+    return _coarse_score_op("stream", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
 
 
 def coarse_pairs(y, row_off, gidx, yq, qrow_off, qidx, coef, kernel="fused", iters=10, tau=0.01, out=None,
@@ -716,40 +752,26 @@ def coarse_pairs(y, row_off, gidx, yq, qrow_off, qidx, coef, kernel="fused", ite
     (``*_host``: host copies, so the checks need no device synchronisation).  CPU tensors take the
     plain-torch statement of ``coarse_score`` pair by pair, in ``dtype`` arithmetic."""
     op = "coarse_pairs"
-    if kernel not in _COARSE_PAIRS_KERNELS:
-        raise _lib.FpmError("%s: kernel must be one of %s" % (op, tuple(_COARSE_PAIRS_KERNELS)))
-    sym, bound, nmax = _COARSE_PAIRS_KERNELS[kernel]
-    for name, t, dt in (("gidx", gidx, torch.int32), ("qidx", qidx, torch.int32), ("row_off", row_off, torch.int64),
-                        ("qrow_off", qrow_off, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt:
-            raise _lib.FpmError("%s: %s must be a %s tensor (got %s)"
-                                % (op, name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
-        if t.dim() != 1 or not t.is_contiguous():
-            raise _lib.FpmError("%s: %s must be a contiguous 1-d tensor" % (op, name))
-    if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.bfloat16) or y.dim() != 2 \
-            or y.shape[1] != 768 or not y.is_contiguous():
-        raise _lib.FpmError("%s: y must be contiguous fp32 or bf16 rows of 768 channels" % op)
-    for name, t in (("yq", yq), ("coef", coef)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
-                or not t.is_contiguous():
-            raise _lib.FpmError("%s: %s must be contiguous fp32 rows of 768 channels" % (op, name))
-    for name, t in (("row_off", row_off), ("gidx", gidx), ("yq", yq), ("qrow_off", qrow_off), ("qidx", qidx),
-                    ("coef", coef), ("out", out)):
-        if t is not None and t.device != y.device:
-            raise _lib.FpmError("%s: %s is on %s, y on %s" % (op, name, t.device, y.device))
+    if kernel not in _COARSE_KERNELS:
+        raise _lib.FpmError("%s: kernel must be one of %s" % (op, COARSE_KERNELS))
+    _, _, bound, nmax, _ = _COARSE_KERNELS[kernel]
+    _check_index_tensors(op, (("gidx", gidx, torch.int32), ("qidx", qidx, torch.int32),
+                              ("row_off", row_off, torch.int64), ("qrow_off", qrow_off, torch.int64)))
+    _check_coarse_rows(op, y, (("yq", yq), ("coef", coef)))
+    _check_on_device_of(op, y, (("row_off", row_off), ("gidx", gidx), ("yq", yq), ("qrow_off", qrow_off),
+                                ("qidx", qidx), ("coef", coef), ("out", out)))
     G, Q, B = int(row_off.numel()) - 1, int(qrow_off.numel()) - 1, int(gidx.numel())
     if G < 1 or Q < 1:
         raise _lib.FpmError("%s: empty gallery or empty probe set" % op)
     if int(qidx.numel()) != B:
         raise _lib.FpmError("%s: gidx names %d pairs, qidx %d" % (op, B, int(qidx.numel())))
     _shape(coef, (B, 768), "%s coef" % op)
-    host = lambda h, t: torch.as_tensor(h if h is not None else t.cpu()).view(-1).long()
-    gh, qh, oh, qoh = host(gidx_host, gidx), host(qidx_host, qidx), host(row_off_host, row_off), host(qrow_off_host,
-                                                                                                      qrow_off)
+    gh, qh = _host_copy(gidx_host, gidx), _host_copy(qidx_host, qidx)
+    oh, qoh = _host_copy(row_off_host, row_off), _host_copy(qrow_off_host, qrow_off)
     if gh.numel() != B or qh.numel() != B or oh.numel() != G + 1 or qoh.numel() != Q + 1:
         raise _lib.FpmError("%s: host copies of gidx / qidx / row_off / qrow_off do not match the device tensors" % op)
     for name, o, rows in (("row_off", oh, y), ("qrow_off", qoh, yq)):
-        if int(o[0]) != 0 or int(o[-1]) != rows.shape[0] or bool((o[1:] < o[:-1]).any()):
+        if not _offsets_rise(o, rows):
             raise _lib.FpmError("%s: %s must rise from 0 to the %d rows of its store" % (op, name, rows.shape[0]))
     nqmax = ngmax = 0
     if B:
@@ -764,41 +786,20 @@ def coarse_pairs(y, row_off, gidx, yq, qrow_off, qidx, coef, kernel="fused", ite
                 raise _lib.FpmError("%s: a %s of %d keypoints; the %s coarse pass takes 1 to %s = %d"
                                     % (op, what, int(n.max()) if int(n.max()) > nmax else int(n.min()), kernel, bound,
                                        nmax))
-    iters, tau = int(iters), float(tau)
-    if iters < 0 or not tau > 0:
-        raise _lib.FpmError("%s: iters >= 0 and tau > 0 required" % op)
+    iters, tau = _check_iters_tau(op, iters, tau)
     if not y.is_cuda:
-        dtype = dtype or torch.float32
-        if dtype not in (torch.float32, torch.float64):
-            raise _lib.FpmError("%s: the host statement runs in float32 or float64" % op)
+        dtype = _host_dtype(op, dtype)
         res = torch.empty(B, dtype=dtype)
         for b in range(B):
             q = int(qh[b])
             res[b:b + 1] = _coarse_score_host(y, oh, gh[b:b + 1], yq[int(qoh[q]):int(qoh[q + 1])], coef[b:b + 1], iters,
                                               tau, dtype)
-        if out is not None:
-            _shape(out, (B,), "%s out" % op)
-            out.copy_(res)
-            return out
-        return res
-    if dtype is not None:
-        raise _lib.FpmError("%s: dtype selects the host statement's arithmetic; the kernel is fp32" % op)
-    if out is None:
-        out = torch.empty(B, device=y.device, dtype=torch.float32)
-    _shape(out, (B,), "%s out" % op)
-    if out.dtype != torch.float32 or not out.is_contiguous():
-        raise _lib.FpmError("%s: out must be contiguous fp32" % op)
-    if not B:
-        return out
-    args = (_p(y), _p(row_off), _p(gidx), G, B, _p(yq), _p(qrow_off), _p(qidx), Q, _p(coef), iters, tau, _p(out))
-    if kernel == "fused":
-        _lib.call(sym + _rows16(y), *args, _stream(y))
-        return out
-    # the stream kernel's slots: the largest probe and the largest entry of the launch, from whichever pairs
-    wsb = int(_lib.load().fpm_coarse_score_wide_ws_bytes(B) if kernel == "wide"
-              else _lib.load().fpm_coarse_score_stream_ws_bytes(B, nqmax, ngmax))
-    ws = torch.empty(wsb, device=y.device, dtype=torch.uint8)
-    _lib.call(sym + _rows16(y), *args, _p(ws), wsb, _stream(y))
+        return _coarse_out(op, y, B, out, dtype, res)
+    out = _coarse_out(op, y, B, out, dtype)
+    if B:
+        # the stream kernel's slots: the largest probe and the largest entry of the launch, from whichever pairs
+        _coarse_call(kernel, True, y, (_p(y), _p(row_off), _p(gidx), G, B, _p(yq), _p(qrow_off), _p(qidx), Q, _p(coef),
+                                       iters, tau, _p(out)), B, nqmax, ngmax)
     return out
 
 
