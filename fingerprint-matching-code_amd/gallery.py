@@ -30,6 +30,13 @@ pair-list instantiations (``ops.coarse_pairs``) score all pairs in bounded launc
 forward runs in groups of probes (``probe_groups``) on batches whose two sides are both gathered from
 cached rows (``pair_batch``).  Every score and output is the bits of the one-probe path's for the same
 pair and padded box.
+
+From keypoints (``Net.enroll_keypoints``, ``enroll_images``, ``probe_graphs``): ``enroll`` reads host
+graph dicts; ``_enroll_device`` takes padded keypoints and features where they are, builds each
+sub-batch's graphs on the device (``graphs.build_graph_batch``) and packs its ragged output rows -- fp32,
+bf16 or both -- into an index allocated once (``fpm_rows_pack``, one launch per sub-batch): every field
+equals ``enroll``'s on the same graphs.  Probe dicts of device tensors are staged by the query calls as
+they are (``_probe_tensors``).
 """
 import contextlib
 import hashlib
@@ -368,20 +375,224 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32"):
                         spline_weights_id(net), y16=y16, layout=layout)
 
 
+def _check_enroll(net, what, layout, sc_mode):
+    """The refusals of ``enroll`` that need no graphs -> the SplineConv arithmetic to enrol with."""
+    if net.training:
+        raise FpmError("%s: inference only (call net.eval())" % what)
+    if layout not in LAYOUTS:
+        raise FpmError("%s: layout must be one of %s" % (what, LAYOUTS))
+    sc_mode = sc_mode or ("f32" if net.dtype_mode == "f32" else "bf16")
+    if sc_mode not in ("f32", "bf16") or (sc_mode == "bf16" and net.dtype_mode != "bf16"):
+        raise FpmError("%s: sc_mode must be 'f32', or 'bf16' on a dtype='bf16' net" % what)
+    return sc_mode
+
+
+def _keypoint_args(what, P, n):
+    """Padded keypoints and their counts, as given (arrays or tensors, host or device) -> (P (G, nmax, 2)
+    fp32 tensor where it was, n host int64 (G,)); refuses an empty set and counts outside [1, nmax]."""
+    P = torch.as_tensor(P)
+    if P.dim() != 3 or P.shape[-1] != 2:
+        raise FpmError("%s: P must be (G, nmax, 2) padded keypoints (got %s)" % (what, tuple(P.shape)))
+    G, nmax = int(P.shape[0]), int(P.shape[1])
+    if G == 0:
+        raise FpmError("%s: empty gallery" % what)
+    n_h = torch.as_tensor(n).reshape(-1).cpu().to(torch.int64)
+    if n_h.numel() != G:
+        raise FpmError("%s: %d keypoint counts for %d graphs" % (what, n_h.numel(), G))
+    if int(n_h.min()) < 1 or int(n_h.max()) > nmax:
+        raise FpmError("%s: a graph of %d keypoints; counts must lie in [1, nmax = %d]"
+                       % (what, int(n_h.max()) if int(n_h.max()) > nmax else int(n_h.min()), nmax))
+    return P.to(torch.float32), n_h
+
+
+def _feature_args(what, x, w, G, nmax):
+    """Node and global features as given -> (x (G, nmax, 768) fp32 view, w (G, 512) fp32), where they were."""
+    x, w = torch.as_tensor(x), torch.as_tensor(w)
+    D = C.NODE_FEATURE_DIM
+    if tuple(x.shape) not in ((G, nmax, D), (G * nmax, D)):
+        raise FpmError("%s: x must be (%d, %d, %d) or (%d, %d) node features (got %s)"
+                       % (what, G, nmax, D, G * nmax, D, tuple(x.shape)))
+    if tuple(w.shape) != (G, C.GLOBAL_FEATURE_DIM):
+        raise FpmError("%s: w must be (%d, %d) global features (got %s)" % (what, G, C.GLOBAL_FEATURE_DIM, tuple(w.shape)))
+    return x.to(torch.float32).reshape(G, nmax, D), w.to(torch.float32)
+
+
+def _device_of(device, *ts):
+    """The device of a keypoint call: ``device``, else that of the first device tensor, else the current GPU."""
+    if device is not None:
+        return torch.device(device)
+    for t in ts:
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg):
+    """The enrolment loop of ``enroll_keypoints`` / ``enroll_images`` -> GalleryIndex.  ``feats(g0, g1, m)``:
+    the features of graphs [g0, g1) on the device, (x (g1 - g0, >= m, 768) fp32, w (g1 - g0, 512) fp32).  Per
+    sub-batch: trim to its own largest count m (the shapes ``enroll`` runs at), the graphs on the device
+    (``graphs.build_graph_batch``), the two SplineConv layers as ``enroll`` calls them, and one
+    ``ops.rows_pack`` from the padded output into the index's rows, allocated once before the loop."""
+    from . import graphs
+    G, nmax, D = int(n_h.numel()), int(P.shape[1]), C.NODE_FEATURE_DIM
+    step = max(1, int(batch))
+    wp = net.packed(dev)
+    f32 = sc_mode == "f32"
+    W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
+    code = ops.F32 if f32 else ops.BF16
+    row_off_h = torch.cat([torch.zeros(1, dtype=torch.int64), n_h.cumsum(0)])
+    total = int(row_off_h[-1])
+    srcs, dsts, pss, cnts = [], [], [], []
+    with torch.cuda.device(dev):
+        row_off = row_off_h.to(dev)
+        n_d = n_h.to(torch.int32).to(dev)
+        y = y16 = y_host = stage = None
+        if layout != "bf16+host":
+            y = torch.empty(total, D, device=dev, dtype=torch.float32)
+        if layout != "f32":
+            y16 = torch.empty(total, D, device=dev, dtype=torch.bfloat16)
+        if layout == "bf16+host":
+            y_host = _host_rows((total, D), dev)
+            # one sub-batch of fp32 rows on the device, reused: the copies to the host are ordered on the stream
+            stage = torch.empty(max(int(row_off_h[min(G, g0 + step)] - row_off_h[g0]) for g0 in range(0, G, step)), D,
+                                device=dev, dtype=torch.float32)
+        w_all = torch.empty(G, C.GLOBAL_FEATURE_DIM, device=dev, dtype=torch.float32)
+        for g0 in range(0, G, step):
+            g1 = min(G, g0 + step)
+            Bs, nsub, nv = g1 - g0, n_h[g0:g1], n_d[g0:g1]
+            m = int(nsub.max())
+            xs, ws = feats(g0, g1, m)
+            w_all[g0:g1] = ws
+            keep = torch.arange(m, device=dev)[None, :] < nv.view(-1, 1)
+            x0 = torch.where(keep[..., None], xs[:, :m], torch.zeros((), device=dev)).reshape(Bs * m, D)
+            gb = graphs.build_graph_batch(P[g0:g1, :m].to(dev).contiguous(), nv, stg=stg)
+            cnt = gb.edge_off_host[1:] - gb.edge_off_host[:-1]
+            nn_, E = Bs * m, int(gb.src.numel())
+            plan = ops.spline_plan(gb.src, gb.dst, gb.pseudo, nn_, m, int(cnt.max()))
+            x_op = x0 if f32 else ops.cast_bf16(x0)
+            yws = ops.spline_y_ws(code, E, nn_, dev)
+            h = torch.empty(nn_, D, device=dev, dtype=x_op.dtype)
+            ops.spline_conv(x_op, plan, E, nn_, m, nv, W0, wp["bias0"], yws, 0, out_t=h)
+            yb = torch.empty(nn_, D, device=dev, dtype=torch.float32)
+            ops.spline_conv(h, plan, E, nn_, m, nv, W1, wp["bias1"], yws, 1, xres=x0, out_f=yb)
+            # padded -> ragged rows (and their bf16 copy) in one pass, into their place in the index
+            r0, r1 = int(row_off_h[g0]), int(row_off_h[g1])
+            ops.rows_pack(yb, nv, m, row_off[g0:g1 + 1] - r0, out32=stage if y is None else y[r0:r1],
+                          out16=None if y16 is None else y16[r0:r1], n_host=nsub,
+                          out_off_host=row_off_h[g0:g1 + 1] - r0)
+            if y_host is not None:
+                y_host[r0:r1].copy_(stage[:r1 - r0], non_blocking=True)
+            srcs.append(gb.src % m)                          # edges back to graph-local ids
+            dsts.append(gb.dst % m)
+            pss.append(gb.pseudo)
+            cnts.append(cnt)
+        Pk = P if P.device == dev else P.cpu()
+        keep = torch.arange(nmax, device=Pk.device)[None, :] < n_h.to(Pk.device).view(-1, 1)
+        Pr = Pk[keep].to(dev)
+        edge_off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cat(cnts).cumsum(0)])
+        if y_host is not None:
+            torch.cuda.current_stream(dev).synchronize()   # the host rows are complete before they are read
+        return GalleryIndex(y if y_host is None else y_host, row_off, n_h.to(torch.int32), torch.cat(srcs),
+                            torch.cat(dsts), torch.cat(pss), edge_off, w_all, Pr, sc_mode, net._pack_gen,
+                            spline_weights_id(net), y16=y16, layout=layout)
+
+
+def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri"):
+    """``Net.enroll_keypoints``: see there."""
+    what = "enroll_keypoints"
+    sc_mode = _check_enroll(net, what, layout, sc_mode)
+    P, n_h = _keypoint_args(what, P, n)
+    x, w = _feature_args(what, x, w, int(P.shape[0]), int(P.shape[1]))
+    dev = _device_of(device, P, x)
+
+    def feats(g0, g1, m):
+        return x[g0:g1, :m].to(dev), w[g0:g1].to(dev)
+
+    return _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg)
+
+
+def _check_images(what, images, G):
+    images = torch.as_tensor(images)
+    if images.dim() != 4 or int(images.shape[0]) != G:
+        raise FpmError("%s: images must be (%d, 3, H, W), one per graph (got %s)" % (what, G, tuple(images.shape)))
+    return images
+
+
+def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri"):
+    """``Net.enroll_images``: see there."""
+    what = "enroll_images"
+    net._need_backbone()
+    sc_mode = _check_enroll(net, what, layout, sc_mode)
+    P, n_h = _keypoint_args(what, P, n)
+    images = _check_images(what, images, int(P.shape[0]))
+    dev = _device_of(device, P, images)
+    nmax = int(P.shape[1])
+
+    def feats(g0, g1, m):
+        # one side of the pair front end, a sub-batch at a time: the backbone's memory is bounded by ``batch``
+        xs, gs = net.image_features([images[g0:g1]], [P[g0:g1]], [n_h[g0:g1]])
+        return xs[0].view(g1 - g0, nmax, C.NODE_FEATURE_DIM), gs[0]
+
+    return _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg)
+
+
+def probe_graphs(net, P, n, x=None, w=None, images=None, device=None, stg="tri"):
+    """``Net.probe_graphs``: see there."""
+    from . import graphs
+    what = "probe_graphs"
+    if (images is None) == (x is None and w is None) or (x is None) != (w is None):
+        raise FpmError("%s: give the features x and w, or images (not both)" % what)
+    if images is not None:
+        net._need_backbone()
+    P, n_h = _keypoint_args(what, P, n)
+    G, nmax = int(P.shape[0]), int(P.shape[1])
+    if images is None:
+        x, w = _feature_args(what, x, w, G, nmax)
+    else:
+        images = _check_images(what, images, G)
+    dev = _device_of(device, P, x, images)
+    with torch.cuda.device(dev):
+        if images is not None:
+            xs, gs = net.image_features([images], [P], [n_h])
+            x, w = xs[0].view(G, nmax, C.NODE_FEATURE_DIM), gs[0]
+        x, w, P = x.to(dev), w.to(dev), P.to(dev).contiguous()
+        gb = graphs.build_graph_batch(P, n_h.to(torch.int32).to(dev), stg=stg)
+        ei = torch.stack([gb.src % nmax, gb.dst % nmax])           # graph-local ids
+        eo = gb.edge_off_host.tolist()
+    return [dict(n=int(k), x=x[g, :k], w=w[g], edge_index=ei[:, eo[g]:eo[g + 1]], pseudo=gb.pseudo[eo[g]:eo[g + 1]],
+                 P=P[g, :k]) for g, k in enumerate(n_h.tolist())]
+
+
+_PROBE_DTYPES = {"x": (torch.float32, np.float32), "edge_index": (torch.int32, np.int32),
+                 "pseudo": (torch.float32, np.float32), "w": (torch.float32, np.float32)}
+
+
+def _probe_tensors(probe, dev):
+    """A probe graph dict's fields staged on ``dev`` -> (n, x (n, 768) fp32, edge_index (2, E) int32, pseudo
+    (E, 2) fp32, w (512,) fp32).  The values are numpy arrays (``synth.make_graph``), host tensors or device
+    tensors (``Net.probe_graphs``); a tensor on ``dev`` is taken as it is: no host round trip."""
+    out = []
+    for key, (dt, npdt) in _PROBE_DTYPES.items():
+        v = probe[key]
+        if not isinstance(v, torch.Tensor):
+            v = torch.from_numpy(np.ascontiguousarray(np.asarray(v).astype(npdt, copy=False)))
+        out.append(v.to(device=dev, dtype=dt))
+    x, ei, ps, w = out
+    return int(probe["n"]), x.contiguous(), ei, ps.reshape(-1, 2), w.reshape(-1)
+
+
 def probe_batch(probe, index, select=None):
     """The probe x gallery batch of one probe graph over ``index`` -> (_CachedBatch, sel host int64)."""
     dev = index.device
     sel, f = index._selection(select)
-    B, n0 = int(sel.numel()), int(probe["n"])
-    x0 = torch.from_numpy(np.ascontiguousarray(np.asarray(probe["x"], dtype=np.float32))).to(dev)
-    ei = torch.from_numpy(np.asarray(probe["edge_index"]).astype(np.int32)).to(dev)
-    ps = torch.from_numpy(np.asarray(probe["pseudo"], dtype=np.float32).reshape(-1, 2)).to(dev)
+    n0, x0, ei, ps, w0 = _probe_tensors(probe, dev)
+    B = int(sel.numel())
     e0 = int(ei.shape[1])
     shift = (torch.arange(B, device=dev, dtype=torch.int32) * n0).view(B, 1)
-    src0 = (ei[0].view(1, e0) + shift).reshape(-1).contiguous()
-    dst0 = (ei[1].view(1, e0) + shift).reshape(-1).contiguous()
-    ps0 = ps.view(1, e0, 2).expand(B, e0, 2).reshape(-1, 2).contiguous()
-    w0 = torch.from_numpy(np.asarray(probe["w"], dtype=np.float32)).to(dev).view(1, -1).expand(B, -1).contiguous()
+    src0 = (ei[0].reshape(1, e0) + shift).reshape(-1).contiguous()
+    dst0 = (ei[1].reshape(1, e0) + shift).reshape(-1).contiguous()
+    ps0 = ps.reshape(1, e0, 2).expand(B, e0, 2).reshape(-1, 2).contiguous()
+    w0 = w0.reshape(1, -1).expand(B, -1).contiguous()
     eo0 = torch.arange(B + 1, dtype=torch.int64) * e0
     bt = _CachedBatch(B, np.full(B, n0, np.int32), f["n"], [x0, x0.new_empty(0, C.NODE_FEATURE_DIM)], [w0, f["w"]],
                       [src0, f["src"]], [dst0, f["dst"]], [ps0, f["pseudo"]], dev, nmax=[n0, f["nmax"]],
@@ -421,16 +632,15 @@ class _ProbeSide:
 
     def __init__(self, probe, index):
         dev = index.device
-        n0 = int(probe["n"])
-        ei = torch.from_numpy(np.asarray(probe["edge_index"]).astype(np.int32)).to(dev)
+        n0, x0, ei, ps, w0 = _probe_tensors(probe, dev)
         self.device, self.sc_mode = dev, index.sc_mode
         self.nmax = [n0, n0]
-        self.x = [torch.from_numpy(np.ascontiguousarray(np.asarray(probe["x"], dtype=np.float32))).to(dev)]
+        self.x = [x0]
         self.src, self.dst = [ei[0].contiguous()], [ei[1].contiguous()]
-        self.pseudo = [torch.from_numpy(np.asarray(probe["pseudo"], dtype=np.float32).reshape(-1, 2)).to(dev)]
+        self.pseudo = [ps.contiguous()]
         self.edge_off = [torch.tensor([0, int(ei.shape[1])], dtype=torch.int64)]
         self.n = [torch.tensor([n0], dtype=torch.int32, device=dev)]
-        self.w0 = torch.from_numpy(np.asarray(probe["w"], dtype=np.float32)).to(dev).view(1, -1)
+        self.w0 = w0.reshape(1, -1)
 
 
 def _select_host(index, select, what):

@@ -1486,6 +1486,40 @@ class Net(nn.Module):
         from . import gallery
         return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch, layout=layout)
 
+    def enroll_keypoints(self, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri"):
+        """``enroll`` from keypoints and features, on the device: no host graph dicts.  P: (G, nmax, 2)
+        fp32 padded keypoints, n: (G,) counts in [1, nmax], x: (G, nmax, 768) or (G * nmax, 768) fp32
+        node features (padding rows are ignored), w: (G, 512) global features; tensors or arrays, host
+        or device (``device``: where to enrol; default the inputs' GPU, else the current one).  Per
+        sub-batch of ``batch`` graphs, trimmed to its own largest count: the graphs by
+        ``graphs.build_graph_batch`` (``stg``: "tri" Delaunay as the data loader builds them, "fc",
+        "near"), the two SplineConv layers as ``enroll`` runs them, and one ``ops.rows_pack`` launch that
+        writes the sub-batch's ragged rows -- fp32, bf16 or both, by ``layout`` -- into their place in
+        the index, whose rows are allocated once: the device peak is the index plus one sub-batch.
+        -> ``GalleryIndex``, every field equal to ``enroll`` on the same graphs as host dicts with the
+        same ``batch``.  ``sc_mode`` / ``layout``: as ``enroll``."""
+        from . import gallery
+        return gallery.enroll_keypoints(self, P, n, x, w, device=device, sc_mode=sc_mode, batch=batch, layout=layout,
+                                        stg=stg)
+
+    def enroll_images(self, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri"):
+        """``enroll_keypoints`` from images (needs ``Net(backbone=True)``): images (G, 3, H, W), P and n as
+        there.  Per sub-batch ``image_features`` (backbone + feature_align, one side) makes x and w, so
+        the backbone's memory is bounded by ``batch``."""
+        from . import gallery
+        return gallery.enroll_images(self, images, P, n, device=device, sc_mode=sc_mode, batch=batch, layout=layout,
+                                     stg=stg)
+
+    def probe_graphs(self, P, n, x=None, w=None, images=None, device=None, stg="tri"):
+        """Probe graphs for ``identify`` / ``coarse_scores`` from keypoints, on the device -> a list of
+        graph dicts (n int, x (n, 768), w (512,), edge_index (2, E) int32 graph-local, pseudo (E, 2),
+        P (n, 2)) whose values are device tensor views: the query calls stage them without a host round
+        trip.  Inputs as ``enroll_keypoints``; the features are ``x`` and ``w``, or come from ``images``
+        (``Net(backbone=True)``).  Many probes at once: enrol them as a probe set instead
+        (``enroll_keypoints`` / ``enroll_images``, then ``identify_many``)."""
+        from . import gallery
+        return gallery.probe_graphs(self, P, n, x=x, w=w, images=images, device=device, stg=stg)
+
     def coarse_scores(self, probes, index, select=None, coarse="fused"):
         """The coarse first pass of a shortlisted identification: for each probe graph (one dict, or a
         list) one cheap score per gallery entry of ``select`` (default all) -> (P, len(select)) fp32 on
@@ -1591,14 +1625,17 @@ class Net(nn.Module):
                                      select=select, score=score, coarse=coarse, chunks=chunks,
                                      group_pairs=group_pairs, exclude_self=exclude_self)
 
+    def _need_backbone(self):
+        if not hasattr(self, "node_layers"):
+            raise NotImplementedError("image input needs the backbone: this Net was built with backbone=False "
+                                      "(pass data_dict['node_features'] / ['global_features'] instead)")
+
     def image_features(self, images, Ps, ns, dev=None):
         """ngm.py:226-248 on the device: per side, node_layers/edge_layers (ResNet-18 convolutions
         on MIOpen, channels_last; bf16 autocast in the bf16 mode), then one HIP kernel set for
         global max-pool + channel L2-norm + bilinear feature_align + [U || F] concat.
         Returns (node feature rows 2 x (B*nmax, 768) with zero padding rows, globals 2 x (B, 512))."""
-        if not hasattr(self, "node_layers"):
-            raise NotImplementedError("image input needs the backbone: this Net was built with backbone=False "
-                                      "(pass data_dict['node_features'] / ['global_features'] instead)")
+        self._need_backbone()
         dev = dev or torch.device("cuda", torch.cuda.current_device())
         if self._backbone_dev != dev:
             for m in (self.node_layers, self.edge_layers):

@@ -3,8 +3,8 @@
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
 no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``,
-``coarse_score`` / ``coarse_pairs`` and ``rows_fetch`` alone keep a plain-torch host path for CPU tensors: the statements
-of the ordering, of the coarse score and of the ragged copy, which the tests hold the kernels to).
+``coarse_score`` / ``coarse_pairs``, ``rows_fetch`` and ``rows_pack`` alone keep a plain-torch host path for CPU tensors:
+the statements of the ordering, of the coarse score and of the ragged copies, which the tests hold the kernels to).
 """
 import ctypes
 
@@ -430,6 +430,74 @@ def rows_fetch(src, row_off, idx, out, out_off, idx_host=None, row_off_host=None
         _lib.call("fpm_rows_fetch", _p(src), int(src.shape[0]), _p(row_off), _p(idx), G, M, int(ng.max()), _p(out),
                   int(out.shape[0]), _p(out_off), _stream(out))
     return out
+
+
+def rows_pack(src, n, nmax, out_off, out32=None, out16=None, n_host=None, out_off_host=None):
+    """Ragged row pack (fpm_rows_pack), the inverse of the padding: ``src`` ((B * nmax, 768) fp32 padded
+    rows, graph b at rows [b * nmax, b * nmax + n[b]); n int32 [B]) packed into ``out32`` (fp32,
+    unchanged) and / or ``out16`` (bf16, the bits of ``cast_bf16``), graph b at rows
+    [out_off[b], out_off[b + 1]) of either (out_off int64 [B + 1], rising by n; it need not start at 0,
+    so a sub-batch packs into its place in a whole index) -> (out32, out16).  One launch, one read of
+    the source; padding rows are not read, rows outside the offsets are not written.
+
+    Everything lives on one device.  Checked on the host before anything is launched: dtypes,
+    contiguity, devices, 0 <= n[b] <= nmax, the offsets, both outputs large enough (``n_host`` /
+    ``out_off_host``: host copies, so the check needs no device synchronisation; without them the
+    device tensors are copied back).  All-CPU tensors take the torch statement of the copy and the
+    rounding."""
+    for name, t, dt in (("n", n, torch.int32), ("out_off", out_off, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise _lib.FpmError("rows_pack: %s must be a %s tensor (got %s)"
+                                % (name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise _lib.FpmError("rows_pack: %s must be a contiguous 1-d tensor" % name)
+    if out32 is None and out16 is None:
+        raise _lib.FpmError("rows_pack: give out32, out16 or both")
+    for name, t, dt in (("src", src, torch.float32), ("out32", out32, torch.float32), ("out16", out16, torch.bfloat16)):
+        if t is None and name != "src":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 768 \
+                or not t.is_contiguous():
+            raise _lib.FpmError("rows_pack: %s must be contiguous %s rows of 768 channels"
+                                % (name, "bf16" if dt == torch.bfloat16 else "fp32"))
+    for name, t in (("n", n), ("out_off", out_off), ("out32", out32), ("out16", out16)):
+        if t is not None and t.device != src.device:
+            raise _lib.FpmError("rows_pack: %s is on %s, src on %s" % (name, t.device, src.device))
+    B, nmax = int(n.numel()), int(nmax)
+    if nmax < 0:
+        raise _lib.FpmError("rows_pack: negative nmax")
+    if B > 65535:
+        raise _lib.FpmError("rows_pack: at most 65535 graphs per call")
+    if src.shape[0] != B * nmax:
+        raise _lib.FpmError("rows_pack: src holds %d rows, %d graphs of nmax = %d have %d"
+                            % (src.shape[0], B, nmax, B * nmax))
+    if out_off.numel() != B + 1:
+        raise _lib.FpmError("rows_pack: out_off must hold %d offsets (got %d)" % (B + 1, out_off.numel()))
+    nh = torch.as_tensor(n_host if n_host is not None else n.cpu()).view(-1).long()
+    oh = torch.as_tensor(out_off_host if out_off_host is not None else out_off.cpu()).view(-1).long()
+    if nh.numel() != B or oh.numel() != B + 1:
+        raise _lib.FpmError("rows_pack: host copies of n / out_off do not match the device tensors")
+    if B and (int(nh.min()) < 0 or int(nh.max()) > nmax):
+        raise _lib.FpmError("rows_pack: a graph has n = %d outside [0, nmax = %d]"
+                            % (int(nh.max()) if int(nh.max()) > nmax else int(nh.min()), nmax))
+    if int(oh[0]) < 0 or not torch.equal(oh[1:] - oh[:-1], nh):
+        raise _lib.FpmError("rows_pack: out_off must rise from a non-negative offset by the graphs' row counts n")
+    for name, t in (("out32", out32), ("out16", out16)):
+        if t is not None and t.shape[0] < int(oh[-1]):
+            raise _lib.FpmError("rows_pack: %s holds %d rows, the offsets end at %d" % (name, t.shape[0], int(oh[-1])))
+    if not src.is_cuda:
+        if B and int(nh.sum()):
+            rows = torch.cat([src[b * nmax:b * nmax + k] for b, k in enumerate(nh.tolist())])
+            if out32 is not None:
+                out32[int(oh[0]):int(oh[-1])] = rows
+            if out16 is not None:
+                out16[int(oh[0]):int(oh[-1])] = rows.to(torch.bfloat16)
+        return out32, out16
+    if B and nmax and int(nh.sum()):
+        out_rows = min(t.shape[0] for t in (out32, out16) if t is not None)
+        _lib.call("fpm_rows_pack", _p(src), int(src.shape[0]), _p(n), B, nmax, _p(out_off), _p(out32), _p(out16),
+                  int(out_rows), _stream(src))
+    return out32, out16
 
 
 def rank_key(scores):

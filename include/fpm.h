@@ -262,6 +262,16 @@ int fpm_rows_gather_scale(int dtype, const float* y, const long* row_off, const 
  * written outside out). */
 int fpm_rows_fetch(const float* src, long src_rows, const long* row_off, const int* idx, int G, int M, int nmax,
                    float* out, long out_rows, const long* out_off, void* stream);
+/* Ragged row pack (enrolment: a sub-batch's padded SplineConv output rows into the index, one pass).
+ * src: src_rows x 768 fp32 (device), src_rows >= B * nmax, graph b at rows [b * nmax, b * nmax + n[b])
+ * (n: B int32, device, 0 <= n[b] <= nmax; B <= 65535); graph b's rows go to rows
+ * [out_off[b], out_off[b + 1]) (out_off: B + 1 int64, device, out_off[b + 1] - out_off[b] = n[b]) of
+ * out32 (out_rows x 768 fp32, unchanged) and of out16 (out_rows x 768 bf16, rounded as fpm_cast_bf16
+ * rounds); either may be NULL, not both.  src, out32 and out16 16-byte aligned.  The caller checks n
+ * and the offsets; a graph that violates them is not copied (nothing is read outside src or written
+ * outside the outputs).  Padding rows are not read; n[b] = 0 writes nothing. */
+int fpm_rows_pack(const float* src, long src_rows, const int* n, int B, int nmax, const long* out_off, float* out32,
+                  void* out16, long out_rows, void* stream);
 /* vertex_attr_to_edge_attr (spline_conv.py:73-81): out[e] = x[src[e]] - x[dst[e]] */
 int fpm_edge_diff(const float* x, const int* src, const int* dst, long E, int D, float* out, void* stream);
 /* same, written into a padded per-pair layout and scaled: out[row[e]] = (x[src]-x[dst]) o c[pair[e]]
