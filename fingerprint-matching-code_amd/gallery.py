@@ -37,6 +37,13 @@ sub-batch's graphs on the device (``graphs.build_graph_batch``) and packs its ra
 bf16 or both -- into an index allocated once (``fpm_rows_pack``, one launch per sub-batch): every field
 equals ``enroll``'s on the same graphs.  Probe dicts of device tensors are staged by the query calls as
 they are (``_probe_tensors``).
+
+Subjects (``enroll*(subjects=...)``, ``GalleryIndex.set_subjects``, ``identify`` / ``identify_many(by="subject")``):
+an entry is one impression, a subject (a finger) has several.  The index keeps one label per entry and
+makes a selection's CSR group tables on the host (``subject_groups``); the queries fuse scores per subject
+on the device (``ops.group_scores``: max, or a mean in a fixed order) between the coarse scores and
+``rank_select`` -- the shortlist then counts subjects -- and between the exact scores and ``rank_topk``.
+The exact forward still runs over plain entry lists, so every per-pair output is the entry-level call's.
 """
 import contextlib
 import hashlib
@@ -85,13 +92,16 @@ class GalleryIndex:
       edge_off  (G + 1,) int64      edge offsets per graph (host)
       w         (G, 512) fp32       global features (device)
       P         (sum n, 2) fp32     keypoints, or None when the graphs carry none (device)
+      subject   (G,) int64 or None  the subject label (>= 0) of each entry (host; ``set_subjects``): the
+                                    impressions of one finger share a label.  ``subject_groups`` makes a
+                                    selection's CSR group tables, which ``identify(by="subject")`` fuses by
       sc_mode   "f32" | "bf16"      the SplineConv arithmetic that produced y
       _pack_gen, weights_id         the enrolling net's weight-pack generation and a digest of its
                                     SplineConv weights (``Net.identify`` refuses other weights)
     """
 
     def __init__(self, y, row_off, n, src, dst, pseudo, edge_off, w, P, sc_mode, pack_gen, weights_id, y16=None,
-                 layout="f32"):
+                 layout="f32", subject=None):
         if sc_mode not in ("f32", "bf16"):
             raise FpmError("GalleryIndex: sc_mode must be 'f32' or 'bf16'")
         if layout not in LAYOUTS:
@@ -115,12 +125,16 @@ class GalleryIndex:
         self._pack_gen = int(pack_gen)
         self.weights_id = str(weights_id)
         self._sel = None            # the last selection's side-1 batch data (_selection)
+        self.subject = None         # (G,) int64 host subject labels (set_subjects), or None
+        self._groups = None         # the last selection's group tables (subject_groups)
         G = self.G
         if (row_off.dtype != torch.int64 or self.row_off_host.numel() != G + 1 or self.edge_off.numel() != G + 1
                 or int(self.row_off_host[-1]) != y.shape[0] or int(self.edge_off[-1]) != src.numel()
                 or not torch.equal(self.row_off_host[1:] - self.row_off_host[:-1], self.n.long())
                 or tuple(w.shape) != (G, C.GLOBAL_FEATURE_DIM) or y.dtype != torch.float32):
             raise FpmError("GalleryIndex: inconsistent fields")
+        if subject is not None:
+            self.set_subjects(subject)
 
     @property
     def G(self):
@@ -135,6 +149,8 @@ class GalleryIndex:
         1.5 KB in "bf16+host"), plus edges and global features."""
         ts = [self.row_off, self.src, self.dst, self.pseudo, self.w] + ([] if self.P is None else [self.P])
         ts += ([] if self.layout == "bf16+host" else [self.y]) + ([] if self.y16 is None else [self.y16])
+        if self._groups is not None:
+            ts += [self._groups[1][k] for k in ("labels_d", "off_d", "pos_d")]
         return sum(t.numel() * t.element_size() for t in ts)
 
     def host_nbytes(self):
@@ -151,6 +167,8 @@ class GalleryIndex:
             d["P"] = self.P.cpu()
         if self.layout != "f32":
             d.update(format=FORMAT_LAYOUTS, layout=self.layout, y16=self.y16.cpu())
+        if self.subject is not None:
+            d["subject"] = self.subject
         torch.save(d, path)
 
     @staticmethod
@@ -167,7 +185,40 @@ class GalleryIndex:
             y = mv("y")
         return GalleryIndex(y, mv("row_off"), d["n"], mv("src"), mv("dst"), mv("pseudo"), d["edge_off"], mv("w"),
                             mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"],
-                            y16=mv("y16") if layout != "f32" else None, layout=layout)
+                            y16=mv("y16") if layout != "f32" else None, layout=layout, subject=d.get("subject"))
+
+    def set_subjects(self, labels):
+        """Label (or relabel) the entries: ``labels`` (G,) integers >= 0, the subject of each entry (the
+        impressions of one finger share a label).  Kept as a host int64 tensor (``subject``); the
+        cached group tables are dropped.  None removes the labels."""
+        self.subject = None if labels is None else _check_subjects("set_subjects", labels, self.G)
+        self._groups = None
+
+    def subject_groups(self, select=None):
+        """The group tables of the entries ``select`` (None: all) by subject -> dict:
+          labels  (S,) int64 host     the distinct labels of the selection, ascending (``labels_d``: device)
+          off     (S + 1,) int32 host group s is pos[off[s]:off[s + 1]]          (``off_d``: device)
+          pos     (Gs,) int32 host    positions into the selection, ascending inside a group (``pos_d``)
+          group   (Gs,) int64 host    the group number of each position of the selection
+        Built on the host with a stable sort of the selection's labels; independent of the probe, so the
+        last selection's tables are kept for the next query (as ``_selection`` keeps its batch data)."""
+        if self.subject is None:
+            raise FpmError("subject_groups: the index has no subject labels (set_subjects, or enroll(subjects=...))")
+        sel = _select_host(self, select, "subject_groups")
+        if self._groups is not None and torch.equal(self._groups[0], sel):
+            return self._groups[1]
+        lab = self.subject[sel]
+        order = torch.argsort(lab, stable=True)
+        labels, cnt = torch.unique_consecutive(lab[order], return_counts=True)
+        off = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)]).to(torch.int32)
+        pos = order.to(torch.int32)
+        group = torch.empty_like(order)
+        group[order] = torch.repeat_interleave(torch.arange(int(labels.numel())), cnt)
+        dev = self.device
+        t = dict(labels=labels, off=off, pos=pos, group=group, labels_d=labels.to(dev), off_d=off.to(dev),
+                 pos_d=pos.to(dev))
+        self._groups = (sel, t)
+        return t
 
     def fetch(self, sel):
         """The fp32 rows of the entries ``sel`` (host int64, in that order) of a "bf16+host" index, copied
@@ -246,6 +297,19 @@ class GalleryIndex:
         return f
 
 
+def _check_subjects(what, labels, G):
+    """Subject labels as given -> host int64 (G,), a copy: one integer >= 0 per entry."""
+    t = torch.as_tensor(labels)
+    if t.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+        raise FpmError("%s: subject labels must be integers (got %s)" % (what, t.dtype))
+    if t.dim() != 1 or int(t.numel()) != int(G):
+        raise FpmError("%s: %s subject labels for %d entries (one label per entry)" % (what, tuple(t.shape), G))
+    t = t.detach().cpu().to(torch.int64).clone()
+    if int(G) and int(t.min()) < 0:
+        raise FpmError("%s: a negative subject label (%d)" % (what, int(t.min())))
+    return t
+
+
 class _CachedBatch(DeviceBatch):
     """A batch one or both of whose sides live in a GalleryIndex: laid out like ``DeviceBatch.from_pairs``,
     except that a cached side stages no node features: ``cached`` (a pair of model._CachedSide, None for a
@@ -303,12 +367,14 @@ def spline_weights_id(net):
     return net._sc_weights_id[1]
 
 
-def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32"):
+def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None):
     """``Net.enroll``: the two SplineConv layers over ``graphs`` (dicts as ``fpm.synth.make_graph``
     returns: n, x, w, edge_index, pseudo, optionally P) in sub-batches of ``batch`` graphs -> GalleryIndex.
     ``layout`` (LAYOUTS): where the rows are kept.  The bf16 copy is rounded per sub-batch on the device
     (``ops.cast_bf16``: the coarse kernels' own rounding); for "bf16+host" each sub-batch's fp32 rows go
-    straight to the pinned host tensor, so the device holds the bf16 rows plus one sub-batch at most."""
+    straight to the pinned host tensor, so the device holds the bf16 rows plus one sub-batch at most.
+    ``subjects``: one integer label >= 0 per graph (``GalleryIndex.subject``), checked before any GPU work;
+    every other field of the index is the same with or without it."""
     if net.training:
         raise FpmError("enroll: inference only (call net.eval())")
     if layout not in LAYOUTS:
@@ -320,6 +386,8 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32"):
     graphs = list(graphs)
     if not graphs:
         raise FpmError("enroll: empty gallery")
+    if subjects is not None:
+        subjects = _check_subjects("enroll", subjects, len(graphs))
     wp = net.packed(dev)
     f32 = sc_mode == "f32"
     W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
@@ -372,7 +440,7 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32"):
         torch.cuda.current_stream(dev).synchronize()       # the host rows are complete before they are read
     return GalleryIndex(torch.cat(ys) if y_host is None else y_host, row_off.to(dev), n_all, torch.cat(srcs),
                         torch.cat(dsts), torch.cat(pss), edge_off, w, P, sc_mode, net._pack_gen,
-                        spline_weights_id(net), y16=y16, layout=layout)
+                        spline_weights_id(net), y16=y16, layout=layout, subject=subjects)
 
 
 def _check_enroll(net, what, layout, sc_mode):
@@ -427,7 +495,7 @@ def _device_of(device, *ts):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg):
+def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subjects=None):
     """The enrolment loop of ``enroll_keypoints`` / ``enroll_images`` -> GalleryIndex.  ``feats(g0, g1, m)``:
     the features of graphs [g0, g1) on the device, (x (g1 - g0, >= m, 768) fp32, w (g1 - g0, 512) fp32).  Per
     sub-batch: trim to its own largest count m (the shapes ``enroll`` runs at), the graphs on the device
@@ -494,13 +562,15 @@ def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg):
             torch.cuda.current_stream(dev).synchronize()   # the host rows are complete before they are read
         return GalleryIndex(y if y_host is None else y_host, row_off, n_h.to(torch.int32), torch.cat(srcs),
                             torch.cat(dsts), torch.cat(pss), edge_off, w_all, Pr, sc_mode, net._pack_gen,
-                            spline_weights_id(net), y16=y16, layout=layout)
+                            spline_weights_id(net), y16=y16, layout=layout, subject=subjects)
 
 
-def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri"):
+def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri", subjects=None):
     """``Net.enroll_keypoints``: see there."""
     what = "enroll_keypoints"
     sc_mode = _check_enroll(net, what, layout, sc_mode)
+    if subjects is not None:
+        subjects = _check_subjects(what, subjects, int(torch.as_tensor(P).shape[0]))
     P, n_h = _keypoint_args(what, P, n)
     x, w = _feature_args(what, x, w, int(P.shape[0]), int(P.shape[1]))
     dev = _device_of(device, P, x)
@@ -508,7 +578,7 @@ def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layo
     def feats(g0, g1, m):
         return x[g0:g1, :m].to(dev), w[g0:g1].to(dev)
 
-    return _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg)
+    return _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subjects)
 
 
 def _check_images(what, images, G):
@@ -518,11 +588,13 @@ def _check_images(what, images, G):
     return images
 
 
-def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri"):
+def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri", subjects=None):
     """``Net.enroll_images``: see there."""
     what = "enroll_images"
     net._need_backbone()
     sc_mode = _check_enroll(net, what, layout, sc_mode)
+    if subjects is not None:
+        subjects = _check_subjects(what, subjects, int(torch.as_tensor(P).shape[0]))
     P, n_h = _keypoint_args(what, P, n)
     images = _check_images(what, images, int(P.shape[0]))
     dev = _device_of(device, P, images)
@@ -533,7 +605,7 @@ def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layou
         xs, gs = net.image_features([images[g0:g1]], [P[g0:g1]], [n_h[g0:g1]])
         return xs[0].view(g1 - g0, nmax, C.NODE_FEATURE_DIM), gs[0]
 
-    return _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg)
+    return _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subjects)
 
 
 def probe_graphs(net, P, n, x=None, w=None, images=None, device=None, stg="tri"):
@@ -780,10 +852,88 @@ def coarse_scores(net, probes, index, select=None, chunk=COARSE_CHUNK, coarse="f
     return out
 
 
+IMPRESSIONS = ("all", "best")
+
+
+def _check_by(what, index, by, fuse, impressions, shortlist):
+    """The refusals of the subject-level arguments (before any GPU work) -> whether ``by`` is "subject"."""
+    if by not in (None, "subject"):
+        raise FpmError("%s: by must be None or 'subject'" % what)
+    if fuse not in ops.GROUP_FUSE:
+        raise FpmError("%s: fuse must be one of %s" % (what, ops.GROUP_FUSE))
+    if impressions not in IMPRESSIONS:
+        raise FpmError("%s: impressions must be one of %s" % (what, IMPRESSIONS))
+    if by is None:
+        if impressions != "all":
+            raise FpmError("%s: impressions=%r without by='subject'" % (what, impressions))
+        return False
+    if not isinstance(index, GalleryIndex):
+        raise FpmError("%s: index must be a GalleryIndex (Net.enroll)" % what)
+    if index.subject is None:
+        raise FpmError("%s: by='subject' needs subject labels on the index (enroll(subjects=...) or "
+                       "GalleryIndex.set_subjects)" % what)
+    if impressions == "best" and shortlist is None:
+        raise FpmError("%s: impressions='best' needs a shortlist (the coarse score picks a subject's best impression)"
+                       % what)
+    return True
+
+
+def _subject_entry_lists(gt, spos, best=None, own=None):
+    """The exact stage's entry lists of shortlisted subjects, per probe, on the host.  ``gt``: the
+    selection's group tables; ``spos`` (Q, M): each probe's group numbers in coarse-rank order; ``best``
+    (Q, S) or None: each group's best position (impressions "best"), None: every position of a group,
+    ascending ("all"); ``own`` (Q, Gs) bool or None: positions left out (the probe's own entry)
+    -> per probe (positions into the selection (L,), subject-major in the order of spos; offsets (M + 1,))."""
+    off, pos = gt["off"].long(), gt["pos"].long()
+    M = int(spos.shape[1])
+    lists = []
+    for i in range(int(spos.shape[0])):
+        sp = spos[i].long()
+        if best is None:
+            cnt = off[sp + 1] - off[sp]
+            grp = torch.repeat_interleave(torch.arange(M), cnt)
+            first = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
+            p = pos[off[sp][grp] + torch.arange(int(grp.numel())) - first[grp]]
+        else:
+            p, grp = best[i].long()[sp], torch.arange(M)
+        if own is not None:
+            keep = ~own[i][p]
+            p, grp = p[keep], grp[keep]
+        so = torch.cat([torch.zeros(1, dtype=torch.int64), torch.bincount(grp, minlength=M).cumsum(0)])
+        lists.append((p, so))
+    return lists
+
+
+def _subject_ranking(rows, ents, offs, labels, fuse, topk, dev):
+    """The subject ranking of the exact stage over ragged pair lists.  rows[i]: probe i's exact scores
+    (L_i,) on the device; ents[i]: their entry numbers (L_i,) host; offs[i]: (M + 1,) host offsets of the M
+    subjects into them; labels (Q, M) device int64.  The rows are padded with NaN to one matrix, each
+    with its own group structure (``ops.group_scores``), then ``ops.rank_topk`` over the M subjects
+    -> subject_score (Q, M), top_subject (Q, k) int64, top_score (Q, k), top_idx (Q, k) int32: the entry of
+    each top subject's best impression (-1 for a subject with no pair)."""
+    Q, M = len(rows), int(labels.shape[1])
+    L = max(1, max(int(r.numel()) for r in rows))
+    mat = torch.full((Q, L), float("nan"), device=dev, dtype=torch.float32)
+    ent = torch.full((Q, L), -1, dtype=torch.int32)
+    for i, r in enumerate(rows):
+        mat[i, :r.numel()] = r.view(-1)
+        ent[i, :r.numel()] = ents[i].to(torch.int32)
+    off = torch.stack([o.to(torch.int32) for o in offs])
+    pos = torch.arange(L, dtype=torch.int32).view(1, L).expand(Q, L).contiguous()
+    gsc, gb = ops.group_scores(mat, off.to(dev), pos.to(dev), fuse, off_host=off, pos_host=pos)
+    k = max(1, min(int(topk), M, 128))
+    ti, ts = ops.rank_topk(gsc, k)
+    bp = torch.gather(gb, 1, ti.long())
+    te = torch.gather(ent.to(dev), 1, bp.clamp(min=0).long())
+    te = torch.where(bp >= 0, te, torch.full_like(te, -1))
+    return gsc, torch.gather(labels, 1, ti.long()), ts, te
+
+
 def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None, shortlist=None,
-             coarse="fused"):
+             coarse="fused", by=None, fuse="max", impressions="all"):
     """``Net.identify``: see there."""
     _check_coarse(coarse, "identify")
+    subj = _check_by("identify", index, by, fuse, impressions, shortlist)
     if net.training:
         raise FpmError("identify: inference only (call net.eval()); training through an index is not supported")
     if net.use_graphs:
@@ -792,6 +942,9 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
         raise FpmError("identify: score must be one of %s" % (SCORES,))
     _check_query(net, index, "identify")
     if shortlist is not None:
+        if subj:
+            return _identify_shortlist_subject(net, probes, index, topk, select, score, chunks, shortlist, coarse, fuse,
+                                               impressions)
         return _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist, coarse)
     single = isinstance(probes, dict)
     plist = [probes] if single else list(probes)
@@ -800,7 +953,19 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
         for p in plist:
             bt, sel = probe_batch(p, index, select)
             outs.append(net.run(bt, chunks=chunks))
-        if outs:
+        if outs and subj:
+            # one structure for all probes: the selection's groups, positions in selection order
+            gt = index.subject_groups(sel)
+            sc = torch.stack([o[score].view(-1) for o in outs])
+            gsc, gb = ops.group_scores(sc, gt["off_d"], gt["pos_d"], fuse, off_host=gt["off"], pos_host=gt["pos"])
+            k = max(1, min(int(topk), int(gt["labels"].numel()), 128))
+            ti, ts = ops.rank_topk(gsc, k)
+            te = index._sel[1]["idx"][torch.gather(gb, 1, ti.long()).long()]
+            tl = gt["labels_d"][ti.long()]
+            for i, o in enumerate(outs):
+                o["subjects"], o["subject_score"] = gt["labels_d"], gsc[i]
+                o["top_subject"], o["top_score"], o["top_idx"] = tl[i], ts[i], te[i]
+        elif outs:
             k = max(1, min(int(topk), int(sel.numel()), 128))
             sc = torch.stack([o[score].view(-1) for o in outs])
             ti, ts = ops.rank_topk(sc, k)
@@ -808,6 +973,46 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
             ti = sel_d[ti.long()]
             for i, o in enumerate(outs):
                 o["top_idx"], o["top_score"] = ti[i], ts[i]
+    return outs[0] if single else outs
+
+
+def _identify_shortlist_subject(net, probes, index, topk, select, score, chunks, shortlist, coarse, fuse, impressions):
+    """``identify(by="subject", shortlist=M)``: per probe the coarse pass over ``select``, fused per subject
+    by max whatever ``fuse`` is (a subject stays in if any of its impressions matches), the M best
+    subjects (``ops.rank_select``), the plain ``identify`` over their impressions (all of them, or each
+    subject's best by the coarse score), subject-major in coarse-rank order, and the subject ranking of
+    the exact scores (``_subject_ranking``)."""
+    M = _check_shortlist(shortlist, "identify")
+    sel = _select_host(index, select, "identify")
+    gt = index.subject_groups(sel)
+    M = min(M, int(gt["labels"].numel()))
+    single = isinstance(probes, dict)
+    plist = [probes] if single else list(probes)
+    if not plist:
+        return []
+    dev = index.device
+    call = coarse_scores(net, plist, index, select=sel, coarse=coarse)
+    with torch.cuda.device(dev):
+        cg, cb = ops.group_scores(call, gt["off_d"], gt["pos_d"], "max", off_host=gt["off"], pos_host=gt["pos"])
+        spos, csc = ops.rank_select(cg, M)
+        labs = gt["labels_d"][spos.long()]
+        spos_h = spos.cpu()                     # the shortlist shapes the host-side batch: one copy per query
+        best_h = cb.cpu() if impressions == "best" else None
+    lists = _subject_entry_lists(gt, spos_h, best_h)
+    outs, ents = [], []
+    for i, p in enumerate(plist):
+        ent = sel[lists[i][0]]
+        o = identify(net, p, index, topk=topk, select=ent, score=score, chunks=chunks)
+        o["short_subject"], o["coarse_subject_score"], o["coarse_all"] = labs[i], csc[i], call[i]
+        o["short_idx"] = ent.to(torch.int32).to(dev)
+        o["short_off"] = lists[i][1].to(torch.int32).to(dev)
+        outs.append(o)
+        ents.append(ent)
+    with torch.cuda.device(dev):
+        gsc, tl, ts, te = _subject_ranking([o[score] for o in outs], ents, [l[1] for l in lists], labs, fuse, topk, dev)
+    for i, o in enumerate(outs):
+        o["subjects"], o["subject_score"] = labs[i], gsc[i]
+        o["top_subject"], o["top_score"], o["top_idx"] = tl[i], ts[i], te[i]
     return outs[0] if single else outs
 
 
@@ -997,10 +1202,12 @@ def probe_groups(n_probe_host, pairs_per_probe, group_pairs):
 
 
 def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
-                  coarse="fused", chunks=None, group_pairs=1024, exclude_self=False):
+                  coarse="fused", chunks=None, group_pairs=1024, exclude_self=False, by=None, fuse="max",
+                  impressions="all"):
     """``Net.identify_many``: see there."""
     what = "identify_many"
     _check_coarse(coarse, what)
+    subj = _check_by(what, index, by, fuse, impressions, shortlist)
     if score not in SCORES:
         raise FpmError("%s: score must be one of %s" % (what, SCORES))
     if exclude_self and probes is not index:
@@ -1013,6 +1220,9 @@ def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None
     dev = index.device
     if exclude_self and Gs < 2:
         raise FpmError("%s: exclude_self needs at least two selected entries" % what)
+    if subj:
+        return _identify_many_subject(net, probes, index, topk, shortlist, psel, sel, score, coarse, chunks, group_pairs,
+                                      exclude_self, fuse, impressions)
     short = csc = call = None
     with torch.cuda.device(dev):
         psel_d, sel_d = psel.to(dev), sel.to(dev)
@@ -1057,4 +1267,65 @@ def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None
         d["top_idx"], d["top_score"] = ti[i], ts[i]
         if short is not None:
             d["short_idx"], d["coarse_score"], d["coarse_all"] = short[i], csc[i], call[i]
+    return outs
+
+
+def _identify_many_subject(net, probes, index, topk, shortlist, psel, sel, score, coarse, chunks, group_pairs,
+                           exclude_self, fuse, impressions):
+    """``identify_many(by="subject")`` after the shared checks.  The coarse scores are fused per subject by
+    max over one structure shared by all probes; the exact stage's pair lists are ragged (a subject has
+    as many pairs as impressions), so ``probe_groups`` takes one pair count per probe and the exact scores
+    are fused over one structure per probe (``_subject_ranking``).  ``exclude_self``: leave-one-out -- the
+    probe's own entry counts as -inf in the coarse fuse and is left out of its pair list and of its
+    group; its subject's other impressions stay, and a subject emptied that way ranks last (NaN)."""
+    what = "identify_many"
+    dev = index.device
+    Qs = int(psel.numel())
+    gt = index.subject_groups(sel)
+    S = int(gt["labels"].numel())
+    own = (psel.view(-1, 1) == sel.view(1, -1)) if exclude_self else None
+    call = csc = best_h = None
+    with torch.cuda.device(dev):
+        if shortlist is not None:
+            M = min(_check_shortlist(shortlist, what), S)
+            call = coarse_scores_many(net, probes, index, probe_select=psel, select=sel, coarse=coarse)
+            ranked = call if own is None else call.masked_fill(own.to(dev), float("-inf"))
+            cg, cb = ops.group_scores(ranked, gt["off_d"], gt["pos_d"], "max", off_host=gt["off"], pos_host=gt["pos"])
+            spos, csc = ops.rank_select(cg, M)
+            spos_h = spos.cpu()                                  # the pair lists shape the host-side batches: one copy
+            best_h = cb.cpu() if impressions == "best" else None
+            labs = gt["labels_d"][spos.long()]
+        else:
+            M = S
+            spos_h = torch.arange(S, dtype=torch.int32).view(1, S).expand(Qs, S)
+            labs = gt["labels_d"].view(1, S).expand(Qs, S)
+    lists = _subject_entry_lists(gt, spos_h, best_h, own)
+    ents = [sel[p] for p, _ in lists]
+    per = torch.tensor([int(e.numel()) for e in ents], dtype=torch.int64)
+    if int(per.min()) < 1:
+        raise FpmError("%s: a probe is left with no pair (exclude_self took its only shortlisted entry); "
+                       "raise shortlist or widen select" % what)
+    groups = probe_groups(probes.n[psel], per, group_pairs)
+    outs, rows = [None] * Qs, [None] * Qs
+    for gi, grp in enumerate(groups):
+        pairs = torch.cat([torch.stack([psel[i].expand(int(per[i])), ents[i]], 1) for i in grp])
+        o = _run_pairs(net, probes, index, pairs, chunks)
+        Bg, b0 = int(pairs.shape[0]), 0
+        for i in grp:
+            b1 = b0 + int(per[i])
+            d = {key: (v[b0:b1] if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == Bg else v)
+                 for key, v in o.items()}
+            d["group"] = (gi, b0, b1)
+            rows[i] = d[score].view(-1)
+            outs[i] = d
+            b0 = b1
+    with torch.cuda.device(dev):
+        gsc, tl, ts, te = _subject_ranking(rows, ents, [so for _, so in lists], labs, fuse, topk, dev)
+    for i, d in enumerate(outs):
+        d["subjects"], d["subject_score"] = labs[i], gsc[i]
+        d["top_subject"], d["top_score"], d["top_idx"] = tl[i], ts[i], te[i]
+        d["short_idx"] = ents[i].to(torch.int32).to(dev)
+        d["short_off"] = lists[i][1].to(torch.int32).to(dev)
+        if call is not None:
+            d["short_subject"], d["coarse_subject_score"], d["coarse_all"] = labs[i], csc[i], call[i]
     return outs

@@ -1466,7 +1466,7 @@ class Net(nn.Module):
                                 chunk_timeline_ms=timeline)
         return res
 
-    def enroll(self, graphs, device, sc_mode=None, batch=256, layout="f32"):
+    def enroll(self, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None):
         """Enrol a gallery for 1:N identification (inference only): run the two SplineConv layers over
         ``graphs`` (dicts as ``fpm.synth.make_graph`` returns) once, in sub-batches of ``batch``, and
         keep their fp32 output rows -> ``fpm.gallery.GalleryIndex`` (3 KB per keypoint).  ``sc_mode``:
@@ -1482,11 +1482,16 @@ class Net(nn.Module):
         the fp32 rows in pinned host memory (3 KB per keypoint of host RAM), written sub-batch by
         sub-batch, so the device never holds the whole fp32 gallery; the exact forward copies the
         rows of the entries it runs over to the device per query.  Every output of ``identify`` and
-        ``coarse_scores`` is the same bits whatever the layout."""
-        from . import gallery
-        return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch, layout=layout)
+        ``coarse_scores`` is the same bits whatever the layout.
 
-    def enroll_keypoints(self, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri"):
+        ``subjects``: one integer label >= 0 per graph, the subject (finger) each impression belongs to;
+        kept on the index (``GalleryIndex.subject``, ``set_subjects`` relabels) for
+        ``identify(by="subject")``.  Every other field of the index is the same with or without it."""
+        from . import gallery
+        return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch, layout=layout, subjects=subjects)
+
+    def enroll_keypoints(self, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri",
+                         subjects=None):
         """``enroll`` from keypoints and features, on the device: no host graph dicts.  P: (G, nmax, 2)
         fp32 padded keypoints, n: (G,) counts in [1, nmax], x: (G, nmax, 768) or (G * nmax, 768) fp32
         node features (padding rows are ignored), w: (G, 512) global features; tensors or arrays, host
@@ -1497,18 +1502,19 @@ class Net(nn.Module):
         writes the sub-batch's ragged rows -- fp32, bf16 or both, by ``layout`` -- into their place in
         the index, whose rows are allocated once: the device peak is the index plus one sub-batch.
         -> ``GalleryIndex``, every field equal to ``enroll`` on the same graphs as host dicts with the
-        same ``batch``.  ``sc_mode`` / ``layout``: as ``enroll``."""
+        same ``batch``.  ``sc_mode`` / ``layout`` / ``subjects``: as ``enroll``."""
         from . import gallery
         return gallery.enroll_keypoints(self, P, n, x, w, device=device, sc_mode=sc_mode, batch=batch, layout=layout,
-                                        stg=stg)
+                                        stg=stg, subjects=subjects)
 
-    def enroll_images(self, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri"):
+    def enroll_images(self, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri",
+                      subjects=None):
         """``enroll_keypoints`` from images (needs ``Net(backbone=True)``): images (G, 3, H, W), P and n as
         there.  Per sub-batch ``image_features`` (backbone + feature_align, one side) makes x and w, so
         the backbone's memory is bounded by ``batch``."""
         from . import gallery
         return gallery.enroll_images(self, images, P, n, device=device, sc_mode=sc_mode, batch=batch, layout=layout,
-                                     stg=stg)
+                                     stg=stg, subjects=subjects)
 
     def probe_graphs(self, P, n, x=None, w=None, images=None, device=None, stg="tri"):
         """Probe graphs for ``identify`` / ``coarse_scores`` from keypoints, on the device -> a list of
@@ -1545,7 +1551,7 @@ class Net(nn.Module):
         return gallery.coarse_scores(self, probes, index, select=select, coarse=coarse)
 
     def identify(self, probes, index, topk=10, select=None, shortlist=None, score="cls_prob", chunks=None,
-                 coarse="fused"):
+                 coarse="fused", by=None, fuse="max", impressions="all"):
         """1:N identification against an enrolled gallery: for each probe graph (one dict, or a list)
         the shared-probe forward over the gallery entries ``select`` (an index list; default all),
         with side 1's operand rows gathered from ``index`` (no SplineConv for the gallery side) --
@@ -1570,10 +1576,32 @@ class Net(nn.Module):
         device and the forward runs over the selected entries' fp32 rows, copied from pinned host
         memory into a reused staging buffer (``GalleryIndex.fetch``): the same outputs bit for bit.
         ``shortlist=M`` is the intended use there; without one the selection's rows must fit
-        ``gallery.FETCH_MAX_BYTES`` (1.89 GB, the largest shortlist's), larger ones are refused."""
+        ``gallery.FETCH_MAX_BYTES`` (1.89 GB, the largest shortlist's), larger ones are refused.
+
+        ``by="subject"`` (an index with subject labels: ``enroll(subjects=...)``) ranks subjects, not
+        entries; ``by=None`` (the default) is everything above, unchanged.  The exact forward runs over
+        the selected entries as above, ``score`` is fused per subject on the device
+        (``ops.group_scores``; ``fuse``: "max", a subject's best impression, or "mean" over its selected
+        impressions) and ``ops.rank_topk`` ranks the S subjects, k = min(topk, S, 128).  The dict carries
+        ``subjects`` (S, int64: the selection's distinct labels, ascending), ``subject_score`` (S),
+        ``top_subject`` (k, int64), ``top_score`` (k, fused) and ``top_idx`` (k, int32: the entry of each
+        top subject's best impression).
+
+        ``by="subject", shortlist=M``: M counts subjects (clamped to S).  The coarse scores are fused per
+        subject by max whatever ``fuse`` is -- a subject stays in if any of its impressions matches --
+        ``ops.rank_select`` keeps the M best subjects, and the forward runs over their impressions,
+        subject-major in coarse-rank order: ``impressions="all"``, every selected impression of those
+        subjects (ascending position inside a subject), or ``"best"``, each subject's best impression by
+        the coarse score alone.  The exact scores are then fused with ``fuse`` and ranked; ``subjects``
+        and ``subject_score`` speak of the M shortlisted subjects.  Further outputs: ``short_subject`` (M,
+        int64), ``coarse_subject_score`` (M), ``short_idx`` (L, int32: the entry list), ``short_off``
+        (M + 1, int32: subject m's pairs are short_idx[short_off[m]:short_off[m + 1]]) and ``coarse_all``.
+        Every per-pair output equals ``identify(probe, index, select=short_idx)`` bit for bit.
+        Refused: an index without labels, an unknown ``fuse`` or ``impressions``, ``impressions`` without
+        ``by``, and ``impressions="best"`` without a shortlist."""
         from . import gallery
         return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
-                                shortlist=shortlist, coarse=coarse)
+                                shortlist=shortlist, coarse=coarse, by=by, fuse=fuse, impressions=impressions)
 
     # Probe sets: a *probe set* is a GalleryIndex enrolled from the probe graphs (``enroll``), with its
     # fp32 rows on the device (layout "f32" or "f32+bf16"), on the gallery's device, enrolled with the
@@ -1600,7 +1628,8 @@ class Net(nn.Module):
         return gallery.coarse_scores_many(self, probes, index, probe_select=probe_select, select=select, coarse=coarse)
 
     def identify_many(self, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
-                      coarse="fused", chunks=None, group_pairs=1024, exclude_self=False):
+                      coarse="fused", chunks=None, group_pairs=1024, exclude_self=False, by=None, fuse="max",
+                      impressions="all"):
         """1:N identification of a whole probe set -> a list of dicts, one per probe of ``probe_select``
         (default all), in that order.  ``coarse_scores_many``, ``ops.rank_select`` to the ``shortlist``
         best entries per probe, one host copy of all shortlists, then the exact forward in *groups* of
@@ -1619,11 +1648,21 @@ class Net(nn.Module):
 
         ``exclude_self`` (only with ``probes is index``: de-duplicating a gallery): the pair (q, entry
         q) is left out: its coarse score counts as -inf in the ranking (``coarse_all`` keeps it) and
-        the shortlist is clamped to len(select) - 1."""
+        the shortlist is clamped to len(select) - 1.
+
+        ``by="subject"`` / ``fuse`` / ``impressions``: as ``identify``, with ``subjects`` the subjects of
+        ``subject_score`` (the M shortlisted ones, or all S).  A probe's pair list is ragged under
+        ``impressions="all"`` (``short_idx`` / ``short_off`` are always there), so the groups are packed
+        by each probe's own pair count, and the exact scores are fused over one group structure per
+        probe.  ``exclude_self`` then means leave-one-out identification: the probe's own entry counts
+        as -inf in the coarse fuse and is left out of its pair list and of its group, while the other
+        impressions of its subject stay; a subject emptied that way ranks last (``subject_score`` NaN,
+        ``top_idx`` -1)."""
         from . import gallery
         return gallery.identify_many(self, probes, index, topk=topk, shortlist=shortlist, probe_select=probe_select,
                                      select=select, score=score, coarse=coarse, chunks=chunks,
-                                     group_pairs=group_pairs, exclude_self=exclude_self)
+                                     group_pairs=group_pairs, exclude_self=exclude_self, by=by, fuse=fuse,
+                                     impressions=impressions)
 
     def _need_backbone(self):
         if not hasattr(self, "node_layers"):

@@ -2,9 +2,10 @@
 
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
-no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``,
+no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``group_scores``,
 ``coarse_score`` / ``coarse_pairs``, ``rows_fetch`` and ``rows_pack`` alone keep a plain-torch host path for CPU tensors:
-the statements of the ordering, of the coarse score and of the ragged copies, which the tests hold the kernels to).
+the statements of the ordering, of the group fusion, of the coarse score and of the ragged copies, which the tests
+hold the kernels to).
 """
 import ctypes
 
@@ -592,8 +593,142 @@ def rank_select(scores, k, top_idx=None, top_score=None):
     return top_idx, top_score
 
 
+GROUP_FUSE = ("max", "mean")
+GROUP_TEAM = 16                 # lanes that sum a group of at most GROUP_WIDE entries
+GROUP_WIDE = 1024               # larger groups are summed by 64 lanes
+
+
+def _group_rows_host(scores, off, pos, mean, gscore, gbest):
+    """The statement of fpm_group_scores for rows that share one structure: scores (R, G) fp32, off
+    (S + 1,) and pos int64 host tensors (checked by the caller), into gscore / gbest (R, S).
+
+    gbest: the group's position with the largest ``rank_key``.  Max: the score there.  Mean, for a
+    group of c entries x[0..c) (x[j] = scores[r, pos[off[s] + j]]): W = GROUP_TEAM lanes for
+    c <= GROUP_WIDE, else 64; lane t starts from +0.0 and adds x[t], x[t + W], ... in order (a lane past
+    the group's end adds +0.0, which changes no bit: a lane's value is never -0.0); then for
+    m = W/2 .. 1 every lane takes v + v[lane ^ m]; lane 0's value over fp32(c), NaN as 0x7FC00000."""
+    R = int(scores.shape[0])
+    keys = rank_key(scores) if R else scores.new_zeros(scores.shape, dtype=torch.int64)
+    cnt = off[1:] - off[:-1]
+    width = torch.where(cnt > GROUP_WIDE, 64, GROUP_TEAM)
+    rounds = (cnt + width - 1) // width
+    qnan = torch.full((), float("nan"), dtype=torch.float32)
+    gscore.copy_(qnan.expand_as(gscore))
+    gbest.fill_(-1)
+    for w, r in sorted(set(zip(width[cnt > 0].tolist(), rounds[cnt > 0].tolist()))):
+        gs = torch.nonzero((width == w) & (rounds == r) & (cnt > 0)).view(-1)
+        j = torch.arange(r * w, dtype=torch.int64).view(1, -1)
+        valid = j < cnt[gs].view(-1, 1)
+        at = pos[torch.where(valid, off[gs].view(-1, 1) + j, torch.zeros((), dtype=torch.int64))]       # (ng, r * w)
+        k = torch.where(valid.unsqueeze(0), keys[:, at], torch.full((), -2 ** 63, dtype=torch.int64))
+        best = 0xFFFFFFFF - (k.max(dim=2).values & 0xFFFFFFFF)                                       # (R, ng)
+        gbest[:, gs] = best.to(torch.int32)
+        if not mean:
+            gscore[:, gs] = torch.gather(scores, 1, best)
+            continue
+        x = torch.where(valid.unsqueeze(0), scores[:, at], torch.zeros((), dtype=torch.float32)).view(R, -1, r, w)
+        acc = torch.zeros(R, int(gs.numel()), w, dtype=torch.float32)
+        for i in range(r):
+            acc = acc + x[:, :, i, :]
+        lanes = torch.arange(w)
+        m = w // 2
+        while m:
+            acc = acc + acc[..., lanes ^ m]
+            m //= 2
+        val = acc[..., 0] / cnt[gs].to(torch.float32).view(1, -1)
+        gscore[:, gs] = torch.where(torch.isnan(val), qnan, val)
+
+
+def group_scores(scores, off, pos, fuse="max", gscore=None, gbest=None, off_host=None, pos_host=None):
+    """Per-group fusion of a score matrix (fpm_group_scores; a group is the impressions of one subject):
+    scores (P, G) fp32 (any row stride); CSR tables ``off`` (S + 1,) int32 rising from 0 and ``pos`` int32
+    positions into a row of scores, group s = pos[off[s]:off[s + 1]] -- one structure shared by all
+    rows, or one per row: off (P, S + 1), pos (P, L), row p's positions at pos[p, :off[p, S]] (the rest
+    of the row is padding).  Positions need not cover the row; a group may be empty.
+    -> (gscore (P, S) fp32, gbest (P, S) int32).
+
+    gbest: the group's position with the largest ``rank_key`` (the key built from the position): the best
+    score, ties to the lower position, NaN below every number (an all-NaN group: its lowest position).
+    fuse="max": gscore = scores[p, gbest], the same bits.  fuse="mean": the fp32 sum of the group's
+    entries in the fixed order ``_group_rows_host`` states, over fp32(count), correctly rounded; NaN and
+    infinities propagate, a NaN mean is the canonical 0x7FC00000.  An empty group: NaN, -1.  A group's
+    result depends on its own entries and their order alone: not on P, S or the other groups.
+
+    Device tensors run the kernel; CPU tensors take the statement, which the kernel equals bit for bit.
+    Refused before any launch: dtypes, shapes, devices, offsets that do not start at 0, fall or pass
+    the end of pos, a used position outside [0, G), P > 65535 (``off_host`` / ``pos_host``: host copies,
+    so the check needs no device synchronisation; without them the device tensors are copied back)."""
+    op = "group_scores"
+    if fuse not in GROUP_FUSE:
+        raise _lib.FpmError("%s: fuse must be one of %s" % (op, GROUP_FUSE))
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
+        raise _lib.FpmError("%s: scores must be a (P, G) fp32 tensor" % op)
+    P, G = int(scores.shape[0]), int(scores.shape[1])
+    if G < 1:
+        raise _lib.FpmError("%s: scores has no columns" % op)
+    for name, t in (("off", off), ("pos", pos)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise _lib.FpmError("%s: %s must be a int32 tensor (got %s)" % (op, name, getattr(t, "dtype", type(t).__name__)))
+        if not t.is_contiguous():
+            raise _lib.FpmError("%s: %s must be contiguous" % (op, name))
+        if t.device != scores.device:
+            raise _lib.FpmError("%s: %s is on %s, scores on %s" % (op, name, t.device, scores.device))
+    per_row = off.dim() == 2
+    if off.dim() not in (1, 2) or pos.dim() != off.dim() or off.shape[-1] < 1:
+        raise _lib.FpmError("%s: off (S + 1,) with pos (L,) for a shared structure, or off (P, S + 1) with pos (P, L)" % op)
+    S = int(off.shape[-1]) - 1
+    if per_row and (int(off.shape[0]) != P or int(pos.shape[0]) != P or int(pos.shape[1]) < 1):
+        raise _lib.FpmError("%s: per-row structures need off (%d, S + 1) and pos (%d, L >= 1)" % (op, P, P))
+    if P > 65535:
+        raise _lib.FpmError("%s: at most 65535 rows per call" % op)
+    oh = torch.as_tensor(off_host if off_host is not None else off.cpu()).long()
+    ph = torch.as_tensor(pos_host if pos_host is not None else pos.cpu()).long()
+    if tuple(oh.shape) != tuple(off.shape) or tuple(ph.shape) != tuple(pos.shape):
+        raise _lib.FpmError("%s: host copies of off / pos do not match the device tensors" % op)
+    oh2, ph2 = oh.view(-1, S + 1), ph.view(oh.numel() // (S + 1), -1)
+    L = int(ph2.shape[1])
+    if oh2.numel() and (bool((oh2[:, 0] != 0).any()) or bool((oh2[:, 1:] < oh2[:, :-1]).any())):
+        raise _lib.FpmError("%s: offsets must start at 0 and must not fall" % op)
+    if oh2.numel() and int(oh2[:, -1].max()) > L:
+        raise _lib.FpmError("%s: offsets end at %d, pos holds %d positions" % (op, int(oh2[:, -1].max()), L))
+    used = torch.arange(L).view(1, -1) < oh2[:, -1:]
+    if bool((used & ((ph2 < 0) | (ph2 >= G))).any()):
+        raise _lib.FpmError("%s: a position outside [0, %d)" % (op, G))
+    if gscore is None:
+        gscore = torch.empty(P, S, device=scores.device, dtype=torch.float32)
+    if gbest is None:
+        gbest = torch.empty(P, S, device=scores.device, dtype=torch.int32)
+    _shape(gscore, (P, S), "group_scores gscore")
+    _shape(gbest, (P, S), "group_scores gbest")
+    if gscore.dtype != torch.float32 or gbest.dtype != torch.int32 or not gscore.is_contiguous() \
+            or not gbest.is_contiguous() or gscore.device != scores.device or gbest.device != scores.device:
+        raise _lib.FpmError("%s: gscore must be contiguous fp32, gbest contiguous int32, on the scores' device" % op)
+    if P == 0 or S == 0:
+        return gscore, gbest
+    if L == 0:                                   # no positions at all: every group is empty
+        gscore.fill_(float("nan"))
+        gbest.fill_(-1)
+        return gscore, gbest
+    mean = fuse == "mean"
+    if not scores.is_cuda:
+        if per_row:
+            for p in range(P):
+                _group_rows_host(scores[p:p + 1], oh2[p], ph2[p], mean, gscore[p:p + 1], gbest[p:p + 1])
+        else:
+            _group_rows_host(scores, oh2[0], ph2[0], mean, gscore, gbest)
+        return gscore, gbest
+    if G > 1 and scores.stride(1) != 1:
+        scores = scores.contiguous()
+    ld = int(scores.stride(0)) if P > 1 else G
+    if ld < G:
+        scores, ld = scores.contiguous(), G
+    _lib.call("fpm_group_scores", _p(scores), ld, P, G, _p(off), S + 1 if per_row else 0, _p(pos), L if per_row else 0, S,
+              int(mean), _p(gscore), _p(gbest), _stream(scores))
+    return gscore, gbest
+
+
 COARSE_NMAX = 128
-COARSE_WIDE_NMAX = 256          # ``coarse_score_wide``: the block in registers
+COARSE_WIDE_NMAX = 256         # ``coarse_score_wide``: the block in registers
 COARSE_STREAM_NMAX = 600        # ``coarse_score_stream``: the block streamed from a workspace (the matcher's cap)
 
 

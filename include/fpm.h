@@ -544,6 +544,22 @@ int fpm_rank_topk(const float* scores, long ld, int P, int G, int k, int* top_id
 long fpm_rank_select_ws_bytes(int P);
 int fpm_rank_select(const float* scores, long ld, int P, int G, int k, int* top_idx, float* top_score, void* ws,
                     long ws_bytes, void* stream);
+/* Per-group fusion of a score matrix (subject-level identification: a group is the impressions of one
+ * subject).  Row p's groups are CSR tables: group s holds the positions grp_pos[grp_off[s] .. grp_off[s + 1])
+ * (int32, positions into row p of scores, each in [0, G); they need not cover the row), read at
+ * grp_off + p * off_ld and grp_pos + p * pos_ld: both strides 0 for one structure shared by all rows,
+ * or off_ld >= S + 1 and pos_ld > 0 for one structure per row.  Outputs (P, S), contiguous:
+ *   gbest   the group's position with the largest fpm_rank_topk key (the key built from the position):
+ *           the best score, ties to the lower position, NaN below every number;
+ *   gscore  fuse 0 (max): scores[p][gbest], the same bits; fuse 1 (mean): the fp32 sum of the group's
+ *           entries divided by fp32(count), correctly rounded; a NaN mean is written as 0x7FC00000.
+ *   An empty group gives gscore = NaN (0x7FC00000), gbest = -1.
+ * Order of the sum (a function of the group's count c and the order of its positions alone): W = 16
+ * lanes for c <= 1024, else 64; lane t starts at +0.0 and adds entries t, t + W, ... in order; then
+ * for m = W/2 .. 1 every lane takes v + v[lane ^ m]; lane 0 holds the sum.  One launch, no atomics, no
+ * scratch.  P <= 65535. */
+int fpm_group_scores(const float* scores, long ld, int P, int G, const int* grp_off, long off_ld,
+                     const int* grp_pos, long pos_ld, int S, int fuse, float* gscore, int* gbest, void* stream);
 
 /* ---- coarse 1:N score (the first pass of a shortlisted identification) ---------------------------
  * One scalar per (probe, enrolled entry) pair, one workgroup per pair, B pairs per launch:

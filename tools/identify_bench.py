@@ -13,6 +13,13 @@
                                                                        (-> profiles/identify_compact.json)
     python tools/identify_bench.py --probes 16 --shortlist 64 [--coarse auto --n 256 --large 0] [--append]
                                                                        (-> profiles/identify_many.json)
+    python tools/identify_bench.py --subjects 4 --shortlist 64 --probes 16 --gallery 16384 --large 0 --dtypes bf16
+                                                                       (-> profiles/identify_subjects.json)
+
+``--subjects R`` (with ``--shortlist M``): the gallery labelled with R consecutive entries per subject.
+``ops.group_scores`` (max and mean) and ``ops.rank_select`` timed on the same ``--probes`` x gallery coarse
+matrix, and one probe's subject-level shortlisted query (``impressions`` all and best) against the
+entry-level one at the same M.
 
 ``--probes Q`` (with ``--shortlist M``): a probe set.  The looped ``identify(list of Q probes, shortlist=M)``
 (one probe at a time: the path before probe sets) against ``identify_many`` over the same enrolled gallery
@@ -440,6 +447,59 @@ def child_probes(args):
     print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
 
 
+def child_subjects(args):
+    """``--subjects R --shortlist M [--probes Q]``: the gallery labelled with R consecutive entries per
+    subject.  On the Q x G coarse matrix of a probe set: ``ops.group_scores`` (max and mean) against
+    ``ops.rank_select`` to M on the same matrix; then one probe's subject-level shortlisted query (both
+    ``impressions``) against the entry-level one at the same M, in this one process."""
+    import torch
+    import bench
+    import fpm
+    from fpm import ops, params, synth
+    dev = torch.device("cuda", 0)
+    G, n, dtype, M, coarse, R = args.gallery, args.n, args.child, args.shortlist, args.coarse, args.subjects
+    Q = args.probes or 16
+    probes = [synth.make_graph(args.seed, p, 0, n) for p in range(Q)]
+    base = bench.make_gallery(args.seed, 1, min(G, args.distinct), n, args.gen_workers)
+    gallery = [base[i % len(base)] for i in range(G)]      # past --distinct graphs the gallery repeats them
+    net = fpm.Net(regression=True, backbone=False, dtype=dtype)
+    net.load_state_dict(params.init_params(args.seed))
+    index = net.enroll(gallery, dev, subjects=[i // R for i in range(G)])
+    pset = net.enroll(probes, dev)
+    torch.cuda.synchronize()
+    del gallery, base
+    gt = index.subject_groups()
+    S = int(gt["labels"].numel())
+    res = dict(dtype=dtype, gallery=G, distinct_graphs=min(G, args.distinct), n=n, probes=Q, shortlist=M, per_subject=R,
+               subjects=S, sc_mode=index.sc_mode, reps=args.reps, coarse=coarse)
+    call = net.coarse_scores_many(pset, index, coarse=coarse)
+    torch.cuda.synchronize()
+
+    def series(fn):
+        fn()
+        torch.cuda.synchronize()
+        return _ev(_timed(fn, args.reps))
+
+    def fresh(fn):
+        index._sel = None                  # every timed query stages its entries, as a new probe's would
+        return fn()
+    gs = torch.empty(Q, S, device=dev)
+    gb = torch.empty(Q, S, device=dev, dtype=torch.int32)
+    for fuse in ops.GROUP_FUSE:
+        res["group_scores_%s" % fuse] = series(lambda: ops.group_scores(call, gt["off_d"], gt["pos_d"], fuse, gscore=gs,
+                                                                         gbest=gb, off_host=gt["off"], pos_host=gt["pos"]))
+    res["rank_select_entries"] = series(lambda: ops.rank_select(call, M))
+    res["rank_select_subjects"] = series(lambda: ops.rank_select(gs, min(M, S)))
+    res["matrix"] = "%d x %d" % (Q, G)
+    probe = probes[0]
+    res["entry_query"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, shortlist=M, coarse=coarse)))
+    for imp in ("all", "best"):
+        q = lambda: net.identify(probe, index, topk=10, shortlist=M, coarse=coarse, by="subject", impressions=imp)
+        res["subject_query_%s" % imp] = series(lambda: fresh(q))
+        res["subject_query_%s" % imp]["exact_pairs"] = int(q()["short_idx"].numel())
+    print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
+
+
 def main_shortlist(ap, args):
     lines = []
     shapes = [(args.gallery, dt) for dt in args.dtypes.split(",")]
@@ -449,7 +509,8 @@ def main_shortlist(ap, args):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", dtype, "--gallery", str(G), "--n", str(args.n),
                "--reps", str(args.reps), "--seed", str(args.seed), "--gen-workers", str(args.gen_workers),
                "--shortlist", str(args.shortlist), "--distinct", str(args.distinct), "--coarse", args.coarse,
-               "--layout", args.layout, "--probes", str(args.probes), "--group-pairs", str(args.group_pairs)]
+               "--layout", args.layout, "--probes", str(args.probes), "--group-pairs", str(args.group_pairs),
+               "--subjects", str(args.subjects)]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
         except subprocess.TimeoutExpired:
@@ -466,13 +527,20 @@ def main_shortlist(ap, args):
         name = "identify_compact.json"
     if args.probes:
         name = "identify_many.json"
+    if args.subjects:
+        name = "identify_subjects.json"
     out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", name)
-    doc = dict(tool="tools/identify_bench.py%s --shortlist %d%s%s" % (" --probes %d" % args.probes if args.probes else "",
+    doc = dict(tool="tools/identify_bench.py%s --shortlist %d%s%s" % ((" --subjects %d" % args.subjects if args.subjects
+                                                                       else "") +
+                                                                      (" --probes %d" % args.probes if args.probes else ""),
                                                                       args.shortlist, "" if args.coarse == "fused" else
                                                                     " --coarse %s --n %d" % (args.coarse, args.n),
                                                                     "" if args.layout == "f32" else
                                                                     " --layout %s" % args.layout),
-               config="1 probe x gallery, n keypoints per graph; full = identify over every entry (the path before "
+               config="gallery labelled with R consecutive entries per subject; group_scores (max, mean) and rank_select on "
+                      "the same probes x gallery coarse matrix; one probe's subject-level shortlisted query (impressions "
+                      "all / best) against the entry-level one at the same M" if args.subjects else
+                      "1 probe x gallery, n keypoints per graph; full = identify over every entry (the path before "
                       "the shortlist existed), shortlisted = coarse pass + rank_select + identify over the M entries"
                       if not args.probes else
                       "%d probes x gallery, n keypoints per graph; looped = identify(list, shortlist=M), one probe at a "
@@ -508,6 +576,10 @@ def main():
     ap.add_argument("--probes", type=int, default=0,
                     help="--shortlist: Q > 0 probes: the looped identify against identify_many "
                          "(profiles/identify_many.json)")
+    ap.add_argument("--subjects", type=int, default=0,
+                    help="--shortlist: R > 0 labels the gallery with R consecutive entries per subject and times "
+                         "group_scores against rank_select on the --probes (default 16) x gallery coarse matrix, and the "
+                         "subject-level shortlisted query against the entry-level one (profiles/identify_subjects.json)")
     ap.add_argument("--group-pairs", type=int, default=1024, help="--probes: identify_many's group_pairs")
     ap.add_argument("--append", action="store_true",
                     help="--shortlist: add the results to those the output file already holds (another --n)")
@@ -526,9 +598,11 @@ def main():
     args = ap.parse_args()
     if args.reps < 5:
         ap.error("--reps must be at least 5")
-    if args.probes and not args.shortlist > 0:
-        ap.error("--probes goes with --shortlist M")
+    if (args.probes or args.subjects) and not args.shortlist > 0:
+        ap.error("--probes and --subjects go with --shortlist M")
     if args.child:
+        if args.subjects:
+            return child_subjects(args)
         if args.probes:
             return child_probes(args)
         if args.shortlist > 0 and args.layout != "f32":
