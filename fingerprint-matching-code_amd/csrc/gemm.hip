@@ -261,6 +261,7 @@ int& combine_lds_kb_flag();
 int& gnn_mlp_off_flag();
 int& outer_sum_vec_flag();
 int& gnn_sweeps_flag();
+int& gnn_form_flag();
 int& scatter_f32_rows_flag();
 int& scatter_batch_flag();
 int& afau_head_split_flag();
@@ -284,6 +285,7 @@ extern "C" int fpm_set_tuning(const char* key, int value) {
     else if (key && !strcmp(key, "gnn_mlp_off")) f = &gnn_mlp_off_flag();
     else if (key && !strcmp(key, "outer_sum_vec")) f = &outer_sum_vec_flag();
     else if (key && !strcmp(key, "gnn_sweeps")) f = &gnn_sweeps_flag();
+    else if (key && !strcmp(key, "gnn_form")) f = &gnn_form_flag();
     else if (key && !strcmp(key, "scatter_f32_rows")) f = &scatter_f32_rows_flag();
     else if (key && !strcmp(key, "scatter_batch")) f = &scatter_batch_flag();
     else if (key && !strcmp(key, "afau_head_split")) f = &afau_head_split_flag();

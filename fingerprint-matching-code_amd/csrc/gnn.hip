@@ -18,6 +18,7 @@
 // workgroups of 2-4 BFS-consecutive nodes loading their neighbour-row union once: the larger
 // workgroups lost more to occupancy than the shared loads saved.)
 #include "fpm_common.h"
+#include <cstdint>
 #include <cstdlib>
 
 namespace {
@@ -263,6 +264,198 @@ __global__ __launch_bounds__(1024) void gnn_layer_kernel(const float* __restrict
     (void)NSW;
 }
 
+// ---- the resident form (boxes of at most 256 keypoints) -----------------------------------------
+// The form above needs 77 VGPRs: 6 waves per SIMD = 6 workgroups of 256 threads per CU.  This one
+// keeps every value's arithmetic and order (bit-identical) and is laid out by hand for 64 VGPRs with
+// no scratch and 18 KiB of LDS, so that 8 workgroups are resident per CU:
+//   phase 1   two neighbour rows' loads in flight; the sums as channel pairs (v_pk_add_f32: the same
+//             IEEE add per lane), written to 72-B node rows (18 KiB at 256 nodes; every row 8-B
+//             aligned); channel 17 of a row is a zero pad
+//   phase 2   the chains that need only x first: h = relu(W1 x + b1), then u = relu(W2 h + b2) for
+//             all 16 output channels (h is dead from here); then the graph-1 gather (agg is needed
+//             only by lin_l) and the mean on channel pairs; then per output pair l and r and
+//             ((l + bl) + r) + u.  Live at the peak: x (18) + u (16) + agg (18) + a few, which is why
+//             every address of this phase is one 32-bit offset against a base in SGPRs.
+// Measured (profiles/r08_gnn_resident.txt): 2-4 % off a 17-channel launch alone, 3-12 % off a 1-channel
+// launch, by box.  The two more resident workgroups are the smaller part of that: the layer's time is the sum
+// of its parts' throughputs (the neighbour rows arrive at ~55 B per clock and CU, the rate of the
+// L2 -> L1 path), not residency x latency -- three rows in flight at 7 workgroups per CU and raised
+// wave priority in either phase measured the same or slower and are not kept.
+template <int C>
+__device__ __forceinline__ void gnn_resident_body(float* T, const float* __restrict__ X, int n1max, int n2max,
+                                                  const int* __restrict__ ptr1, const int* __restrict__ nbr1,
+                                                  const int* __restrict__ ptr2, const int* __restrict__ nbr2,
+                                                  const int* __restrict__ n1, const int* __restrict__ n2,
+                                                  const float* __restrict__ W, float* __restrict__ Xo,
+                                                  float* __restrict__ zbuf, float* __restrict__ vpart,
+                                                  const float* __restrict__ cls_w, int B,
+                                                  const int* __restrict__ ord2) {
+    using P = GnnPack<C>;
+    constexpr int CP = (C + 1) / 2;                       // channel pairs (the last one half empty)
+    constexpr int TS = C == 1 ? 1 : 2 * CP;               // floats per node row in LDS
+    int b, d;
+    if (!pair_block(n2max, B, b, d)) return;
+    if (ord2) d = ord2[(long)b * n2max + d];
+    const int i = threadIdx.x;
+    const long N = (long)n1max * n2max;
+    const __amdgpu_buffer_rsrc_t xr =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(X + (long)b * C * N), (short)0, (int)(C * N * 4), 0x00020000);
+    const int N4 = (int)(N * 4);
+    const int beg2 = ptr2[(long)b * n2max + d], end2 = ptr2[(long)b * n2max + d + 1];
+    auto load_row = [&](int off, f2_t (&v)[CP]) {         // the C channels at byte offset off, as pairs
+#pragma unroll
+        for (int k = 0; k < CP; ++k) {
+            v[k].x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xr, off, 2 * k * N4, 0));
+            v[k].y = 2 * k + 1 < C ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xr, off, (2 * k + 1) * N4, 0))
+                                   : 0.f;
+        }
+    };
+    if (i < n1max) {
+        f2_t acc[CP];
+#pragma unroll
+        for (int k = 0; k < CP; ++k) acc[k] = (f2_t){0.f, 0.f};
+        int k = beg2;
+        for (; k + 1 < end2; k += 2) {                    // two rows' loads in flight, summed in list order
+            f2_t va[CP], vb[CP];
+            load_row((nbr2[k] * n1max + i) * 4, va);
+            load_row((nbr2[k + 1] * n1max + i) * 4, vb);
+#pragma unroll
+            for (int q = 0; q < CP; ++q) acc[q] += va[q];
+#pragma unroll
+            for (int q = 0; q < CP; ++q) acc[q] += vb[q];
+        }
+        if (k < end2) {
+            f2_t va[CP];
+            load_row((nbr2[k] * n1max + i) * 4, va);
+#pragma unroll
+            for (int q = 0; q < CP; ++q) acc[q] += va[q];
+        }
+        float* Ti = T + i * TS;
+        if constexpr (C == 1) {
+            Ti[0] = acc[0].x;
+        } else {
+#pragma unroll
+            for (int q = 0; q < CP; ++q) *(f2_t*)(Ti + 2 * q) = acc[q];
+        }
+    }
+    __syncthreads();
+    if (i >= n1max) return;
+
+    // 32-bit positions from here on (host check: 17 * N * 4 < 2^31); every access of this phase is a
+    // buffer access at the one VGPR offset p4 (or e4), its base in SGPRs
+    const int nn2 = end2 - beg2;
+    const int p4 = (d * n1max + i) * 4;
+    const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc((void*)(Xo + (long)b * 17 * N), (short)0,
+                                                                         (int)(17 * N * 4), 0x00020000);
+    const f2_t* W2p = (const f2_t*)W;                     // pair view (all block offsets even)
+    f2_t x2[CP];
+    load_row(p4, x2);
+    f2_t u[8];
+    {
+        f2_t h[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            f2_t s = W2p[(P::b1 >> 1) + m];
+#pragma unroll
+            for (int c = 0; c < C; ++c) pk_fma_bcast(s, W2p[((P::W1 + c * 16) >> 1) + m], x2[c >> 1], c & 1);
+            h[m] = (f2_t){fmaxf(s.x, 0.f), fmaxf(s.y, 0.f)};
+        }
+#pragma unroll
+        for (int op = 0; op < 8; ++op) {
+            f2_t t = {0.f, 0.f};
+#pragma unroll
+            for (int m = 0; m < 16; ++m) pk_fma_bcast(t, W2p[((P::W2 + m * 16) >> 1) + op], h[m >> 1], m & 1);
+            const f2_t tb = t + W2p[(P::b2 >> 1) + op];
+            u[op] = (f2_t){fmaxf(tb.x, 0.f), fmaxf(tb.y, 0.f)};
+        }
+    }
+    // the graph-1 gather from the node rows in LDS, in neighbour-list order; the pair's slice of the
+    // neighbour list as a buffer (its extent is not known here: no range check, as with a pointer)
+    const int base1 = ptr1[(long)b * n1max];
+    const __amdgpu_buffer_rsrc_t nr =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(nbr1 + base1), (short)0, 0x7ffffffc, 0x00020000);
+    const int beg = ptr1[(long)b * n1max + i] - base1, end = ptr1[(long)b * n1max + i + 1] - base1;
+    f2_t a2[CP];
+#pragma unroll
+    for (int q = 0; q < CP; ++q) a2[q] = (f2_t){0.f, 0.f};
+    // a node row as pairs of ds_read_b64 (left to the compiler the nine reads pair up into
+    // ds_read2_b64, which moves its bytes at a quarter of the rate; more than two in flight does
+    // not fit the 64 registers); the loads and their wait are one statement, so the compiler never
+    // sees a destination before its data has landed
+    const unsigned tbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)T;
+    for (int e4 = beg * 4; e4 < end * 4; e4 += 4) {
+        const int a = __builtin_amdgcn_raw_buffer_load_b32(nr, e4, 0, 0);
+        if constexpr (C == 1) {
+            a2[0].x += T[a];
+        } else {
+            const unsigned ta = tbase + a * (TS * 4);
+#define FPM_GNN_READ2(q0, o0, o1)                                                                                \
+    {                                                                                                            \
+        f2_t g0, g1;                                                                                             \
+        asm volatile("ds_read_b64 %0, %2 offset:" #o0 "\n\tds_read_b64 %1, %2 offset:" #o1                       \
+                     "\n\ts_waitcnt lgkmcnt(0)"                                                                  \
+                     : "=&v"(g0), "=&v"(g1)                                                                      \
+                     : "v"(ta)                                                                                   \
+                     : "memory");                                                                                \
+        a2[q0] += g0;                                                                                            \
+        a2[q0 + 1] += g1;                                                                                        \
+    }
+            FPM_GNN_READ2(0, 0, 8)
+            FPM_GNN_READ2(2, 16, 24)
+            FPM_GNN_READ2(4, 32, 40)
+            FPM_GNN_READ2(6, 48, 56)
+#undef FPM_GNN_READ2
+            {
+                f2_t g0;
+                asm volatile("ds_read_b64 %0, %1 offset:64\n\ts_waitcnt lgkmcnt(0)" : "=&v"(g0) : "v"(ta) : "memory");
+                a2[8] += g0;
+            }
+        }
+    }
+    const bool self = (p4 >> 2) < n1[b] * n2[b];
+    const float cnt = (float)((end - beg) * nn2 + (self ? 1 : 0));
+    const float rc = cnt > 0.f ? 1.f / cnt : 0.f;         // one division per position (see gnn_point)
+#pragma unroll
+    for (int q = 0; q < CP; ++q) {
+        const f2_t v = self ? a2[q] + x2[q] : a2[q];
+        a2[q] = v * rc;
+    }
+    float z = 0.f, vp = 0.f;
+#pragma unroll
+    for (int op = 0; op < 8; ++op) {
+        const int o = 2 * op;
+        f2_t l = {0.f, 0.f}, r = {0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            pk_fma_bcast(l, W2p[((P::Wl + c * 16) >> 1) + op], a2[c >> 1], c & 1);
+            pk_fma_bcast(r, W2p[((P::Wr + c * 16) >> 1) + op], x2[c >> 1], c & 1);
+        }
+        const f2_t x1 = ((l + W2p[(P::bl >> 1) + op]) + r) + u[op];
+        if (vpart) {
+            vp = fmaf(cls_w[o], x1.x, vp);
+            vp = fmaf(cls_w[o + 1], x1.y, vp);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x1.x), orr, p4, o * N4, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x1.y), orr, p4, (o + 1) * N4, 0);
+        }
+        z = fmaf(W[P::wc + o], x1.x, z);
+        z = fmaf(W[P::wc + o + 1], x1.y, z);
+    }
+    if (vpart) vpart[(long)b * N + (p4 >> 2)] = vp;
+    zbuf[(long)b * N + (p4 >> 2)] = z + W[P::bc];
+}
+
+// WPS: waves per SIMD the register allocation is bounded for = workgroups of 256 threads per CU
+template <int C, int WPS>
+__global__ __launch_bounds__(256, WPS) void gnn_layer_resident_kernel(
+    const float* __restrict__ X, int n1max, int n2max, const int* __restrict__ ptr1, const int* __restrict__ nbr1,
+    const int* __restrict__ ptr2, const int* __restrict__ nbr2, const int* __restrict__ n1, const int* __restrict__ n2,
+    const float* __restrict__ W, float* __restrict__ Xo, float* __restrict__ zbuf, float* __restrict__ vpart,
+    const float* __restrict__ cls_w, int B, const int* __restrict__ ord2) {
+    extern __shared__ __attribute__((aligned(16))) float T[];
+    gnn_resident_body<C>(T, X, n1max, n2max, ptr1, nbr1, ptr2, nbr2, n1, n2, W, Xo, zbuf, vpart, cls_w, B, ord2);
+}
+
 // v[p] = classifier(emb[p]) (ngm.py:368), written as s[b][i][j] = v[b][j*n1max + i] (ngm.py:369).
 // With vpart (the last GNN layer's w[0:16] . x1, fused there) only channel 16 (its Sinkhorn) is read.
 // 64 x 64 (d, i) tiles transposed through LDS: reads along i and writes s along d are both
@@ -330,6 +523,50 @@ int& gnn_mlp_off_flag() {
     return v;
 }
 
+// fpm_set_tuning("gnn_form", v): 1 (default) = boxes of at most 256 keypoints on the resident form, 8
+// workgroups per CU; 0 = the 1024-thread-bounded kernel for every box.  The other gnn_* switches
+// select variants of form 0 and take the launch there.
+int& gnn_form_flag() {
+    static int v = [] {
+        const char* e = getenv("FPM_GNN_FORM");
+        return e ? atoi(e) : 1;
+    }();
+    return v;
+}
+
+namespace {
+typedef void (*gnn_kernel_t)(const float*, int, int, const int*, const int*, const int*, const int*, const int*,
+                             const int*, const float*, float*, float*, float*, const float*, int, const int*);
+
+bool gnn_resident(int n1max) {
+    return gnn_form_flag() != 0 && n1max <= 256 && gnn_sweeps_flag() == 1 && !gnn_mlp_off_flag() &&
+           !gnn_store_sc1_flag();
+}
+
+gnn_kernel_t gnn_resident_kernel(int C) {
+    return C == 1 ? gnn_layer_resident_kernel<1, 8> : gnn_layer_resident_kernel<17, 8>;
+}
+
+size_t gnn_resident_lds(int C, int n1max) { return (size_t)(C == 1 ? 1 : 18) * n1max * 4; }
+}  // namespace
+
+// workgroups of the layer's kernel resident per CU at this box (the occupancy query; no launch)
+extern "C" int fpm_gnn_resident_blocks(int C, int n1max) {
+    FPM_CHECK_ARG(C == 1 || C == 17, "gnn_resident_blocks: C must be 1 or 17 (got %d)", C);
+    FPM_CHECK_ARG(n1max >= 1 && n1max <= 1024, "gnn_resident_blocks: n1max must be in [1, 1024]");
+    const bool res = gnn_resident(n1max);
+    const gnn_kernel_t k = res ? gnn_resident_kernel(C)
+                               : (C == 1 ? gnn_layer_kernel<1> : gnn_layer_kernel<17>);
+    const size_t sh = res ? gnn_resident_lds(C, n1max) : (size_t)(C == 1 ? 1 : 20) * n1max * 4;
+    if (sh > 65536) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, (n1max + 63) / 64 * 64, sh) != hipSuccess) {
+        fpm::set_error("gnn_resident_blocks: the occupancy query failed");
+        return -1;
+    }
+    return nb;
+}
+
 extern "C" int fpm_kron_gnn_layer_fwd_ord(const float* X, int C, int B, int n1max, int n2max, const int* ptr1,
                                           const int* nbr1, const int* ptr2, const int* nbr2, const int* n1,
                                           const int* n2, const float* params, float* Xout, float* zbuf,
@@ -339,15 +576,18 @@ extern "C" int fpm_kron_gnn_layer_fwd_ord(const float* X, int C, int B, int n1ma
     if (B == 0) return 0;
     FPM_CHECK_ARG(n1max >= 1 && n1max <= 1024, "gnn_layer: n1max must be in [1, 1024]");
     FPM_CHECK_ARG((long)17 * n1max * n2max * 4 < (1L << 31), "gnn_layer: a pair's state must be < 2 GiB");
-    const size_t sh = (size_t)(C == 1 ? 1 : 20) * n1max * 4;
+    size_t sh = (size_t)(C == 1 ? 1 : 20) * n1max * 4;
     const int threads = (n1max + 63) / 64 * 64;
-    void (*k)(const float*, int, int, const int*, const int*, const int*, const int*, const int*, const int*,
-              const float*, float*, float*, float*, const float*, int, const int*) =
+    gnn_kernel_t k =
         (C == 17 && gnn_sweeps_flag() == 2 && !gnn_mlp_off_flag() && !gnn_store_sc1_flag()) ? gnn_layer_kernel<17, 0, true, 2>
         : (C == 17 && gnn_sweeps_flag() == 3 && !gnn_mlp_off_flag() && !gnn_store_sc1_flag()) ? gnn_layer_kernel<17, 0, true, 3>
         : gnn_mlp_off_flag() ? (C == 1 ? gnn_layer_kernel<1, 0, false> : gnn_layer_kernel<17, 0, false>)
         : gnn_store_sc1_flag() ? (C == 1 ? gnn_layer_kernel<1, 16> : gnn_layer_kernel<17, 16>)
                                : (C == 1 ? gnn_layer_kernel<1> : gnn_layer_kernel<17>);
+    if (gnn_resident(n1max)) {
+        k = gnn_resident_kernel(C);
+        sh = gnn_resident_lds(C, n1max);
+    }
     if (sh > 65536) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     hipLaunchKernelGGL(k, dim3(pair_grid(n2max, B)), dim3(threads), sh, (hipStream_t)stream, X, n1max, n2max, ptr1,
                        nbr1, ptr2, nbr2, n1, n2, params, Xout, zbuf, vpart, cls_w, B, ord2);

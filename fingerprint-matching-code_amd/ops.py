@@ -1037,6 +1037,15 @@ def gnn_layer(X, C, B, n1max, n2max, csr1, csr2, n1, n2, params, Xout, zbuf, vpa
               _p(params), _p(Xout), _p(zbuf), _p(vpart), _p(cls_w), _p(ord2), _stream(X))
 
 
+def gnn_resident_blocks(C, n1max):
+    """Workgroups of the GNN layer's kernel for (C, n1max), under the current tuning, resident per CU
+    (the runtime's occupancy query; no launch)."""
+    nb = int(_lib.load().fpm_gnn_resident_blocks(int(C), int(n1max)))
+    if nb < 0:
+        raise _lib.FpmError(_lib.load().fpm_last_error().decode(errors="replace"))
+    return nb
+
+
 def node_classifier(X, B, n1max, n2max, w, b, out, vpart=None):
     _dev(X, w, b, out, vpart)
     _shape(X, (B, 17, n2max, n1max), "node_classifier X")

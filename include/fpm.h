@@ -178,6 +178,10 @@ int fpm_gemm_x3out(const void* A, long lda, const void* B, long ldb, int M, int 
  *                16-B aligned (0: one 4-B load per row and position); same products, same order
  *   "gnn_sweeps" (FPM_GNN_SWEEPS, default 1): the 17-channel GNN layer's graph-2 neighbour rows
  *                read in 1 / 2 / 3 channel-group sweeps (same sums, same order; 2 and 3 measured slower)
+ *   "gnn_form" (FPM_GNN_FORM, default 1): the GNN layer for boxes of at most 256 keypoints on the
+ *                resident kernel (1: 64 registers and 72-B LDS node rows, 8 workgroups of 256 threads per
+ *                CU) or on the kernel of the larger boxes (0: 6 per CU); the other gnn_* switches are
+ *                variants of form 0 and take the launch there; same arithmetic in the same order
  *   "scatter_f32_rows" (FPM_SCATTER_F32_ROWS, default 0): the bf16 scatter SplineConv backward also
  *                writes its fp32 cell rows of dY (nothing reads them; gradients unchanged)
  *   "afau_head_split" (default 0 = by launch size): the cross-set attention's 16 heads per 16-row
@@ -291,7 +295,8 @@ int fpm_edge_diff_padded(const float* x, const int* src, const int* dst, const i
  * params: fpm_gnn_param_count(C) floats = lin_l.weight^T [C][16], lin_l.bias [16],
  * lin_r.weight^T [C][16], n_self_func.0.weight^T [C][16], n_self_func.0.bias [16],
  * n_self_func.2.weight^T [16][16], n_self_func.2.bias [16], classifier.weight [16], classifier.bias.
- * n1max <= 1024; neighbour lists ascending (the plan CSR). */
+ * n1max <= 1024; neighbour lists ascending (the plan CSR); ptr1 / ptr2 index the whole batch's nbr1 /
+ * nbr2 and do not decrease (a pair's lists start at ptr[b * nmax]). */
 int fpm_kron_gnn_layer_fwd(const float* X, int C, int B, int n1max, int n2max, const int* ptr1, const int* nbr1,
                            const int* ptr2, const int* nbr2, const int* n1, const int* n2, const float* params,
                            float* Xout, float* zbuf, float* vpart, const float* cls_w, void* stream);
@@ -302,6 +307,9 @@ int fpm_kron_gnn_layer_fwd_ord(const float* X, int C, int B, int n1max, int n2ma
                                const float* params, float* Xout, float* zbuf, float* vpart, const float* cls_w,
                                const int* ord2, void* stream);
 int fpm_gnn_param_count(int C);
+/* Workgroups of the layer's kernel for this (C, n1max), under the current tuning, that one CU holds
+ * at a time (the runtime's occupancy query; nothing is launched).  Negative on error. */
+int fpm_gnn_resident_blocks(int C, int n1max);
 /* final classifier (ngm.py:368-369): s[b][i][j] = w . X[b][:, j, i] + bias; with vpart (NULL =
  * all 17 channels): s = vpart + w[16] X[b][16, j, i] + bias */
 int fpm_node_classifier(const float* X, int B, int n1max, int n2max, const float* w, const float* bias,

@@ -54,6 +54,7 @@ for (var, C), ts in res.items():
     ms = sorted(ts)[len(ts) // 2]
     gb = B * n * n * 4 * (C + 17) / 1e9        # algorithmic: X in (C channels) + 16 channels + z out
     print("%-40s C=%-2d median %.3f ms (min %.3f)  %.0f GB/s algorithmic" % (var, C, ms, min(ts), gb / (ms / 1e3)))
+    print("%-40s C=%-2d rounds %s" % (var, C, " ".join("%.3f" % t for t in ts)))
 
 # phase split (timing only): graph-2 and/or graph-1 neighbour lists emptied (ptr all zero)
 if os.environ.get("GNN_PHASES"):

@@ -3,7 +3,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/pmc_gnn; mkdir -p $O
-p() { local n=$1; shift; timeout -s KILL 120 rocprofv3 --pmc "$@" --kernel-include-regex "gnn_layer_kernel<17" -d $O/$n -o run --output-format csv -- python tools/gnn_bench.py > $O/$n.log 2>&1; }
+p() { local n=$1; shift; timeout -s KILL 120 rocprofv3 --pmc "$@" --kernel-include-regex "gnn_layer_(resident_)?kernel<17" -d $O/$n -o run --output-format csv -- python tools/gnn_bench.py > $O/$n.log 2>&1; }
 p a FETCH_SIZE GRBM_GUI_ACTIVE && p b WRITE_SIZE TCC_HIT_sum TCC_MISS_sum && p c SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VMEM_RD SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_WAIT_ANY
 for n in a b c; do f=$(find $O/$n -name "*counter_collection.csv" | head -1); python - "$f" <<'PY'
 import csv, sys, collections

@@ -44,6 +44,8 @@ def work(n, E, rows_per_node):
         # (match substring, kind, per-pair work over all calls of one forward, calls per pair, note)
         ("gnn_layer_kernel<17", "bytes", (17 + 17) * f4 + (17 + 2) * f4, 2, "layers 2-3: X in, 16 ch + z / vpart + z out"),
         ("gnn_layer_kernel<1,", "bytes", 18 * f4, 1, "layer 1: 1 ch in, 16 ch + z out"),
+        ("gnn_layer_resident_kernel<17", "bytes", (17 + 17) * f4 + (17 + 2) * f4, 2, "layers 2-3, boxes <= 256"),
+        ("gnn_layer_resident_kernel<1,", "bytes", 18 * f4, 1, "layer 1, boxes <= 256"),
         ("sinkhorn_reg_kernel", "bytes", 4 * 2 * f4, 4, "3 GNN Sinkhorns (20 it) + final (10 it), s in, out out"),
         ("sinkhorn_lform_kernel", "bytes", 4 * 2 * f4, 4, "3 GNN Sinkhorns (20 it) + final (10 it), s in, out out"),
         ("sinkhorn_stream_kernel", "bytes", 4 * 2 * f4, 4, "same, n > 256"),
