@@ -2,66 +2,18 @@
 rows, eight workgroups per CU; ``gnn_form`` 1) against the kernel it replaced there (``gnn_form`` 0),
 bit for bit, on random X and random weights over hand-built graphs.
 
-The graphs are built on the CPU (``_graphs``) so that the shapes the kernel can go wrong at are
+The graphs are built on the CPU (``gnn_ref._graphs``) so that the shapes the kernel can go wrong at are
 certain to occur: graph-2 neighbour lists of every length 0..7 (every remainder of the batches of
 rows phase 1 keeps in flight), a graph-1 node of degree 0 and one of degree 12, pairs shorter than
 the box (the diagonal term's ``p < n1 * n2`` edge, padded nodes with empty lists), boxes that are no
 multiple of the wave, and fewer pairs than the grid's padding to 8."""
-import functools
-
 import pytest
 import torch
 
 from fpm import _lib, ops
+from gnn_ref import SHAPES, _graphs
 
 DEV = torch.device("cuda", 0)
-
-# (n1max, n2max, n1 per pair, n2 per pair)
-SHAPES = {
-    "40x24": (40, 24, (40, 33, 13), (24, 19, 9)),
-    "40x40": (40, 40, (40, 33, 13), (40, 35, 9)),
-    "64x24": (64, 24, (64, 57, 13), (24, 19, 9)),
-    "64x40": (64, 40, (64, 57, 13), (40, 35, 9)),
-    "256x256": (256, 256, (256, 200), (256, 131)),
-}
-
-
-def _csr(lists, nmax):
-    """Batch CSR of per-pair neighbour lists: ptr (B * nmax + 1, global, non-decreasing), nbr (local ids)."""
-    ptr, nbr = [0], []
-    for pair in lists:
-        assert len(pair) == nmax
-        for row in pair:
-            assert row == sorted(set(row))
-            nbr += row
-            ptr.append(len(nbr))
-    return torch.tensor(ptr, dtype=torch.int32), torch.tensor(nbr + [0], dtype=torch.int32)
-
-
-def _pick(g, n, k):
-    return sorted(torch.randperm(n, generator=g)[:k].tolist())
-
-
-@functools.lru_cache(maxsize=None)
-def _graphs(shape):
-    """CPU tensors (ptr1, nbr1, ptr2, nbr2, n1, n2) and the per-pair Python lists behind them."""
-    n1max, n2max, n1s, n2s = SHAPES[shape]
-    g = torch.Generator().manual_seed(1000 + n1max * 7 + n2max)
-    l1, l2 = [], []
-    for n1, n2 in zip(n1s, n2s):
-        assert n1 >= 13 and n2 >= 9
-        # graph 1: node 0 has no neighbour, node 1 has twelve, the rest 1..9; padded nodes none
-        deg = [0, 12] + [1 + int(torch.randint(0, 9, (1,), generator=g)) for _ in range(n1 - 2)]
-        l1.append([_pick(g, n1, k) for k in deg] + [[] for _ in range(n1max - n1)])
-        # graph 2: node d has d % 8 neighbours (every length 0..7), shuffled over the nodes
-        order = torch.randperm(n2, generator=g).tolist()
-        rows = [None] * n2
-        for k, d in enumerate(order):
-            rows[d] = _pick(g, n2, k % 8)
-        l2.append(rows + [[] for _ in range(n2max - n2)])
-    ptr1, nbr1 = _csr(l1, n1max)
-    ptr2, nbr2 = _csr(l2, n2max)
-    return (ptr1, nbr1, ptr2, nbr2, torch.tensor(n1s, dtype=torch.int32), torch.tensor(n2s, dtype=torch.int32)), l1, l2
 
 
 @pytest.mark.parametrize("shape", sorted(SHAPES))
