@@ -44,6 +44,15 @@ makes a selection's CSR group tables on the host (``subject_groups``); the queri
 on the device (``ops.group_scores``: max, or a mean in a fixed order) between the coarse scores and
 ``rank_select`` -- the shortlist then counts subjects -- and between the exact scores and ``rank_topk``.
 The exact forward still runs over plain entry lists, so every per-pair output is the entry-level call's.
+
+Query stages: ``identify`` and ``identify_many`` are the same sequence for every form (one probe or a probe
+set, entries or subjects, with or without a shortlist): the checks (``_check_eager``, ``_check_query``;
+``_check_many``), the coarse scores (``coarse_scores`` / ``coarse_scores_many``), the shortlist stage
+(``_shortlist``: the file's one ``rank_select`` and its one coarse fuse; ``_all_lists`` without a shortlist), the
+exact stage (one probe: the plain ``identify(select=...)`` per probe, the shared side 0 with the probe's
+SplineConv live; a probe set: ``_exact_many``, groups of ragged pair lists with both sides cached), the ranking
+(``_entry_ranking`` or ``_subject_ranking``) and ``_attach``, which puts the result keys on the dicts.  The stages
+take and return tensors and run on CPU tensors as they are; the device contexts stay in the callers.
 """
 import contextlib
 import hashlib
@@ -375,23 +384,14 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
     straight to the pinned host tensor, so the device holds the bf16 rows plus one sub-batch at most.
     ``subjects``: one integer label >= 0 per graph (``GalleryIndex.subject``), checked before any GPU work;
     every other field of the index is the same with or without it."""
-    if net.training:
-        raise FpmError("enroll: inference only (call net.eval())")
-    if layout not in LAYOUTS:
-        raise FpmError("enroll: layout must be one of %s" % (LAYOUTS,))
+    sc_mode = _check_enroll(net, "enroll", layout, sc_mode)
     dev = torch.device(device)
-    sc_mode = sc_mode or ("f32" if net.dtype_mode == "f32" else "bf16")
-    if sc_mode not in ("f32", "bf16") or (sc_mode == "bf16" and net.dtype_mode != "bf16"):
-        raise FpmError("enroll: sc_mode must be 'f32', or 'bf16' on a dtype='bf16' net")
     graphs = list(graphs)
     if not graphs:
         raise FpmError("enroll: empty gallery")
     if subjects is not None:
         subjects = _check_subjects("enroll", subjects, len(graphs))
     wp = net.packed(dev)
-    f32 = sc_mode == "f32"
-    W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
-    code = ops.F32 if f32 else ops.BF16
     ys, srcs, dsts, pss, cnts = [], [], [], [], []
     total = sum(int(g["n"]) for g in graphs)
     y16 = y_host = None
@@ -407,12 +407,7 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
             Bs, nn_, E = len(sub), len(sub) * nmax, int(src.numel())
             nv = n.to(dev)
             plan = ops.spline_plan(src, dst, ps, nn_, nmax, int(cnt.max()))
-            x_op = x0 if f32 else ops.cast_bf16(x0)
-            yws = ops.spline_y_ws(code, E, nn_, dev)
-            h = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=x_op.dtype)
-            ops.spline_conv(x_op, plan, E, nn_, nmax, nv, W0, wp["bias0"], yws, 0, out_t=h)
-            y = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
-            ops.spline_conv(h, plan, E, nn_, nmax, nv, W1, wp["bias1"], yws, 1, xres=x0, out_f=y)
+            y = net._spline_layers(wp, sc_mode == "f32", x0, plan, E, nn_, nmax, nv)
             # padded -> ragged rows, edges back to graph-local ids (off the hot path: torch indexing)
             keep = (torch.arange(nmax, device=dev)[None, :] < nv.view(-1, 1)).reshape(-1)
             yr = y[keep]
@@ -505,9 +500,6 @@ def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subject
     G, nmax, D = int(n_h.numel()), int(P.shape[1]), C.NODE_FEATURE_DIM
     step = max(1, int(batch))
     wp = net.packed(dev)
-    f32 = sc_mode == "f32"
-    W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
-    code = ops.F32 if f32 else ops.BF16
     row_off_h = torch.cat([torch.zeros(1, dtype=torch.int64), n_h.cumsum(0)])
     total = int(row_off_h[-1])
     srcs, dsts, pss, cnts = [], [], [], []
@@ -537,12 +529,7 @@ def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subject
             cnt = gb.edge_off_host[1:] - gb.edge_off_host[:-1]
             nn_, E = Bs * m, int(gb.src.numel())
             plan = ops.spline_plan(gb.src, gb.dst, gb.pseudo, nn_, m, int(cnt.max()))
-            x_op = x0 if f32 else ops.cast_bf16(x0)
-            yws = ops.spline_y_ws(code, E, nn_, dev)
-            h = torch.empty(nn_, D, device=dev, dtype=x_op.dtype)
-            ops.spline_conv(x_op, plan, E, nn_, m, nv, W0, wp["bias0"], yws, 0, out_t=h)
-            yb = torch.empty(nn_, D, device=dev, dtype=torch.float32)
-            ops.spline_conv(h, plan, E, nn_, m, nv, W1, wp["bias1"], yws, 1, xres=x0, out_f=yb)
+            yb = net._spline_layers(wp, sc_mode == "f32", x0, plan, E, nn_, m, nv)
             # padded -> ragged rows (and their bf16 copy) in one pass, into their place in the index
             r0, r1 = int(row_off_h[g0]), int(row_off_h[g1])
             ops.rows_pack(yb, nv, m, row_off[g0:g1 + 1] - r0, out32=stage if y is None else y[r0:r1],
@@ -809,6 +796,15 @@ def _launch_by_route(rt, cf, dst, launch):
         dst[pos_d] = part
 
 
+def _coef_rows(wp, w_probe, w_entry, coef):
+    """The forward's own affinity coefficients of a chunk's pairs, from the global features of each
+    pair's probe and entry ((B, 512) each), into the first B rows of the chunk's scratch ``coef`` -> those
+    rows (the one-probe pass and the pair-list pass compute the same rows)."""
+    cf = coef[:w_probe.shape[0]]
+    ops.coef_tanh(ops.global_weights(w_probe, w_entry), wp["aff_wT"], wp["aff_b"], cf)
+    return cf
+
+
 def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk, coarse="fused"):
     """One probe's coarse scores over the entries ``sel`` into ``out`` (len(sel),).  ``coarse``: the
     route (``coarse_routes``; host copy of n: no synchronisation)."""
@@ -829,9 +825,7 @@ def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk, coarse="fused"):
             ops._coarse_score_op(kernel, rows, index.row_off, sel_d[b0:b1][pos_d].contiguous(), yp, cf, C.SK_ITER_NUM,
                                  net.tau, dst, sel32[b0:b1][pos], index.row_off_host, None)
 
-        gw = ops.global_weights(w0[:b1 - b0], index.w[sel_d[b0:b1].long()])
-        cf = coef[:b1 - b0]
-        ops.coef_tanh(gw, wp["aff_wT"], wp["aff_b"], cf)
+        cf = _coef_rows(wp, w0[:b1 - b0], index.w[sel_d[b0:b1].long()], coef)
         _launch_by_route(rt[b0:b1], cf, out[b0:b1], launch)
 
 
@@ -909,9 +903,10 @@ def _subject_ranking(rows, ents, offs, labels, fuse, topk, dev):
     (L_i,) on the device; ents[i]: their entry numbers (L_i,) host; offs[i]: (M + 1,) host offsets of the M
     subjects into them; labels (Q, M) device int64.  The rows are padded with NaN to one matrix, each
     with its own group structure (``ops.group_scores``), then ``ops.rank_topk`` over the M subjects
-    -> subject_score (Q, M), top_subject (Q, k) int64, top_score (Q, k), top_idx (Q, k) int32: the entry of
-    each top subject's best impression (-1 for a subject with no pair)."""
-    Q, M = len(rows), int(labels.shape[1])
+    -> the result keys (``_subject_keys``): subjects, subject_score (Q, M), top_subject (Q, k) int64,
+    top_score (Q, k), top_idx (Q, k) int32: the entry of each top subject's best impression (-1 for a
+    subject with no pair)."""
+    Q = len(rows)
     L = max(1, max(int(r.numel()) for r in rows))
     mat = torch.full((Q, L), float("nan"), device=dev, dtype=torch.float32)
     ent = torch.full((Q, L), -1, dtype=torch.int32)
@@ -921,12 +916,89 @@ def _subject_ranking(rows, ents, offs, labels, fuse, topk, dev):
     off = torch.stack([o.to(torch.int32) for o in offs])
     pos = torch.arange(L, dtype=torch.int32).view(1, L).expand(Q, L).contiguous()
     gsc, gb = ops.group_scores(mat, off.to(dev), pos.to(dev), fuse, off_host=off, pos_host=pos)
-    k = max(1, min(int(topk), M, 128))
-    ti, ts = ops.rank_topk(gsc, k)
+    ti, ts = _rank_topk(gsc, topk)
     bp = torch.gather(gb, 1, ti.long())
     te = torch.gather(ent.to(dev), 1, bp.clamp(min=0).long())
     te = torch.where(bp >= 0, te, torch.full_like(te, -1))
-    return gsc, torch.gather(labels, 1, ti.long()), ts, te
+    return _subject_keys(labels, gsc, ti, ts, te)
+
+
+def _rank_topk(scores, topk):
+    """``ops.rank_topk`` of (Q, X) scores for the ``topk`` a query asked for: k is clamped to the X entries
+    or subjects there are and to the kernel's 128."""
+    return ops.rank_topk(scores, max(1, min(int(topk), int(scores.shape[1]), 128)))
+
+
+def _entry_ranking(scores, ent_d, topk):
+    """The entry ranking of (Q, L) exact scores; ``ent_d``: the entry number of each column, (L,) shared
+    by the probes or (Q, L) -> the result keys top_idx (Q, k) int32 entry numbers, top_score (Q, k)."""
+    ti, ts = _rank_topk(scores, topk)
+    ti = ent_d[ti.long()] if ent_d.dim() == 1 else torch.gather(ent_d, 1, ti.long())
+    return dict(top_idx=ti.to(torch.int32), top_score=ts)
+
+
+def _subject_keys(labels, gsc, ti, ts, te):
+    """The result keys of a subject ranking: labels (Q, S) int64 the ranked subjects, gsc (Q, S) their
+    fused scores, ti / ts (Q, k) ``rank_topk`` over gsc, te (Q, k) int32 each top subject's best entry."""
+    return dict(subjects=labels, subject_score=gsc, top_subject=torch.gather(labels, 1, ti.long()), top_score=ts,
+                top_idx=te)
+
+
+def _shortlist_keys(subj, names, csc, call):
+    """The result keys of the coarse stage (``_shortlist``'s names and scores, the coarse matrix)."""
+    if subj:
+        return dict(short_subject=names, coarse_subject_score=csc, coarse_all=call)
+    return dict(short_idx=names.to(torch.int32), coarse_score=csc, coarse_all=call)
+
+
+def _ragged_keys(ents, offs, dev):
+    """The result keys of subject-major entry lists: short_idx the entries, short_off the subjects' (M + 1,)
+    offsets into them, int32 on ``dev``."""
+    return dict(short_idx=[e.to(torch.int32).to(dev) for e in ents], short_off=[o.to(torch.int32).to(dev) for o in offs])
+
+
+def _attach(outs, keys):
+    """The one place the query layer's keys go onto the per-probe result dicts: row i of every value
+    (a (Q, ...) tensor or a list of Q tensors) to outs[i]."""
+    for i, o in enumerate(outs):
+        for name, v in keys.items():
+            o[name] = v[i]
+
+
+def _shortlist(call, sel, M, own=None, gt=None, impressions="all"):
+    """The shortlist stage of every query form.  ``call`` (Q, Gs): the coarse scores of Q probes over the
+    selection ``sel`` (Gs,) host int64; ``M``: the shortlist asked for, clamped here to what there is;
+    ``own`` (Q, Gs) host bool or None: positions that count as -inf and are left out (the probe's own
+    entry); ``gt``: the selection's group tables (``subject_groups``) for a shortlist of subjects -- the
+    coarse scores fused per subject by max whatever the exact stage's fuse is (a subject stays in if any
+    of its impressions matches) -- with ``impressions`` "all" or "best" (each subject's best by the
+    coarse score); None: a shortlist of entries.  The M best by ``ops.rank_select``, copied to the host
+    once: the lists shape the host-side batches of the exact stage.
+    -> (ents: per probe the exact stage's entry numbers, host int64 -- (M,) in coarse-rank order, or
+    subject-major in the coarse-rank order of the subjects; offs: per probe the subjects' (M + 1,) host
+    offsets into ents, None for entries; names (Q, M) int64 on call's device: the shortlisted entry
+    numbers or subject labels; csc (Q, M): their coarse scores)."""
+    dev = call.device
+    ranked = call if own is None else call.masked_fill(own.to(dev), float("-inf"))
+    if gt is None:
+        M = min(M, int(sel.numel()) - (own is not None))
+    else:
+        M = min(M, int(gt["labels"].numel()))
+        ranked, cb = ops.group_scores(ranked, gt["off_d"], gt["pos_d"], "max", off_host=gt["off"], pos_host=gt["pos"])
+    pos, csc = ops.rank_select(ranked, M)
+    if gt is None:
+        names = sel.to(dev)[pos.long()]
+        return list(names.cpu()), None, names, csc
+    lists = _subject_entry_lists(gt, pos.cpu(), cb.cpu() if impressions == "best" else None, own)
+    return [sel[p] for p, _ in lists], [so for _, so in lists], gt["labels_d"][pos.long()], csc
+
+
+def _check_eager(net, what):
+    """The refusals of every forward over cached rows (``identify``, and the probe-set calls)."""
+    if net.training:
+        raise FpmError("%s: inference only (call net.eval()); training through an index is not supported" % what)
+    if net.use_graphs:
+        raise FpmError("%s: cached-gallery forwards are eager; switch HIP-graph replay (use_graphs) off" % what)
 
 
 def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None, shortlist=None,
@@ -934,108 +1006,48 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
     """``Net.identify``: see there."""
     _check_coarse(coarse, "identify")
     subj = _check_by("identify", index, by, fuse, impressions, shortlist)
-    if net.training:
-        raise FpmError("identify: inference only (call net.eval()); training through an index is not supported")
-    if net.use_graphs:
-        raise FpmError("identify: cached-gallery forwards are eager; switch HIP-graph replay (use_graphs) off")
+    _check_eager(net, "identify")
     if score not in SCORES:
         raise FpmError("identify: score must be one of %s" % (SCORES,))
     _check_query(net, index, "identify")
-    if shortlist is not None:
-        if subj:
-            return _identify_shortlist_subject(net, probes, index, topk, select, score, chunks, shortlist, coarse, fuse,
-                                               impressions)
-        return _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist, coarse)
     single = isinstance(probes, dict)
     plist = [probes] if single else list(probes)
+    dev = index.device
+    if shortlist is not None:
+        M = _check_shortlist(shortlist, "identify")
+        sel = _select_host(index, select, "identify")
+        gt = index.subject_groups(sel) if subj else None
+        if not plist:
+            return []
+        call = coarse_scores(net, plist, index, select=sel, coarse=coarse)
+        with torch.cuda.device(dev):
+            ents, offs, names, csc = _shortlist(call, sel, M, gt=gt, impressions=impressions)
+        # the exact stage, a probe at a time: the plain ``identify`` over its list alone, in that order
+        outs = [identify(net, p, index, topk=topk, select=e, score=score, chunks=chunks) for p, e in zip(plist, ents)]
+        keys = _shortlist_keys(subj, names, csc, call)
+        if subj:
+            with torch.cuda.device(dev):
+                keys.update(_subject_ranking([o[score] for o in outs], ents, offs, names, fuse, topk, dev))
+            keys.update(_ragged_keys(ents, offs, dev))
+        _attach(outs, keys)
+        return outs[0] if single else outs
     outs, sel = [], None
-    with _eager_prologue(net), torch.cuda.device(index.device):
+    with _eager_prologue(net), torch.cuda.device(dev):
         for p in plist:
             bt, sel = probe_batch(p, index, select)
             outs.append(net.run(bt, chunks=chunks))
-        if outs and subj:
-            # one structure for all probes: the selection's groups, positions in selection order
-            gt = index.subject_groups(sel)
+        if outs:
             sc = torch.stack([o[score].view(-1) for o in outs])
-            gsc, gb = ops.group_scores(sc, gt["off_d"], gt["pos_d"], fuse, off_host=gt["off"], pos_host=gt["pos"])
-            k = max(1, min(int(topk), int(gt["labels"].numel()), 128))
-            ti, ts = ops.rank_topk(gsc, k)
-            te = index._sel[1]["idx"][torch.gather(gb, 1, ti.long()).long()]
-            tl = gt["labels_d"][ti.long()]
-            for i, o in enumerate(outs):
-                o["subjects"], o["subject_score"] = gt["labels_d"], gsc[i]
-                o["top_subject"], o["top_score"], o["top_idx"] = tl[i], ts[i], te[i]
-        elif outs:
-            k = max(1, min(int(topk), int(sel.numel()), 128))
-            sc = torch.stack([o[score].view(-1) for o in outs])
-            ti, ts = ops.rank_topk(sc, k)
-            sel_d = index._sel[1]["idx"]
-            ti = sel_d[ti.long()]
-            for i, o in enumerate(outs):
-                o["top_idx"], o["top_score"] = ti[i], ts[i]
-    return outs[0] if single else outs
-
-
-def _identify_shortlist_subject(net, probes, index, topk, select, score, chunks, shortlist, coarse, fuse, impressions):
-    """``identify(by="subject", shortlist=M)``: per probe the coarse pass over ``select``, fused per subject
-    by max whatever ``fuse`` is (a subject stays in if any of its impressions matches), the M best
-    subjects (``ops.rank_select``), the plain ``identify`` over their impressions (all of them, or each
-    subject's best by the coarse score), subject-major in coarse-rank order, and the subject ranking of
-    the exact scores (``_subject_ranking``)."""
-    M = _check_shortlist(shortlist, "identify")
-    sel = _select_host(index, select, "identify")
-    gt = index.subject_groups(sel)
-    M = min(M, int(gt["labels"].numel()))
-    single = isinstance(probes, dict)
-    plist = [probes] if single else list(probes)
-    if not plist:
-        return []
-    dev = index.device
-    call = coarse_scores(net, plist, index, select=sel, coarse=coarse)
-    with torch.cuda.device(dev):
-        cg, cb = ops.group_scores(call, gt["off_d"], gt["pos_d"], "max", off_host=gt["off"], pos_host=gt["pos"])
-        spos, csc = ops.rank_select(cg, M)
-        labs = gt["labels_d"][spos.long()]
-        spos_h = spos.cpu()                     # the shortlist shapes the host-side batch: one copy per query
-        best_h = cb.cpu() if impressions == "best" else None
-    lists = _subject_entry_lists(gt, spos_h, best_h)
-    outs, ents = [], []
-    for i, p in enumerate(plist):
-        ent = sel[lists[i][0]]
-        o = identify(net, p, index, topk=topk, select=ent, score=score, chunks=chunks)
-        o["short_subject"], o["coarse_subject_score"], o["coarse_all"] = labs[i], csc[i], call[i]
-        o["short_idx"] = ent.to(torch.int32).to(dev)
-        o["short_off"] = lists[i][1].to(torch.int32).to(dev)
-        outs.append(o)
-        ents.append(ent)
-    with torch.cuda.device(dev):
-        gsc, tl, ts, te = _subject_ranking([o[score] for o in outs], ents, [l[1] for l in lists], labs, fuse, topk, dev)
-    for i, o in enumerate(outs):
-        o["subjects"], o["subject_score"] = labs[i], gsc[i]
-        o["top_subject"], o["top_score"], o["top_idx"] = tl[i], ts[i], te[i]
-    return outs[0] if single else outs
-
-
-def _identify_shortlist(net, probes, index, topk, select, score, chunks, shortlist, coarse="fused"):
-    """``identify(shortlist=M)``: per probe the coarse pass over ``select``, the M best entries
-    (``ops.rank_select``), and the plain ``identify`` over exactly those, in coarse-rank order."""
-    M = _check_shortlist(shortlist, "identify")
-    sel = _select_host(index, select, "identify")
-    M = min(M, int(sel.numel()))
-    single = isinstance(probes, dict)
-    plist = [probes] if single else list(probes)
-    outs = []
-    if not plist:
-        return outs
-    call = coarse_scores(net, plist, index, select=sel, coarse=coarse)
-    with torch.cuda.device(index.device):
-        pos, csc = ops.rank_select(call, M)
-        short = sel.to(index.device)[pos.long()].to(torch.int32)
-        short_host = short.cpu()                # the shortlist shapes the host-side batch: one copy per query
-    for i, p in enumerate(plist):
-        o = identify(net, p, index, topk=topk, select=short_host[i].long(), score=score, chunks=chunks)
-        o["short_idx"], o["coarse_score"], o["coarse_all"] = short[i], csc[i], call[i]
-        outs.append(o)
+            ent_d = index._sel[1]["idx"]
+            if subj:
+                # one structure for all probes: the selection's groups, positions in selection order
+                gt = index.subject_groups(sel)
+                gsc, gb = ops.group_scores(sc, gt["off_d"], gt["pos_d"], fuse, off_host=gt["off"], pos_host=gt["pos"])
+                ti, ts = _rank_topk(gsc, topk)
+                labs = gt["labels_d"].view(1, -1).expand(len(outs), -1)
+                _attach(outs, _subject_keys(labs, gsc, ti, ts, ent_d[torch.gather(gb, 1, ti.long()).long()]))
+            else:
+                _attach(outs, _entry_ranking(sc, ent_d, topk))
     return outs[0] if single else outs
 
 
@@ -1068,10 +1080,7 @@ def _check_many(net, probes, index, what):
     if not isinstance(index, GalleryIndex):
         raise FpmError("%s: index must be a GalleryIndex (Net.enroll)" % what)
     _check_probe_set(probes, index, what)
-    if net.training:
-        raise FpmError("%s: inference only (call net.eval()); training through an index is not supported" % what)
-    if net.use_graphs:
-        raise FpmError("%s: cached-gallery forwards are eager; switch HIP-graph replay (use_graphs) off" % what)
+    _check_eager(net, what)
     _check_query(net, index, what)
 
 
@@ -1154,10 +1163,7 @@ def coarse_scores_many(net, probes, index, probe_select=None, select=None, coars
             dst = flat[p0:p1] if where is None else torch.empty(p1 - p0, device=dev, dtype=torch.float32)
             q, g = psel[qi], sel[gi]
             rt = coarse_routes(nq[qi], ng[gi], coarse)
-            # the forward's own coefficients of each pair (the one-probe pass computes the same rows)
-            gw = ops.global_weights(probes.w[q.to(dev)].contiguous(), index.w[g.to(dev)].contiguous())
-            cf = coef[:p1 - p0]
-            ops.coef_tanh(gw, wp["aff_wT"], wp["aff_b"], cf)
+            cf = _coef_rows(wp, probes.w[q.to(dev)].contiguous(), index.w[g.to(dev)].contiguous(), coef)
             q32, g32 = q.to(torch.int32), g.to(torch.int32)
 
             def launch(kernel, pos, pos_d, cf, dst):
@@ -1201,10 +1207,51 @@ def probe_groups(n_probe_host, pairs_per_probe, group_pairs):
     return groups
 
 
+def _all_lists(Q, sel, dev, own=None, gt=None):
+    """The entry lists of a probe-set query without a shortlist, in ``_shortlist``'s form: every entry of
+    the selection ``sel`` (subject-major when ``gt`` is given) but a probe's ``own`` -> (ents, offs, names)."""
+    if gt is not None:
+        S = int(gt["labels"].numel())
+        lists = _subject_entry_lists(gt, torch.arange(S, dtype=torch.int32).view(1, S).expand(Q, S), None, own)
+        return [sel[p] for p, _ in lists], [so for _, so in lists], gt["labels_d"].view(1, S).expand(Q, S)
+    Gs = int(sel.numel())
+    names = sel.to(dev).view(1, Gs).expand(Q, Gs)
+    if own is not None:
+        names = names[~own.to(dev)].view(Q, Gs - 1)
+    return list(names.cpu()), None, names                    # the pair lists shape the host-side batches: one copy
+
+
+def _exact_many(net, probes, index, psel, ents, score, chunks, group_pairs):
+    """The exact stage of a probe-set query: probe psel[i] against the entries ents[i] (host int64, ragged
+    from probe to probe when the lists are subjects' impressions), in groups of probes (``probe_groups``)
+    whose pair lists run as one batch each (``_run_pairs``) -> (outs: per probe the batch's outputs
+    sliced to its own pairs, with "group" = (group number, first pair, end pair); rows: per probe its
+    ``score`` row (L_i,))."""
+    per = torch.tensor([int(e.numel()) for e in ents], dtype=torch.int64)
+    outs, rows = [None] * len(ents), [None] * len(ents)
+    for gi, grp in enumerate(probe_groups(probes.n[psel], per, group_pairs)):
+        pairs = torch.cat([torch.stack([psel[i].expand(int(per[i])), ents[i]], 1) for i in grp])
+        o = _run_pairs(net, probes, index, pairs, chunks)
+        Bg, b0 = int(pairs.shape[0]), 0
+        for i in grp:
+            b1 = b0 + int(per[i])
+            d = {key: (v[b0:b1] if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == Bg else v)
+                 for key, v in o.items()}
+            d["group"] = (gi, b0, b1)
+            rows[i] = d[score].view(-1)
+            outs[i] = d
+            b0 = b1
+    return outs, rows
+
+
 def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
                   coarse="fused", chunks=None, group_pairs=1024, exclude_self=False, by=None, fuse="max",
                   impressions="all"):
-    """``Net.identify_many``: see there."""
+    """``Net.identify_many``: see there.  Subject-level (``by="subject"``) the exact stage's pair lists are
+    ragged (a subject has as many pairs as impressions) and the exact scores are fused over one structure
+    per probe (``_subject_ranking``).  ``exclude_self`` is then leave-one-out: the probe's own entry counts
+    as -inf in the coarse fuse and is left out of its pair list and of its group; its subject's other
+    impressions stay, and a subject emptied that way ranks last (NaN)."""
     what = "identify_many"
     _check_coarse(coarse, what)
     subj = _check_by(what, index, by, fuse, impressions, shortlist)
@@ -1220,112 +1267,31 @@ def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None
     dev = index.device
     if exclude_self and Gs < 2:
         raise FpmError("%s: exclude_self needs at least two selected entries" % what)
-    if subj:
-        return _identify_many_subject(net, probes, index, topk, shortlist, psel, sel, score, coarse, chunks, group_pairs,
-                                      exclude_self, fuse, impressions)
-    short = csc = call = None
+    gt = index.subject_groups(sel) if subj else None
+    own = (psel.view(-1, 1) == sel.view(1, -1)) if exclude_self else None
+    keys = {}
     with torch.cuda.device(dev):
-        psel_d, sel_d = psel.to(dev), sel.to(dev)
-        own = (psel_d.view(-1, 1) == sel_d.view(1, -1)) if exclude_self else None
         if shortlist is not None:
-            M = min(_check_shortlist(shortlist, what), Gs - 1 if exclude_self else Gs)
+            M = _check_shortlist(shortlist, what)
             call = coarse_scores_many(net, probes, index, probe_select=psel, select=sel, coarse=coarse)
-            ranked = call if own is None else call.masked_fill(own, float("-inf"))
-            pos, csc = ops.rank_select(ranked, M)
-            ent_d = sel_d[pos.long()]                            # (Qs, M) entry numbers, coarse-rank order
-            short = ent_d.to(torch.int32)
-        elif own is None:
-            ent_d = sel_d.view(1, Gs).expand(Qs, Gs)
+            ents, offs, names, csc = _shortlist(call, sel, M, own, gt, impressions)
+            keys.update(_shortlist_keys(subj, names, csc, call))
         else:
-            # every selected entry but the probe's own
-            if not bool((own.sum(1) == 1).all()):
+            if own is not None and not subj and not bool((own.sum(1) == 1).all()):
                 raise FpmError("%s: exclude_self without a shortlist needs every probe of probe_select exactly once "
                                "in select" % what)
-            ent_d = sel_d.view(1, Gs).expand(Qs, Gs)[~own].view(Qs, Gs - 1)
-        ent = ent_d.cpu()                                        # the pair lists shape the host-side batches: one copy
-    per = int(ent.shape[1])
-    groups = probe_groups(probes.n[psel], per, group_pairs)
-    outs = [None] * Qs
-    scores = torch.empty(Qs, per, device=dev, dtype=torch.float32)
-    for gi, grp in enumerate(groups):
-        gp = torch.tensor(grp, dtype=torch.int64)
-        pairs = torch.stack([psel[gp].view(-1, 1).expand(-1, per).reshape(-1), ent[gp].reshape(-1)], 1)
-        o = _run_pairs(net, probes, index, pairs, chunks)
-        Bg = int(pairs.shape[0])
-        for k, i in enumerate(grp):
-            b0, b1 = k * per, (k + 1) * per
-            d = {key: (v[b0:b1] if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == Bg else v)
-                 for key, v in o.items()}
-            d["group"] = (gi, b0, b1)
-            scores[i] = d[score].view(-1)
-            outs[i] = d
-    with torch.cuda.device(dev):
-        k = max(1, min(int(topk), per, 128))
-        ti, ts = ops.rank_topk(scores, k)
-        ti = torch.gather(ent_d, 1, ti.long()).to(torch.int32)
-    for i, d in enumerate(outs):
-        d["top_idx"], d["top_score"] = ti[i], ts[i]
-        if short is not None:
-            d["short_idx"], d["coarse_score"], d["coarse_all"] = short[i], csc[i], call[i]
-    return outs
-
-
-def _identify_many_subject(net, probes, index, topk, shortlist, psel, sel, score, coarse, chunks, group_pairs,
-                           exclude_self, fuse, impressions):
-    """``identify_many(by="subject")`` after the shared checks.  The coarse scores are fused per subject by
-    max over one structure shared by all probes; the exact stage's pair lists are ragged (a subject has
-    as many pairs as impressions), so ``probe_groups`` takes one pair count per probe and the exact scores
-    are fused over one structure per probe (``_subject_ranking``).  ``exclude_self``: leave-one-out -- the
-    probe's own entry counts as -inf in the coarse fuse and is left out of its pair list and of its
-    group; its subject's other impressions stay, and a subject emptied that way ranks last (NaN)."""
-    what = "identify_many"
-    dev = index.device
-    Qs = int(psel.numel())
-    gt = index.subject_groups(sel)
-    S = int(gt["labels"].numel())
-    own = (psel.view(-1, 1) == sel.view(1, -1)) if exclude_self else None
-    call = csc = best_h = None
-    with torch.cuda.device(dev):
-        if shortlist is not None:
-            M = min(_check_shortlist(shortlist, what), S)
-            call = coarse_scores_many(net, probes, index, probe_select=psel, select=sel, coarse=coarse)
-            ranked = call if own is None else call.masked_fill(own.to(dev), float("-inf"))
-            cg, cb = ops.group_scores(ranked, gt["off_d"], gt["pos_d"], "max", off_host=gt["off"], pos_host=gt["pos"])
-            spos, csc = ops.rank_select(cg, M)
-            spos_h = spos.cpu()                                  # the pair lists shape the host-side batches: one copy
-            best_h = cb.cpu() if impressions == "best" else None
-            labs = gt["labels_d"][spos.long()]
-        else:
-            M = S
-            spos_h = torch.arange(S, dtype=torch.int32).view(1, S).expand(Qs, S)
-            labs = gt["labels_d"].view(1, S).expand(Qs, S)
-    lists = _subject_entry_lists(gt, spos_h, best_h, own)
-    ents = [sel[p] for p, _ in lists]
-    per = torch.tensor([int(e.numel()) for e in ents], dtype=torch.int64)
-    if int(per.min()) < 1:
+            ents, offs, names = _all_lists(Qs, sel, dev, own, gt)
+    # only a subject-level list can come out empty (exclude_self left out the one entry it had); an entry-level
+    # list has M >= 1 entries
+    if min(int(e.numel()) for e in ents) < 1:
         raise FpmError("%s: a probe is left with no pair (exclude_self took its only shortlisted entry); "
                        "raise shortlist or widen select" % what)
-    groups = probe_groups(probes.n[psel], per, group_pairs)
-    outs, rows = [None] * Qs, [None] * Qs
-    for gi, grp in enumerate(groups):
-        pairs = torch.cat([torch.stack([psel[i].expand(int(per[i])), ents[i]], 1) for i in grp])
-        o = _run_pairs(net, probes, index, pairs, chunks)
-        Bg, b0 = int(pairs.shape[0]), 0
-        for i in grp:
-            b1 = b0 + int(per[i])
-            d = {key: (v[b0:b1] if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == Bg else v)
-                 for key, v in o.items()}
-            d["group"] = (gi, b0, b1)
-            rows[i] = d[score].view(-1)
-            outs[i] = d
-            b0 = b1
+    outs, rows = _exact_many(net, probes, index, psel, ents, score, chunks, group_pairs)
     with torch.cuda.device(dev):
-        gsc, tl, ts, te = _subject_ranking(rows, ents, [so for _, so in lists], labs, fuse, topk, dev)
-    for i, d in enumerate(outs):
-        d["subjects"], d["subject_score"] = labs[i], gsc[i]
-        d["top_subject"], d["top_score"], d["top_idx"] = tl[i], ts[i], te[i]
-        d["short_idx"] = ents[i].to(torch.int32).to(dev)
-        d["short_off"] = lists[i][1].to(torch.int32).to(dev)
-        if call is not None:
-            d["short_subject"], d["coarse_subject_score"], d["coarse_all"] = labs[i], csc[i], call[i]
+        if subj:
+            keys.update(_subject_ranking(rows, ents, offs, names, fuse, topk, dev))
+            keys.update(_ragged_keys(ents, offs, dev))
+        else:
+            keys.update(_entry_ranking(torch.stack(rows), names, topk))
+    _attach(outs, keys)
     return outs

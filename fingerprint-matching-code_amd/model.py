@@ -422,8 +422,6 @@ class Net(nn.Module):
         ``x_op``: this side's bf16 operand rows when the caller cast the whole batch up front."""
         dev = bt.device
         f32 = self._sc_f32(bt)
-        op = torch.float32 if f32 else torch.bfloat16
-        W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
         nn_ = bt.B * bt.nmax[side]
         E = bt.E[side]
         if plan is None:
@@ -435,27 +433,46 @@ class Net(nn.Module):
             # enrolled gallery: no SplineConv here, the cached rows gathered into the padded box (the
             # plan above still serves the GNN layers' dst CSR)
             split = self._kp_split(side, bt)
-            out = torch.empty(nn_, 3 * C.NODE_FEATURE_DIM if split else C.NODE_FEATURE_DIM, device=dev, dtype=op)
-            outf = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32) if self._keep_feats else None
+            out, outf = self._operand_bufs(nn_, split, f32, dev)
             ops.rows_gather_scale(x_op.y, x_op.row_off, x_op.idx, bt.nmax[side], coef=cscale, out_f=outf, out_t=out,
                                   split=split, idx_host=x_op.idx_host, row_off_host=x_op.row_off_host)
             return plan, out, outf
         if isinstance(x_op, _SharedProbe):          # a one-pair chunk of a probe x gallery batch
             x_op = None
-        x0 = bt.x[side]
-        if x_op is None:
-            x_op = ops.cast_bf16(x0) if op == torch.bfloat16 else x0
-        yws = ops.spline_y_ws(ops.BF16 if op == torch.bfloat16 else ops.F32, E, nn_, dev)
-        h = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=op)
-        ops.spline_conv(x_op, plan, E, nn_, bt.nmax[side], bt.n[side], W0, wp["bias0"], yws, 0, out_t=h)
         # bf16 + kp_x3: the vertex affinity's operands as split rows (x2 = A: [hi | lo | hi], x1 o c = B:
         # [hi | hi | lo]) so Kp is a near-fp32 product on the bf16 MFMA path
-        split = self._kp_split(side, bt)
-        out = torch.empty(nn_, 3 * C.NODE_FEATURE_DIM if split else C.NODE_FEATURE_DIM, device=dev, dtype=op)
-        outf = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32) if self._keep_feats else None
-        ops.spline_conv(h, plan, E, nn_, bt.nmax[side], bt.n[side], W1, wp["bias1"], yws, 1 | (split << 1),
-                        xres=x0, cscale=cscale, out_f=outf, out_t=out)
-        return plan, out, outf
+        return (plan,) + self._spline_layers(wp, f32, bt.x[side], plan, E, nn_, bt.nmax[side], bt.n[side], x_op=x_op,
+                                             operands=True, split=self._kp_split(side, bt), cscale=cscale)
+
+    def _operand_bufs(self, rows, split, f32, dev):
+        """One side's affinity operand rows (``split``: three-part rows of 2304 columns) in the SplineConv
+        dtype and, when the features are kept, their fp32 copy (else None) -> (out, outf), uninitialised."""
+        out = torch.empty(rows, 3 * C.NODE_FEATURE_DIM if split else C.NODE_FEATURE_DIM, device=dev,
+                          dtype=torch.float32 if f32 else torch.bfloat16)
+        outf = torch.empty(rows, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32) if self._keep_feats else None
+        return out, outf
+
+    def _spline_layers(self, wp, f32, x0, plan, E, nn_, nmax, nv, x_op=None, operands=False, split=0, cscale=None):
+        """The two SplineConv layers over one side's padded rows ``x0`` (nn_, 768) fp32 (``plan``, ``E``,
+        ``nmax``, ``nv``: that side's spline plan, edge count, box and keypoint counts), in fp32 or bf16
+        arithmetic (``f32``; ``x_op``: the bf16 operand rows when the caller cast them already) -> the fp32
+        output rows (nn_, 768): what an index keeps and the probe side of a query computes.
+        ``operands``: the forward's form instead -> (operand rows in the SplineConv dtype, scaled per pair by
+        ``cscale`` and laid out by ``split``; their fp32 copy or None), as ``_operand_bufs`` allocates them."""
+        dev = x0.device
+        W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
+        if x_op is None:
+            x_op = x0 if f32 else ops.cast_bf16(x0)
+        yws = ops.spline_y_ws(ops.F32 if f32 else ops.BF16, E, nn_, dev)
+        h = torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=x_op.dtype)
+        ops.spline_conv(x_op, plan, E, nn_, nmax, nv, W0, wp["bias0"], yws, 0, out_t=h)
+        if operands:
+            out, outf = self._operand_bufs(nn_, split, f32, dev)
+        else:
+            out, outf = None, torch.empty(nn_, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
+        ops.spline_conv(h, plan, E, nn_, nmax, nv, W1, wp["bias1"], yws, 1 | (split << 1), xres=x0, cscale=cscale,
+                        out_f=outf, out_t=out)
+        return (out, outf) if operands else outf
 
     def _sc_f32(self, bt):
         """SplineConv products (and the vertex affinity) in fp32 for this batch: the fp32 mode, and the
@@ -480,37 +497,19 @@ class Net(nn.Module):
         """Probe x gallery: the shared side-0 graph's two SplineConv layers once (pair 0's slice; or
         ``probe``, the forward's prologue result), then broadcast to all pairs with the per-pair
         coefficient scaling (fpm_rows_bcast_scale)."""
-        dev = bt.device
         y = probe.y if probe is not None else self._probe_rows(wp, bt)
-        nm = bt.nmax[0]
-        f32 = self._sc_f32(bt)
-        op = torch.float32 if f32 else torch.bfloat16
         split = self._kp_split(0, bt)
-        out = torch.empty(bt.B * nm, 3 * C.NODE_FEATURE_DIM if split else C.NODE_FEATURE_DIM, device=dev, dtype=op)
-        outf = torch.empty(bt.B * nm, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32) if self._keep_feats else None
+        out, outf = self._operand_bufs(bt.B * bt.nmax[0], split, self._sc_f32(bt), bt.device)
         ops.rows_bcast_scale(y, bt.B, coef=cscale, out_f=outf, out_t=out, split=split)
         return out, outf
 
     def _probe_rows(self, wp, bt):
         """The shared probe graph's SplineConv output rows (nmax_0, 768) fp32 (both layers, pair 0's
         graph; the same for every chunk of a probe x gallery batch)."""
-        dev = bt.device
-        f32 = self._sc_f32(bt)
-        op = torch.float32 if f32 else torch.bfloat16
-        W0, W1 = (wp["W0f"], wp["W1f"]) if f32 else (wp["W0"], wp["W1"])
         nm = bt.nmax[0]
         e0 = int(bt.edge_off[0][1])
-        src, dst, ps = bt.src[0][:e0], bt.dst[0][:e0], bt.pseudo[0][:e0]
-        plan = ops.spline_plan(src, dst, ps, nm, nm, e0)
-        x0 = bt.x[0][:nm]
-        nv = bt.n[0][:1]
-        x_op = ops.cast_bf16(x0) if op == torch.bfloat16 else x0
-        yws = ops.spline_y_ws(ops.BF16 if op == torch.bfloat16 else ops.F32, e0, nm, dev)
-        h = torch.empty(nm, C.NODE_FEATURE_DIM, device=dev, dtype=op)
-        ops.spline_conv(x_op, plan, e0, nm, nm, nv, W0, wp["bias0"], yws, 0, out_t=h)
-        y = torch.empty(nm, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
-        ops.spline_conv(h, plan, e0, nm, nm, nv, W1, wp["bias1"], yws, 1, xres=x0, out_f=y)
-        return y
+        plan = ops.spline_plan(bt.src[0][:e0], bt.dst[0][:e0], bt.pseudo[0][:e0], nm, nm, e0)
+        return self._spline_layers(wp, self._sc_f32(bt), bt.x[0][:nm], plan, e0, nm, nm, bt.n[0][:1])
 
     def _afau_norm1_bufs(self, rows, dev):
         """The block's first-norm outputs: fp32 rows and (bf16 modes) the zero-K-padded operand copy."""
@@ -1605,8 +1604,10 @@ class Net(nn.Module):
 
     # Probe sets: a *probe set* is a GalleryIndex enrolled from the probe graphs (``enroll``), with its
     # fp32 rows on the device (layout "f32" or "f32+bf16"), on the gallery's device, enrolled with the
-    # gallery's sc_mode and SplineConv weights; each of these is refused by name otherwise.  The three
-    # methods below take the refusals of ``identify`` (training mode, use_graphs, stale weights).
+    # gallery's sc_mode and SplineConv weights; each of these is refused by name otherwise
+    # (``gallery._check_probe_set``).  The three methods below then take the refusals of ``identify``
+    # (``gallery._check_many``: training mode and use_graphs by ``_check_eager``, stale weights by
+    # ``_check_query``).  ``identify_many`` runs the query stages ``identify`` runs (gallery.py's docstring).
     def match_pairs(self, probes, index, pairs, chunks=None):
         """The exact forward over an explicit list of (probe number, entry number) pairs of a probe set
         and a gallery index, both sides' operand rows gathered from the cached SplineConv rows (no

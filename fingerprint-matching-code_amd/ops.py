@@ -330,23 +330,17 @@ def rows_gather_scale(y, row_off, idx, nmax, coef=None, out_f=None, out_t=None, 
     copies of the two (a caller that built them on the host passes them, and the check needs no
     device synchronisation; without them the device tensors are copied back)."""
     for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt:
-            raise _lib.FpmError("rows_gather_scale: %s must be a %s tensor (got %s)"
-                                % (name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
-        if t.dim() != 1 or not t.is_contiguous():
-            raise _lib.FpmError("rows_gather_scale: %s must be a contiguous 1-d tensor" % name)
-        if t.device != y.device:
-            raise _lib.FpmError("rows_gather_scale: %s is on %s, y on %s" % (name, t.device, y.device))
+        _check_index_tensors("rows_gather_scale", ((name, t, dt),))
+        _check_on_device_of("rows_gather_scale", y, ((name, t),))
     if y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != 768 or not y.is_contiguous():
         raise _lib.FpmError("rows_gather_scale: y must be contiguous fp32 rows of 768 channels")
     G, B, nmax = int(row_off.numel()) - 1, int(idx.numel()), int(nmax)
     if G < 1 or nmax < 0:
         raise _lib.FpmError("rows_gather_scale: empty gallery or negative nmax")
-    ih = torch.as_tensor(idx_host if idx_host is not None else idx.cpu()).view(-1).long()
-    oh = torch.as_tensor(row_off_host if row_off_host is not None else row_off.cpu()).view(-1).long()
+    ih, oh = _host_copy(idx_host, idx), _host_copy(row_off_host, row_off)
     if ih.numel() != B or oh.numel() != G + 1:
         raise _lib.FpmError("rows_gather_scale: host copies of idx / row_off do not match the device tensors")
-    if int(oh[0]) != 0 or int(oh[-1]) != y.shape[0] or bool((oh[1:] < oh[:-1]).any()):
+    if not _offsets_rise(oh, y):
         raise _lib.FpmError("rows_gather_scale: row_off must rise from 0 to the %d rows of y" % y.shape[0])
     if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
         raise _lib.FpmError("rows_gather_scale: idx value outside [0, %d)" % G)
@@ -384,13 +378,8 @@ def rows_fetch(src, row_off, idx, out, out_off, idx_host=None, row_off_host=None
     ``row_off_host`` / ``out_off_host``: host copies, so the check needs no device synchronisation;
     without them the device tensors are copied back).  All-CPU tensors take the torch statement of
     the copy."""
-    for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64),
-                        ("out_off", out_off, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt:
-            raise _lib.FpmError("rows_fetch: %s must be a %s tensor (got %s)"
-                                % (name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
-        if t.dim() != 1 or not t.is_contiguous():
-            raise _lib.FpmError("rows_fetch: %s must be a contiguous 1-d tensor" % name)
+    _check_index_tensors("rows_fetch", (("idx", idx, torch.int32), ("row_off", row_off, torch.int64),
+                                        ("out_off", out_off, torch.int64)))
     for name, t in (("src", src), ("out", out)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
                 or not t.is_contiguous():
@@ -406,11 +395,10 @@ def rows_fetch(src, row_off, idx, out, out_off, idx_host=None, row_off_host=None
         raise _lib.FpmError("rows_fetch: empty gallery")
     if out_off.numel() != M + 1:
         raise _lib.FpmError("rows_fetch: out_off must hold %d offsets (got %d)" % (M + 1, out_off.numel()))
-    ih = torch.as_tensor(idx_host if idx_host is not None else idx.cpu()).view(-1).long()
-    oh = torch.as_tensor(row_off_host if row_off_host is not None else row_off.cpu()).view(-1).long()
+    ih, oh = _host_copy(idx_host, idx), _host_copy(row_off_host, row_off)
     if ih.numel() != M or oh.numel() != G + 1:
         raise _lib.FpmError("rows_fetch: host copies of idx / row_off do not match the device tensors")
-    if int(oh[0]) != 0 or int(oh[-1]) != src.shape[0] or bool((oh[1:] < oh[:-1]).any()):
+    if not _offsets_rise(oh, src):
         raise _lib.FpmError("rows_fetch: row_off must rise from 0 to the %d rows of src" % src.shape[0])
     if M and (int(ih.min()) < 0 or int(ih.max()) >= G):
         raise _lib.FpmError("rows_fetch: idx value outside [0, %d)" % G)
@@ -420,7 +408,7 @@ def rows_fetch(src, row_off, idx, out, out_off, idx_host=None, row_off_host=None
     total = int(ng.sum())
     if out.shape[0] < total:
         raise _lib.FpmError("rows_fetch: out holds %d rows, the selection has %d" % (out.shape[0], total))
-    fh = torch.as_tensor(out_off_host if out_off_host is not None else out_off.cpu()).view(-1).long()
+    fh = _host_copy(out_off_host, out_off)
     if not torch.equal(fh, torch.cat([torch.zeros(1, dtype=torch.int64), ng.cumsum(0)])):
         raise _lib.FpmError("rows_fetch: out_off must rise from 0 by the selected entries' row counts")
     if not out.is_cuda:
@@ -446,12 +434,7 @@ def rows_pack(src, n, nmax, out_off, out32=None, out16=None, n_host=None, out_of
     ``out_off_host``: host copies, so the check needs no device synchronisation; without them the
     device tensors are copied back).  All-CPU tensors take the torch statement of the copy and the
     rounding."""
-    for name, t, dt in (("n", n, torch.int32), ("out_off", out_off, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt:
-            raise _lib.FpmError("rows_pack: %s must be a %s tensor (got %s)"
-                                % (name, str(dt).replace("torch.", ""), getattr(t, "dtype", type(t).__name__)))
-        if t.dim() != 1 or not t.is_contiguous():
-            raise _lib.FpmError("rows_pack: %s must be a contiguous 1-d tensor" % name)
+    _check_index_tensors("rows_pack", (("n", n, torch.int32), ("out_off", out_off, torch.int64)))
     if out32 is None and out16 is None:
         raise _lib.FpmError("rows_pack: give out32, out16 or both")
     for name, t, dt in (("src", src, torch.float32), ("out32", out32, torch.float32), ("out16", out16, torch.bfloat16)):
@@ -474,8 +457,7 @@ def rows_pack(src, n, nmax, out_off, out32=None, out16=None, n_host=None, out_of
                             % (src.shape[0], B, nmax, B * nmax))
     if out_off.numel() != B + 1:
         raise _lib.FpmError("rows_pack: out_off must hold %d offsets (got %d)" % (B + 1, out_off.numel()))
-    nh = torch.as_tensor(n_host if n_host is not None else n.cpu()).view(-1).long()
-    oh = torch.as_tensor(out_off_host if out_off_host is not None else out_off.cpu()).view(-1).long()
+    nh, oh = _host_copy(n_host, n), _host_copy(out_off_host, out_off)
     if nh.numel() != B or oh.numel() != B + 1:
         raise _lib.FpmError("rows_pack: host copies of n / out_off do not match the device tensors")
     if B and (int(nh.min()) < 0 or int(nh.max()) > nmax):
@@ -787,7 +769,9 @@ def _coarse_call(kernel, pairs, y, args, B, n0max, ngmax):
     _lib.call((many if pairs else one) + ("_rows16" if y.dtype == torch.bfloat16 else ""), *args, *ws, _stream(y))
 
 
-# The checks that ``coarse_score*`` and ``coarse_pairs`` make alike; ``op`` names the caller in the message.
+# The checks that ``coarse_score*``, ``coarse_pairs`` and the ``rows_*`` wrappers make alike; ``op`` names the
+# caller in the message.  (The row and device checks of ``rows_fetch`` / ``rows_pack`` word theirs after other
+# tensors -- "out on", "src on" -- and stay with them.)
 def _check_index_tensors(op, named):
     for name, t, dt in named:
         if not isinstance(t, torch.Tensor) or t.dtype != dt:

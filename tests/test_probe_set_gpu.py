@@ -15,7 +15,7 @@ from test_compact_index_cpu import case
 from test_compact_index_gpu import MIXED_N, MIXED_PROBES
 from test_gallery_gpu import CASES
 from test_shortlist_cpu import ENTRY_NS, PROBE_NS, SHAPES, coefficients, state_dicts
-from test_shortlist_gpu import MATES, OUT_KEYS, _bits, _net, planted
+from test_shortlist_gpu import MATES, OUT_KEYS, _bits, _net, check_result_keys, planted
 
 pytestmark = pytest.mark.gpu
 
@@ -230,6 +230,8 @@ def test_identify_many_groups(mates):
     one = net.identify(probes, index, topk=5, shortlist=8)
     assert len(res) == len(probes)
     for a, b in zip(res, one):
+        check_result_keys(a, "identify_many", None, True, k=5, M=8, Gs=len(gal))
+        check_result_keys(b, "identify", None, True, k=5, M=8, Gs=len(gal))
         assert torch.equal(_bits(a["coarse_all"]), _bits(b["coarse_all"]))
         assert a["short_idx"].dtype == torch.int32 and torch.equal(a["short_idx"], b["short_idx"])
         assert torch.equal(_bits(a["coarse_score"]), _bits(b["coarse_score"]))
@@ -252,6 +254,7 @@ def test_identify_many_groups(mates):
     full = net.identify_many(pset, index, topk=2, select=sel, probe_select=[2, 1])
     ref = net.match_pairs(pset, index, [(q, g) for q in (1, 2) for g in sel])        # groups sort by n: 33 then 40
     for r, b0 in zip(full, (4, 0)):
+        check_result_keys(r, "identify_many", None, False, k=2)
         assert "short_idx" not in r and r["group"] == (0, b0, b0 + 4)
         for k in RUN_KEYS:
             assert torch.equal(r[k], ref[k][b0:b0 + 4]), k

@@ -26,6 +26,58 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 OUT_KEYS = ("s", "ss", "ds_mat", "perm_mat", "k_prob", "cls_prob", "top_idx", "top_score")
 
+# The keys of one probe's result dict for each query form, as recorded from a run of the commit before the query
+# stages were shared (the planted gallery of 40 entries, three probes, fp32 and bf16 nets: the same sets).
+# FORWARD_KEYS are the forward's own in every run.  FORWARD_RUN_KEYS it adds by how it runs, not by the query form:
+# "ss64" (the fp64 k chain) on boxes within ``Net.k_f64_nmax``, "Kp" and "coef" when it runs in one piece (not with
+# ``chunks``).  On the planted gallery every form carried all three; a call site whose forward runs otherwise says
+# which it expects (``run_keys``).  QUERY_KEYS: what the query layer adds, by (call, by, shortlisted).  One
+# asymmetry is on purpose: identify_many(by="subject") without a shortlist carries short_idx / short_off (its ragged
+# pair lists), identify(by="subject") without one does not.
+FORWARD_KEYS = {"cls_logits", "cls_loss", "cls_prob", "ds_mat", "k_prob", "ks_error", "ks_loss", "lsa", "perm_mat", "s",
+                "sk_steps", "ss"}
+FORWARD_RUN_KEYS = {"Kp", "coef", "ss64"}
+QUERY_KEYS = {
+    ("identify", None, False): {"top_idx", "top_score"},
+    ("identify", None, True): {"top_idx", "top_score", "short_idx", "coarse_score", "coarse_all"},
+    ("identify", "subject", False): {"top_idx", "top_score", "subjects", "subject_score", "top_subject"},
+    ("identify", "subject", True): {"top_idx", "top_score", "subjects", "subject_score", "top_subject", "short_subject",
+                                    "coarse_subject_score", "coarse_all", "short_idx", "short_off"},
+    ("identify_many", None, False): {"group", "top_idx", "top_score"},
+    ("identify_many", None, True): {"group", "top_idx", "top_score", "short_idx", "coarse_score", "coarse_all"},
+    ("identify_many", "subject", False): {"group", "top_idx", "top_score", "subjects", "subject_score", "top_subject",
+                                          "short_idx", "short_off"},
+    ("identify_many", "subject", True): {"group", "top_idx", "top_score", "subjects", "subject_score", "top_subject",
+                                         "short_subject", "coarse_subject_score", "coarse_all", "short_idx",
+                                         "short_off"},
+}
+# dtype and length of the added keys: k ranks, Gs selected entries, M shortlisted entries or subjects, S ranked
+# subjects (M when shortlisted), L entries in a subject-level query's lists
+QUERY_KEY_FORMS = {
+    "top_idx": (torch.int32, "k"), "top_score": (torch.float32, "k"), "top_subject": (torch.int64, "k"),
+    "coarse_all": (torch.float32, "Gs"), "coarse_score": (torch.float32, "M"),
+    "short_subject": (torch.int64, "M"), "coarse_subject_score": (torch.float32, "M"),
+    "subjects": (torch.int64, "S"), "subject_score": (torch.float32, "S"), "short_off": (torch.int32, "S+1"),
+}
+
+
+def check_result_keys(r, call, by, shortlisted, run_keys=FORWARD_RUN_KEYS, **dims):
+    """The exact key set of the result dict ``r`` of that query form (``run_keys``: those of FORWARD_RUN_KEYS
+    this forward carries), and dtype, shape and device of every key the query layer added (``dims``: the
+    lengths QUERY_KEY_FORMS names)."""
+    added = QUERY_KEYS[(call, by, shortlisted)]
+    want = FORWARD_KEYS | set(run_keys) | added
+    assert set(run_keys) <= FORWARD_RUN_KEYS and set(r) == want, (call, by, shortlisted, sorted(set(r) ^ want))
+    if "S" in dims:
+        dims["S+1"] = dims["S"] + 1
+    for key in sorted(added):
+        if key == "group":
+            assert isinstance(r[key], tuple) and len(r[key]) == 3
+            continue
+        dt, n = (torch.int32, "L" if by else "M") if key == "short_idx" else QUERY_KEY_FORMS[key]
+        assert r[key].dtype == dt and tuple(r[key].shape) == (dims[n],) and r[key].device == DEV, (call, by, key)
+
+
 MEASURED = {
     # case: (device_err, err32, device_err / err32, gate); scores 0.193-0.194 (flat), 0.168-0.288 (spread)
     "flat": (4.80e-08, 4.80e-08, 1.00, 3.84e-07),
@@ -165,6 +217,11 @@ def test_shortlisted_identify_is_selected_identify(enrolled):
     assert res["short_idx"].dtype == torch.int32 and tuple(res["short_idx"].shape) == (3,)
     assert tuple(res["coarse_all"].shape) == (len(gal),)
     ref = net.identify(probe, index, topk=3, select=res["short_idx"], chunks=2)
+    # chunks=2: no "Kp" / "coef"; the fp64 k chain when the probe and the shortlisted entries are within k_f64_nmax
+    box = max([probe["n"]] + [gal[e]["n"] for e in res["short_idx"].tolist()])
+    run_keys = {"ss64"} if box <= net.k_f64_nmax else set()
+    check_result_keys(res, "identify", None, True, run_keys, k=3, M=3, Gs=len(gal))
+    check_result_keys(ref, "identify", None, False, run_keys, k=3)
     for k in OUT_KEYS:
         assert torch.equal(res[k], ref[k]), k
     hi, hs = ops.rank_select(res["coarse_all"].cpu().view(1, -1), 3)

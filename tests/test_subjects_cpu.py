@@ -1,10 +1,13 @@
 """Subject-level 1:N search, host side (no GPU): the statement of ``ops.group_scores`` (max, gbest and the
-fixed-order mean), the index's subject labels and group tables, ``save`` / ``load``, and the refusals.
+fixed-order mean), the index's subject labels and group tables, ``save`` / ``load``, the refusals, and the
+query layer's host-side stages (the shortlist stage and the probe-set exact stage's pair lists) against
+plain Python loops.
 
 Mean bound: against float64 a group's mean may differ by ``(cnt + 1) * 2^-24 * sum|x| / cnt`` -- the
 first-order bound of any fp32 summation order (cnt - 1 additions on a path at most; here far fewer)
 plus the rounding of the divide.  The statement is held to it on every finite group below, and an
 independent lane-by-lane loop in numpy pins its order bit for bit."""
+import math
 import types
 
 import numpy as np
@@ -285,6 +288,146 @@ def test_unlabelled_index_saves_what_it_saved_before(tmp_path):
     hand_index("bf16+host").save(path)
     raw2 = torch.load(path, map_location="cpu", weights_only=True)
     assert sorted(raw2) == sorted(list(raw) + ["layout", "y16"]) and raw2["format"] == 2
+
+
+# ------------------------------------------------------------- the query stages against plain loops
+STAGE_LABELS = [3, 1, 3, 0, 1, 3, 5]                         # subjects of 1, 2, 3 and 1 impressions
+STAGE_SELECTIONS = {"in-order": [0, 1, 2, 3, 4, 5, 6], "permuted": [4, 0, 6, 2, 5, 1, 3]}
+
+
+def stage_case(sel, with_own):
+    """Q = 3 probes over the selection ``sel`` of the 7 labelled entries -> (coarse matrix (3, 7) by
+    position in the selection, own mask or None).  Row 0 carries a tie at the top between entry 1
+    (subject 1) and entry 6 (the singleton subject 5), row 2 a NaN at entry 3 (the singleton subject 0);
+    ``own`` removes entry 6 for probe 1: the only entry of its subject."""
+    gen = torch.Generator().manual_seed(11)
+    by_entry = torch.randn(3, 7, generator=gen)
+    by_entry[0, 1] = by_entry[0, 6] = 9.0
+    by_entry[2, 3] = float("nan")
+    call = by_entry[:, sel].contiguous()
+    own = None
+    if with_own:
+        own = torch.zeros(3, 7, dtype=torch.bool)
+        own[1, sel.index(6)] = True
+    return call, own
+
+
+def _best_first(vals):
+    """Indices of a list of floats, best first: descending, ties to the lower index, NaN after every
+    number (-inf included), NaNs by index."""
+    return sorted(range(len(vals)), key=lambda i: (math.isnan(vals[i]), 0.0 if math.isnan(vals[i]) else -vals[i], i))
+
+
+def shortlist_loop(call, sel, M, own, subject, impressions):
+    """The shortlist stage by a plain loop over a dict of lists -> per probe (entry list, offsets or None,
+    names, coarse scores as (probe row, position) of ``call`` or None for -inf)."""
+    groups = {}
+    for p, e in enumerate(sel):
+        groups.setdefault(STAGE_LABELS[e], []).append(p)
+    labels = sorted(groups)
+    out = []
+    for q in range(call.shape[0]):
+        gone = [own is not None and bool(own[q, p]) for p in range(len(sel))]
+        vals = [float("-inf") if gone[p] else float(call[q, p]) for p in range(len(sel))]
+        if not subject:
+            top = _best_first(vals)[:min(M, len(sel) - (own is not None))]
+            out.append(([sel[p] for p in top], None, [sel[p] for p in top], [vals[p] for p in top]))
+            continue
+        best = {lab: groups[lab][_best_first([vals[p] for p in groups[lab]])[0]] for lab in labels}
+        top = _best_first([vals[best[lab]] for lab in labels])[:min(M, len(labels))]
+        ents, offs = [], [0]
+        for s in top:
+            members = groups[labels[s]] if impressions == "all" else [best[labels[s]]]
+            ents += [sel[p] for p in members if not gone[p]]
+            offs.append(len(ents))
+        out.append((ents, offs, [labels[s] for s in top], [vals[best[labels[s]]] for s in top]))
+    return out
+
+
+def _same_floats(t, want):
+    got = t.tolist()
+    return len(got) == len(want) and all((math.isnan(a) and math.isnan(b)) or a == b for a, b in zip(got, want))
+
+
+@pytest.mark.parametrize("with_own", [False, True])
+@pytest.mark.parametrize("M", [1, 3, 4])
+@pytest.mark.parametrize("order", sorted(STAGE_SELECTIONS))
+def test_shortlist_stage_against_the_loop(order, M, with_own, monkeypatch):
+    monkeypatch.setattr(_lib, "call", lambda *a, **k: pytest.fail("the library was called"))
+    sel = STAGE_SELECTIONS[order]
+    call, own = stage_case(sel, with_own)
+    index = labelled_index(STAGE_LABELS)
+    sel_t = torch.tensor(sel)
+    gt = index.subject_groups(sel_t)
+    emptied = False
+    for subject, impressions in ((False, "all"), (True, "all"), (True, "best")):
+        ents, offs, names, csc = gallery._shortlist(call, sel_t, M, own, gt if subject else None, impressions)
+        want = shortlist_loop(call, sel, M, own, subject, impressions)
+        assert len(ents) == 3 and names.dtype == torch.int64 and csc.dtype == torch.float32
+        assert (offs is None) == (not subject)
+        for q, (w_ents, w_offs, w_names, w_csc) in enumerate(want):
+            where = (order, M, with_own, subject, impressions, q)
+            assert ents[q].dtype == torch.int64 and ents[q].tolist() == w_ents, where
+            assert names[q].tolist() == w_names, where
+            assert _same_floats(csc[q], w_csc), where
+            if subject:
+                assert offs[q].tolist() == w_offs and len(w_offs) == len(w_names) + 1, where
+                emptied |= any(a == b for a, b in zip(w_offs, w_offs[1:]))
+    # leave-one-out: the emptied singleton subject keeps an empty range in the offsets (once the shortlist
+    # is long enough to reach it: its fused score is -inf)
+    assert emptied == (with_own and M == 4)
+
+
+@pytest.mark.parametrize("impressions", ["all", "best"])
+@pytest.mark.parametrize("with_own", [False, True])
+def test_subject_entry_lists_against_the_loop(with_own, impressions):
+    """``_subject_entry_lists`` alone, fed the loop's own ranking: positions and offsets."""
+    sel = STAGE_SELECTIONS["permuted"]
+    call, own = stage_case(sel, with_own)
+    gt = labelled_index(STAGE_LABELS).subject_groups(torch.tensor(sel))
+    labels = gt["labels"].tolist()
+    for M in (1, 3, 4):
+        want = shortlist_loop(call, sel, M, own, True, impressions)
+        spos = torch.tensor([[labels.index(lab) for lab in w[2]] for w in want], dtype=torch.int32)
+        masked = call if own is None else call.masked_fill(own, float("-inf"))
+        best = ops.group_scores(masked, gt["off"], gt["pos"], "max")[1] if impressions == "best" else None
+        lists = gallery._subject_entry_lists(gt, spos, best, own)
+        for (p, so), (w_ents, w_offs, _, _) in zip(lists, want):
+            assert [sel[int(i)] for i in p] == w_ents and so.tolist() == w_offs, (M, with_own, impressions)
+
+
+def test_exact_stage_pair_lists_and_slices(monkeypatch):
+    """The probe-set exact stage on ragged lists (3, 1 and 2 pairs, ``group_pairs`` = 4): each group's
+    pair list and each probe's slice of the batch's outputs, with the forward replaced by a stub."""
+    psel = torch.tensor([5, 2, 7])
+    ents = [torch.tensor([10, 11, 12]), torch.tensor([20]), torch.tensor([30, 31])]
+    probes = types.SimpleNamespace(n=torch.tensor([9, 9, 4, 9, 9, 6, 9, 5], dtype=torch.int32))   # probes 5, 2, 7: 6, 4, 5
+    seen = []
+
+    def run_pairs(net, pset, index, pairs, chunks):
+        assert pset is probes and index == "index" and chunks == 3
+        seen.append(pairs.tolist())
+        B = pairs.shape[0]
+        code = (pairs[:, 0] * 100 + pairs[:, 1]).float()
+        return dict(cls_prob=code, s=code.view(B, 1, 1).expand(B, 2, 3), ks_loss=torch.tensor(7.0),
+                    other=torch.arange(B + 1))
+
+    monkeypatch.setattr(gallery, "_run_pairs", run_pairs)
+    outs, rows = gallery._exact_many("net", probes, "index", psel, ents, "cls_prob", 3, 4)
+    # ascending keypoint count: probe 2 (4), probe 7 (5), probe 5 (6); 1 + 2 pairs fit 4, the 3 of probe 5 do not
+    assert seen == [[[2, 20], [7, 30], [7, 31]], [[5, 10], [5, 11], [5, 12]]]
+    assert [o["group"] for o in outs] == [(1, 0, 3), (0, 0, 1), (0, 1, 3)]
+    for q, (o, row) in enumerate(zip(outs, rows)):
+        want = [float(psel[q]) * 100 + e for e in ents[q].tolist()]
+        assert row.tolist() == want and o["cls_prob"].tolist() == want
+        assert tuple(o["s"].shape) == (len(want), 2, 3) and o["s"][:, 0, 0].tolist() == want
+        assert o["ks_loss"].dim() == 0 and set(o) == {"cls_prob", "s", "ks_loss", "other", "group"}
+        # a tensor that is not batch-sized is passed on whole (both batches have three pairs)
+        assert o["other"].tolist() == [0, 1, 2, 3]
+    # lists of equal length (the entry-level query): the same slicing, one group when it fits
+    del seen[:]
+    outs, rows = gallery._exact_many("net", probes, "index", psel, [e[:1] for e in ents], "cls_prob", 3, 4)
+    assert seen == [[[2, 20], [7, 30], [5, 10]]] and [o["group"] for o in outs] == [(0, 2, 3), (0, 0, 1), (0, 1, 2)]
 
 
 # ---------------------------------------------------------------------------------------- refusals

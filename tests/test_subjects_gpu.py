@@ -17,7 +17,7 @@ import torch
 from fpm import _lib, ops
 from fpm.gallery import GalleryIndex
 from test_shortlist_cpu import state_dicts
-from test_shortlist_gpu import MATES, OUT_KEYS, _net, planted
+from test_shortlist_gpu import MATES, OUT_KEYS, _net, check_result_keys, planted
 from test_subjects_cpu import _bits, _csr, all_cases, cases, per_row_case
 
 pytestmark = pytest.mark.gpu
@@ -186,6 +186,7 @@ def test_shortlisted_subject_identify(planted_subjects, impressions):
                 assert mate in want
             # exact stage: the entry-level identify over exactly those entries, bit for bit
             ref = net.identify(probes[p], index, topk=4, select=r["short_idx"])
+            check_result_keys(r, "identify", "subject", True, k=4, M=4, S=4, L=len(want), Gs=len(gal))
             for k in PAIR_KEYS:
                 assert r[k].dtype == ref[k].dtype and torch.equal(r[k], ref[k]), (fuse, p, k)
             assert torch.equal(r["subjects"], r["short_subject"])
@@ -198,11 +199,15 @@ def test_by_none_is_unchanged_and_full_query_by_subject(planted_subjects):
     new = set(SUBJECT_KEYS + SHORT_KEYS + ("short_off",)) - {"top_score", "top_idx", "short_idx", "coarse_all"}
     sel = [30, 7, 19, 6, 8, 39, 18, 0, 20, 31, 5]
     plain = net.identify(probe, index, topk=5, select=sel)
-    assert not new & set(plain) and not new & set(net.identify(probe, index, topk=3, shortlist=3))
+    short = net.identify(probe, index, topk=3, shortlist=3)
+    assert not new & set(plain) and not new & set(short)
+    check_result_keys(plain, "identify", None, False, k=5)
+    check_result_keys(short, "identify", None, True, k=3, M=3, Gs=len(gal))
     gt = index.subject_groups(sel)
     for fuse in ops.GROUP_FUSE:
         r = net.identify(probe, index, topk=5, select=sel, by="subject", fuse=fuse)
         assert set(r) == set(plain) | set(SUBJECT_KEYS)
+        check_result_keys(r, "identify", "subject", False, k=5, S=len(gt["labels"]))
         for k in PAIR_KEYS:
             assert torch.equal(r[k], plain[k]), k
         assert r["subjects"].dtype == torch.int64 and r["subjects"].tolist() == sorted({labels[e] for e in sel})
@@ -229,6 +234,9 @@ def test_identify_many_by_subject(planted_subjects):
     alone = net.identify_many(pset, index, group_pairs=12, **kw)
     assert sorted(r["group"][0] for r in alone) == [0, 1, 2]
     for p, (a, b) in enumerate(zip(alone, one)):
+        L = int(b["short_off"][-1])                          # the impressions of the four shortlisted subjects
+        check_result_keys(a, "identify_many", "subject", True, k=4, M=4, S=4, L=L, Gs=len(gal))
+        check_result_keys(b, "identify", "subject", True, k=4, M=4, S=4, L=L, Gs=len(gal))
         for k in PAIR_KEYS + SUBJECT_KEYS + SHORT_KEYS:
             assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), (p, k)
         for k in ("subject_score", "top_score", "coarse_subject_score", "coarse_all"):
@@ -254,8 +262,16 @@ def test_identify_many_by_subject(planted_subjects):
     kw.update(fuse="max", impressions="best")
     best = net.identify_many(pset, index, group_pairs=4, **kw)
     for a, b in zip(best, net.identify(probes, index, **kw)):
+        check_result_keys(a, "identify_many", "subject", True, k=4, M=4, S=4, L=4, Gs=len(gal))
         for k in PAIR_KEYS + SUBJECT_KEYS + SHORT_KEYS:
             assert torch.equal(a[k], b[k]), k
+    # without a shortlist the probe-set query still carries its ragged pair lists (short_idx / short_off): every
+    # entry, subject-major; the one-probe query (test_by_none_is_unchanged_and_full_query_by_subject) does not
+    S = len(set(labels))
+    for r in net.identify_many(pset, index, topk=4, by="subject", fuse="mean"):
+        check_result_keys(r, "identify_many", "subject", False, k=4, S=S, L=len(gal))
+        assert sorted(r["short_idx"].tolist()) == list(range(len(gal))) and int(r["short_off"][-1]) == len(gal)
+        _check_subject_ranking(r, "mean", 4)
 
 
 def test_leave_one_out(planted_subjects):
