@@ -49,6 +49,8 @@ SIGNATURES = {
     "fpm_rank_select_ws_bytes": (L, [I]),
     "fpm_rank_select": (I, [P, L, I, I, I, P, P, P, L, P]),
     "fpm_group_scores": (I, [P, L, I, I, P, L, P, L, I, I, P, P, P]),
+    "fpm_group_topr": (I, [P, L, I, I, P, L, P, L, I, I, P, P, P]),
+    "fpm_cohort_decide": (I, [P, I, I, I, I, I, F, I, I, F, P, P, P, P, P, P]),
     "fpm_coarse_score_wide_ws_bytes": (L, [I]),
     "fpm_coarse_score_stream_ws_bytes": (L, [I, I, I]),
     "fpm_rows_fetch": (I, [P, L, P, P, I, I, I, P, L, P, P]),

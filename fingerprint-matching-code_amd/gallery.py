@@ -51,8 +51,14 @@ set, entries or subjects, with or without a shortlist): the checks (``_check_eag
 (``_shortlist``: the file's one ``rank_select`` and its one coarse fuse; ``_all_lists`` without a shortlist), the
 exact stage (one probe: the plain ``identify(select=...)`` per probe, the shared side 0 with the probe's
 SplineConv live; a probe set: ``_exact_many``, groups of ragged pair lists with both sides cached), the ranking
-(``_entry_ranking`` or ``_subject_ranking``) and ``_attach``, which puts the result keys on the dicts.  The stages
-take and return tensors and run on CPU tensors as they are; the device contexts stay in the callers.
+(``_entry_ranking`` or ``_subject_ranking``), the open-set stage when asked for (``_open_set``) and ``_attach``,
+which puts the result keys on the dicts.  The stages take and return tensors and run on CPU tensors as they are;
+the device contexts stay in the callers.
+
+Open set (``top_r``, ``normalize="cohort"``, ``threshold``; all off by default, and then nothing above changes):
+``top_r`` makes the exact-stage fuse the mean of a subject's r best impressions (``ops.group_topr``);
+``_open_set`` takes ``ops.rank_select`` of the row the ranking ranked and ``ops.cohort_decide``: z-scores of the
+top k against the next-best candidates of the same list, ``accept`` per rank and one ``match`` per probe.
 """
 import contextlib
 import hashlib
@@ -872,6 +878,69 @@ def _check_by(what, index, by, fuse, impressions, shortlist):
     return True
 
 
+NORMALIZE = (None, "cohort")
+
+
+def _check_open(what, subj, fuse, top_r, normalize, cohort, cohort_skip, sigma_floor, threshold):
+    """The refusals of the open-set arguments (before any GPU work) -> dict: ``top_r`` (None or the r of the
+    exact-stage fuse), ``stage`` (whether ``_open_set`` runs: ``normalize`` or ``threshold`` was given) and
+    ``_open_set``'s arguments as ``ops.cohort_decide`` takes them."""
+    isint = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    if top_r is not None:
+        if not subj:
+            raise FpmError("%s: top_r without by='subject' (it is the mean of a subject's r best impressions)" % what)
+        if fuse != "mean":
+            raise FpmError("%s: top_r needs fuse='mean' (got fuse=%r)" % (what, fuse))
+        if not isint(top_r) or not 1 <= top_r <= ops.TOPR_MAX:
+            raise FpmError("%s: top_r = %r outside [1, %d] (an integer)" % (what, top_r, ops.TOPR_MAX))
+    if normalize not in NORMALIZE:
+        raise FpmError("%s: normalize must be one of %s" % (what, NORMALIZE))
+    if not isint(cohort) or not isint(cohort_skip) or cohort < 2 or cohort_skip < 0 \
+            or cohort_skip + cohort > ops.COHORT_WINDOW:
+        raise FpmError("%s: cohort = %r, cohort_skip = %r (integers, cohort >= 2, cohort_skip >= 0, cohort_skip + cohort "
+                       "<= %d)" % (what, cohort, cohort_skip, ops.COHORT_WINDOW))
+    floor = float(torch.tensor(float(sigma_floor), dtype=torch.float32))
+    if not 0.0 < floor < float("inf"):
+        raise FpmError("%s: sigma_floor must be a positive finite fp32 number (got %r)" % (what, sigma_floor))
+    if threshold is not None and float(threshold) != float(threshold):
+        raise FpmError("%s: threshold is NaN" % what)
+    return dict(top_r=top_r, stage=normalize is not None or threshold is not None, normalize=normalize is not None,
+                cohort=cohort, skip=cohort_skip, sigma_floor=sigma_floor, threshold=threshold)
+
+
+def _open_set(ranked, rank, opt):
+    """The open-set stage of every query form (one probe or a probe set, entries or subjects, shortlisted or
+    not, with or without ``exclude_self``).  ``ranked`` (Q, X): the scores the ranking ranked -- the exact
+    scores per entry, or the fused scores per subject (NaN: a subject with no pair); ``rank``: the ranking's
+    result keys (top_score (Q, k), and top_subject or top_idx (Q, k): what rank 1 names); ``opt``:
+    ``_check_open``'s.  ``ops.rank_select`` to the K = min(X, max(k, cohort_skip + cohort)) best -- its first k
+    columns are top_score, bit for bit -- then ``ops.cohort_decide``: the cohort is the ranked list's own
+    next-best candidates (with a shortlist: shortlisted candidates), NaN scores outside it.
+    -> the result keys: with ``normalize`` top_z (Q, k), cohort_mu, cohort_sigma (Q,) fp32 and cohort_n (Q,)
+    int32; with ``threshold`` accept (Q, k) bool -- z >= threshold, the raw score without ``normalize`` -- and
+    match (Q,) int64: rank 1's subject label or entry number where it is accepted, else -1."""
+    k = int(rank["top_score"].shape[1])
+    K = min(int(ranked.shape[1]), max(k, opt["skip"] + opt["cohort"]))
+    _, top = ops.rank_select(ranked, K)
+    z, mu, sigma, n, acc = ops.cohort_decide(top, k, opt["skip"], opt["cohort"], opt["sigma_floor"], opt["threshold"],
+                                             opt["normalize"])
+    keys = {}
+    if z is not None:
+        keys.update(top_z=z, cohort_mu=mu, cohort_sigma=sigma, cohort_n=n)
+    if acc is not None:
+        first = rank["top_subject" if "top_subject" in rank else "top_idx"][:, 0].to(torch.int64)
+        keys.update(accept=acc != 0, match=torch.where(acc[:, 0] != 0, first, torch.full_like(first, -1)))
+    return keys
+
+
+def _fuse_exact(scores, off_d, pos_d, fuse, top_r, off_host, pos_host):
+    """The exact stage's fuse per subject: ``ops.group_scores`` with ``fuse``, or (``top_r``) the mean of each
+    subject's r best impressions (``ops.group_topr``) -> (fused scores, each group's best position)."""
+    if top_r is None:
+        return ops.group_scores(scores, off_d, pos_d, fuse, off_host=off_host, pos_host=pos_host)
+    return ops.group_topr(scores, off_d, pos_d, top_r, off_host=off_host, pos_host=pos_host)
+
+
 def _subject_entry_lists(gt, spos, best=None, own=None):
     """The exact stage's entry lists of shortlisted subjects, per probe, on the host.  ``gt``: the
     selection's group tables; ``spos`` (Q, M): each probe's group numbers in coarse-rank order; ``best``
@@ -898,11 +967,12 @@ def _subject_entry_lists(gt, spos, best=None, own=None):
     return lists
 
 
-def _subject_ranking(rows, ents, offs, labels, fuse, topk, dev):
+def _subject_ranking(rows, ents, offs, labels, fuse, topk, dev, top_r=None):
     """The subject ranking of the exact stage over ragged pair lists.  rows[i]: probe i's exact scores
     (L_i,) on the device; ents[i]: their entry numbers (L_i,) host; offs[i]: (M + 1,) host offsets of the M
     subjects into them; labels (Q, M) device int64.  The rows are padded with NaN to one matrix, each
-    with its own group structure (``ops.group_scores``), then ``ops.rank_topk`` over the M subjects
+    with its own group structure (``_fuse_exact``: ``ops.group_scores``, or ``ops.group_topr`` with ``top_r``),
+    then ``ops.rank_topk`` over the M subjects
     -> the result keys (``_subject_keys``): subjects, subject_score (Q, M), top_subject (Q, k) int64,
     top_score (Q, k), top_idx (Q, k) int32: the entry of each top subject's best impression (-1 for a
     subject with no pair)."""
@@ -915,7 +985,7 @@ def _subject_ranking(rows, ents, offs, labels, fuse, topk, dev):
         ent[i, :r.numel()] = ents[i].to(torch.int32)
     off = torch.stack([o.to(torch.int32) for o in offs])
     pos = torch.arange(L, dtype=torch.int32).view(1, L).expand(Q, L).contiguous()
-    gsc, gb = ops.group_scores(mat, off.to(dev), pos.to(dev), fuse, off_host=off, pos_host=pos)
+    gsc, gb = _fuse_exact(mat, off.to(dev), pos.to(dev), fuse, top_r, off, pos)
     ti, ts = _rank_topk(gsc, topk)
     bp = torch.gather(gb, 1, ti.long())
     te = torch.gather(ent.to(dev), 1, bp.clamp(min=0).long())
@@ -1002,10 +1072,12 @@ def _check_eager(net, what):
 
 
 def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None, shortlist=None,
-             coarse="fused", by=None, fuse="max", impressions="all"):
+             coarse="fused", by=None, fuse="max", impressions="all", top_r=None, normalize=None, cohort=32,
+             cohort_skip=1, sigma_floor=1e-6, threshold=None):
     """``Net.identify``: see there."""
     _check_coarse(coarse, "identify")
     subj = _check_by("identify", index, by, fuse, impressions, shortlist)
+    opt = _check_open("identify", subj, fuse, top_r, normalize, cohort, cohort_skip, sigma_floor, threshold)
     _check_eager(net, "identify")
     if score not in SCORES:
         raise FpmError("identify: score must be one of %s" % (SCORES,))
@@ -1025,10 +1097,16 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
         # the exact stage, a probe at a time: the plain ``identify`` over its list alone, in that order
         outs = [identify(net, p, index, topk=topk, select=e, score=score, chunks=chunks) for p, e in zip(plist, ents)]
         keys = _shortlist_keys(subj, names, csc, call)
-        if subj:
-            with torch.cuda.device(dev):
-                keys.update(_subject_ranking([o[score] for o in outs], ents, offs, names, fuse, topk, dev))
-            keys.update(_ragged_keys(ents, offs, dev))
+        with torch.cuda.device(dev):
+            if subj:
+                keys.update(_subject_ranking([o[score] for o in outs], ents, offs, names, fuse, topk, dev, top_r))
+                keys.update(_ragged_keys(ents, offs, dev))
+            if opt["stage"] and subj:
+                keys.update(_open_set(keys["subject_score"], keys, opt))
+            elif opt["stage"]:
+                # the entry ranking is each probe's own (the plain ``identify`` above): its keys, stacked
+                rank = {key: torch.stack([o[key] for o in outs]) for key in ("top_idx", "top_score")}
+                keys.update(_open_set(torch.stack([o[score].view(-1) for o in outs]), rank, opt))
         _attach(outs, keys)
         return outs[0] if single else outs
     outs, sel = [], None
@@ -1042,12 +1120,15 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
             if subj:
                 # one structure for all probes: the selection's groups, positions in selection order
                 gt = index.subject_groups(sel)
-                gsc, gb = ops.group_scores(sc, gt["off_d"], gt["pos_d"], fuse, off_host=gt["off"], pos_host=gt["pos"])
+                gsc, gb = _fuse_exact(sc, gt["off_d"], gt["pos_d"], fuse, top_r, gt["off"], gt["pos"])
                 ti, ts = _rank_topk(gsc, topk)
                 labs = gt["labels_d"].view(1, -1).expand(len(outs), -1)
-                _attach(outs, _subject_keys(labs, gsc, ti, ts, ent_d[torch.gather(gb, 1, ti.long()).long()]))
+                keys = _subject_keys(labs, gsc, ti, ts, ent_d[torch.gather(gb, 1, ti.long()).long()])
             else:
-                _attach(outs, _entry_ranking(sc, ent_d, topk))
+                keys = _entry_ranking(sc, ent_d, topk)
+            if opt["stage"]:
+                keys.update(_open_set(gsc if subj else sc, keys, opt))
+            _attach(outs, keys)
     return outs[0] if single else outs
 
 
@@ -1246,7 +1327,8 @@ def _exact_many(net, probes, index, psel, ents, score, chunks, group_pairs):
 
 def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
                   coarse="fused", chunks=None, group_pairs=1024, exclude_self=False, by=None, fuse="max",
-                  impressions="all"):
+                  impressions="all", top_r=None, normalize=None, cohort=32, cohort_skip=1, sigma_floor=1e-6,
+                  threshold=None):
     """``Net.identify_many``: see there.  Subject-level (``by="subject"``) the exact stage's pair lists are
     ragged (a subject has as many pairs as impressions) and the exact scores are fused over one structure
     per probe (``_subject_ranking``).  ``exclude_self`` is then leave-one-out: the probe's own entry counts
@@ -1255,6 +1337,7 @@ def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None
     what = "identify_many"
     _check_coarse(coarse, what)
     subj = _check_by(what, index, by, fuse, impressions, shortlist)
+    opt = _check_open(what, subj, fuse, top_r, normalize, cohort, cohort_skip, sigma_floor, threshold)
     if score not in SCORES:
         raise FpmError("%s: score must be one of %s" % (what, SCORES))
     if exclude_self and probes is not index:
@@ -1289,9 +1372,11 @@ def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None
     outs, rows = _exact_many(net, probes, index, psel, ents, score, chunks, group_pairs)
     with torch.cuda.device(dev):
         if subj:
-            keys.update(_subject_ranking(rows, ents, offs, names, fuse, topk, dev))
+            keys.update(_subject_ranking(rows, ents, offs, names, fuse, topk, dev, top_r))
             keys.update(_ragged_keys(ents, offs, dev))
         else:
             keys.update(_entry_ranking(torch.stack(rows), names, topk))
+        if opt["stage"]:
+            keys.update(_open_set(keys["subject_score"] if subj else torch.stack(rows), keys, opt))
     _attach(outs, keys)
     return outs

@@ -1550,7 +1550,8 @@ class Net(nn.Module):
         return gallery.coarse_scores(self, probes, index, select=select, coarse=coarse)
 
     def identify(self, probes, index, topk=10, select=None, shortlist=None, score="cls_prob", chunks=None,
-                 coarse="fused", by=None, fuse="max", impressions="all"):
+                 coarse="fused", by=None, fuse="max", impressions="all", top_r=None, normalize=None, cohort=32,
+                 cohort_skip=1, sigma_floor=1e-6, threshold=None):
         """1:N identification against an enrolled gallery: for each probe graph (one dict, or a list)
         the shared-probe forward over the gallery entries ``select`` (an index list; default all),
         with side 1's operand rows gathered from ``index`` (no SplineConv for the gallery side) --
@@ -1597,10 +1598,36 @@ class Net(nn.Module):
         (M + 1, int32: subject m's pairs are short_idx[short_off[m]:short_off[m + 1]]) and ``coarse_all``.
         Every per-pair output equals ``identify(probe, index, select=short_idx)`` bit for bit.
         Refused: an index without labels, an unknown ``fuse`` or ``impressions``, ``impressions`` without
-        ``by``, and ``impressions="best"`` without a shortlist."""
+        ``by``, and ``impressions="best"`` without a shortlist.
+
+        Open set (is the probe's subject in the gallery at all?): three opt-in arguments; with all of them off
+        the call and its keys are everything above, unchanged.
+        ``top_r=r`` (1 <= r <= 16; needs ``by="subject", fuse="mean"``): the exact scores are fused as the mean
+        of each subject's r best impressions (``ops.group_topr``) instead of the mean of all of them, so that
+        one bad impression does not sink a genuine subject while the supporting ones still count.  The coarse
+        stage keeps fusing by max.
+        ``normalize="cohort"`` (with ``cohort=32, cohort_skip=1, sigma_floor=1e-6``): scores are not
+        comparable from probe to probe, so the ranked candidates are judged against the probe's own impostor
+        cohort: the non-NaN scores at ranks cohort_skip .. cohort_skip + cohort - 1 of the same ranked list
+        (the exact scores per entry, or the fused scores per subject; ``ops.rank_select`` to as many ranks
+        as there are, then ``ops.cohort_decide``).  Adds ``top_z`` (k: (top_score - mu) / max(sigma,
+        sigma_floor)), ``cohort_mu``, ``cohort_sigma`` (0-d fp32) and ``cohort_n`` (0-d int32: the cohort's
+        size; below 2 every z is NaN).
+        ``threshold=t``: adds ``accept`` (k, bool: top_z >= t, or top_score >= t without ``normalize``; a NaN
+        never accepts) and ``match`` (0-d int64: ``top_subject[0]``, or ``top_idx[0]`` at entry level, when
+        rank 1 is accepted, else -1).
+        The cohort is the ranked list's own next-best candidates: with a shortlist those are shortlisted
+        candidates (the best of the rest by the coarse score, a harder cohort than the gallery at large).  At
+        entry level a genuine subject's other impressions sit in the cohort and pull the z-score down:
+        subject-level search over a labelled index is the intended use.  Refused: ``top_r`` without
+        ``by="subject"`` or with another fuse, r outside [1, 16], an unknown ``normalize``, cohort < 2,
+        cohort_skip < 0, cohort_skip + cohort > 1024, a sigma_floor that is not positive and finite, a NaN
+        threshold."""
         from . import gallery
         return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
-                                shortlist=shortlist, coarse=coarse, by=by, fuse=fuse, impressions=impressions)
+                                shortlist=shortlist, coarse=coarse, by=by, fuse=fuse, impressions=impressions,
+                                top_r=top_r, normalize=normalize, cohort=cohort, cohort_skip=cohort_skip,
+                                sigma_floor=sigma_floor, threshold=threshold)
 
     # Probe sets: a *probe set* is a GalleryIndex enrolled from the probe graphs (``enroll``), with its
     # fp32 rows on the device (layout "f32" or "f32+bf16"), on the gallery's device, enrolled with the
@@ -1630,7 +1657,8 @@ class Net(nn.Module):
 
     def identify_many(self, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
                       coarse="fused", chunks=None, group_pairs=1024, exclude_self=False, by=None, fuse="max",
-                      impressions="all"):
+                      impressions="all", top_r=None, normalize=None, cohort=32, cohort_skip=1, sigma_floor=1e-6,
+                      threshold=None):
         """1:N identification of a whole probe set -> a list of dicts, one per probe of ``probe_select``
         (default all), in that order.  ``coarse_scores_many``, ``ops.rank_select`` to the ``shortlist``
         best entries per probe, one host copy of all shortlists, then the exact forward in *groups* of
@@ -1658,12 +1686,21 @@ class Net(nn.Module):
         probe.  ``exclude_self`` then means leave-one-out identification: the probe's own entry counts
         as -inf in the coarse fuse and is left out of its pair list and of its group, while the other
         impressions of its subject stay; a subject emptied that way ranks last (``subject_score`` NaN,
-        ``top_idx`` -1)."""
+        ``top_idx`` -1).
+
+        ``top_r`` / ``normalize``, ``cohort``, ``cohort_skip``, ``sigma_floor`` / ``threshold``: the open-set
+        arguments of ``identify``, with the same keys per probe (``top_z``, ``cohort_mu``, ``cohort_sigma``,
+        ``cohort_n``; ``accept``, ``match``) from the same stage (``gallery._open_set``) over each probe's own
+        ranked list.  Under ``exclude_self`` the probe's own entry is in no list, hence in no cohort; a subject
+        emptied by it (NaN) is outside every cohort, its z is NaN and it is never accepted.  As there, the
+        cohort holds shortlisted candidates when there is a shortlist, and subject-level search is the
+        intended use: at entry level a genuine subject's other impressions sit in the cohort."""
         from . import gallery
         return gallery.identify_many(self, probes, index, topk=topk, shortlist=shortlist, probe_select=probe_select,
                                      select=select, score=score, coarse=coarse, chunks=chunks,
                                      group_pairs=group_pairs, exclude_self=exclude_self, by=by, fuse=fuse,
-                                     impressions=impressions)
+                                     impressions=impressions, top_r=top_r, normalize=normalize, cohort=cohort,
+                                     cohort_skip=cohort_skip, sigma_floor=sigma_floor, threshold=threshold)
 
     def _need_backbone(self):
         if not hasattr(self, "node_layers"):

@@ -3,9 +3,9 @@
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
 no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``group_scores``,
-``coarse_score`` / ``coarse_pairs``, ``rows_fetch`` and ``rows_pack`` alone keep a plain-torch host path for CPU tensors:
-the statements of the ordering, of the group fusion, of the coarse score and of the ragged copies, which the tests
-hold the kernels to).
+``group_topr``, ``cohort_decide``, ``coarse_score`` / ``coarse_pairs``, ``rows_fetch`` and ``rows_pack`` alone keep a
+plain-torch host path for CPU tensors: the statements of the ordering, of the group fusions, of the cohort statistics,
+of the coarse score and of the ragged copies, which the tests hold the kernels to).
 """
 import ctypes
 
@@ -640,9 +640,17 @@ def group_scores(scores, off, pos, fuse="max", gscore=None, gbest=None, off_host
     Refused before any launch: dtypes, shapes, devices, offsets that do not start at 0, fall or pass
     the end of pos, a used position outside [0, G), P > 65535 (``off_host`` / ``pos_host``: host copies,
     so the check needs no device synchronisation; without them the device tensors are copied back)."""
-    op = "group_scores"
     if fuse not in GROUP_FUSE:
-        raise _lib.FpmError("%s: fuse must be one of %s" % (op, GROUP_FUSE))
+        raise _lib.FpmError("group_scores: fuse must be one of %s" % (GROUP_FUSE,))
+    mean = fuse == "mean"
+    return _group_op("group_scores", "fpm_group_scores", int(mean), scores, off, pos, gscore, gbest, off_host, pos_host,
+                     lambda s, o, p, gs, gb: _group_rows_host(s, o, p, mean, gs, gb))
+
+
+def _group_op(op, entry, arg, scores, off, pos, gscore, gbest, off_host, pos_host, rows_host):
+    """The checks and the CPU / GPU dispatch shared by ``group_scores`` and ``group_topr``: ``entry`` is the
+    C-ABI function, ``arg`` its one integer besides the structures (the fuse, or r), ``rows_host(scores (R, G),
+    off, pos, gscore, gbest)`` the statement for rows that share one structure."""
     if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
         raise _lib.FpmError("%s: scores must be a (P, G) fp32 tensor" % op)
     P, G = int(scores.shape[0]), int(scores.shape[1])
@@ -680,8 +688,8 @@ def group_scores(scores, off, pos, fuse="max", gscore=None, gbest=None, off_host
         gscore = torch.empty(P, S, device=scores.device, dtype=torch.float32)
     if gbest is None:
         gbest = torch.empty(P, S, device=scores.device, dtype=torch.int32)
-    _shape(gscore, (P, S), "group_scores gscore")
-    _shape(gbest, (P, S), "group_scores gbest")
+    _shape(gscore, (P, S), "%s gscore" % op)
+    _shape(gbest, (P, S), "%s gbest" % op)
     if gscore.dtype != torch.float32 or gbest.dtype != torch.int32 or not gscore.is_contiguous() \
             or not gbest.is_contiguous() or gscore.device != scores.device or gbest.device != scores.device:
         raise _lib.FpmError("%s: gscore must be contiguous fp32, gbest contiguous int32, on the scores' device" % op)
@@ -691,22 +699,183 @@ def group_scores(scores, off, pos, fuse="max", gscore=None, gbest=None, off_host
         gscore.fill_(float("nan"))
         gbest.fill_(-1)
         return gscore, gbest
-    mean = fuse == "mean"
     if not scores.is_cuda:
         if per_row:
             for p in range(P):
-                _group_rows_host(scores[p:p + 1], oh2[p], ph2[p], mean, gscore[p:p + 1], gbest[p:p + 1])
+                rows_host(scores[p:p + 1], oh2[p], ph2[p], gscore[p:p + 1], gbest[p:p + 1])
         else:
-            _group_rows_host(scores, oh2[0], ph2[0], mean, gscore, gbest)
+            rows_host(scores, oh2[0], ph2[0], gscore, gbest)
         return gscore, gbest
     if G > 1 and scores.stride(1) != 1:
         scores = scores.contiguous()
     ld = int(scores.stride(0)) if P > 1 else G
     if ld < G:
         scores, ld = scores.contiguous(), G
-    _lib.call("fpm_group_scores", _p(scores), ld, P, G, _p(off), S + 1 if per_row else 0, _p(pos), L if per_row else 0, S,
-              int(mean), _p(gscore), _p(gbest), _stream(scores))
+    _lib.call(entry, _p(scores), ld, P, G, _p(off), S + 1 if per_row else 0, _p(pos), L if per_row else 0, S,
+              int(arg), _p(gscore), _p(gbest), _stream(scores))
     return gscore, gbest
+
+
+TOPR_MAX = 16
+
+
+def _topr_rows_host(scores, off, pos, r, gscore, gbest):
+    """The statement of fpm_group_topr for rows that share one structure (arguments as ``_group_rows_host``).
+
+    gbest: ``_group_rows_host``'s.  gscore, for a group of c >= 1 entries x[0..c): r' = min(r, c); the entries
+    in descending order of their score's ``rank_key`` bits (NaN last; a stable sort, though entries that tie
+    have one value, so their order changes no bit); s = +0.0, then s = s + x1, ..., s = s + x_r', each one
+    fp32 addition; s / fp32(r'), NaN as 0x7FC00000."""
+    R = int(scores.shape[0])
+    _group_rows_host(scores, off, pos, False, gscore, gbest)            # gbest; gscore is overwritten below
+    bits = (rank_key(scores) >> 32) if R else scores.new_zeros(scores.shape, dtype=torch.int64)
+    cnt = off[1:] - off[:-1]
+    qnan = torch.full((), float("nan"), dtype=torch.float32)
+    for c in sorted(set(cnt[cnt > 0].tolist())):
+        gs = torch.nonzero(cnt == c).view(-1)
+        at = pos[off[gs].view(-1, 1) + torch.arange(c, dtype=torch.int64).view(1, -1)]          # (ng, c)
+        order = torch.sort(bits[:, at], dim=2, descending=True, stable=True).indices[..., :min(r, c)]
+        x = torch.gather(scores[:, at], 2, order)                                               # (R, ng, r')
+        acc = torch.zeros(R, int(gs.numel()), dtype=torch.float32)
+        for i in range(min(r, c)):
+            acc = acc + x[..., i]
+        val = acc / torch.full((), float(min(r, c)), dtype=torch.float32)
+        gscore[:, gs] = torch.where(torch.isnan(val), qnan, val)
+
+
+def group_topr(scores, off, pos, r, gscore=None, gbest=None, off_host=None, pos_host=None):
+    """The mean of each group's r best entries (fpm_group_topr; open-set search: a genuine subject's score
+    rests on its r best impressions, a bad one does not sink it).  Arguments, structures, refusals and
+    dispatch as ``group_scores``; 1 <= r <= TOPR_MAX -> (gscore (P, S) fp32, gbest (P, S) int32).
+
+    gbest: ``group_scores``'s.  gscore of a group of c >= 1 entries: r' = min(r, c), the r' entries with the
+    largest ``rank_key`` in descending order x1 .. x_r', s = +0.0, s = s + x1, ..., s = s + x_r' (fp32
+    additions in that order), s / fp32(r') correctly rounded; NaN ranks last, so it enters (and propagates)
+    only when the group holds fewer than r' numbers; infinities propagate; a NaN result is 0x7FC00000.  r = 1
+    is the max as a number (the bits differ where the best is -0.0, which 0.0 + -0.0 turns into +0.0, or a
+    NaN with other bits).  An empty group: NaN, -1.  A group's result depends on its own entries and their order
+    alone.  Device tensors run the kernel; CPU tensors take the statement (``_topr_rows_host``), which the
+    kernel equals bit for bit."""
+    if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r <= TOPR_MAX:
+        raise _lib.FpmError("group_topr: r = %r outside [1, %d] (an integer)" % (r, TOPR_MAX))
+    return _group_op("group_topr", "fpm_group_topr", r, scores, off, pos, gscore, gbest, off_host, pos_host,
+                     lambda s, o, p, gs, gb: _topr_rows_host(s, o, p, r, gs, gb))
+
+
+COHORT_WINDOW = 1024            # skip + cohort at most: 16 strided rounds of 64 lanes
+
+
+def _lane_sum64(v):
+    """L(v) of ``cohort_decide`` over the last dimension (a multiple of 64, padded with +0.0): 64 lanes, lane t
+    starts from +0.0 and adds v[t], v[t + 64], ... in order; then for m = 32 .. 1 every lane takes
+    v + v[lane ^ m]; lane 0's value.  (``_group_rows_host``'s order with W = 64 always; a padding +0.0 changes
+    no bit: a lane's value is never -0.0.)"""
+    v = v.view(v.shape[0], -1, 64)
+    acc = torch.zeros(v.shape[0], 64, dtype=torch.float32)
+    for i in range(v.shape[1]):
+        acc = acc + v[:, i, :]
+    lanes = torch.arange(64)
+    m = 32
+    while m:
+        acc = acc + acc[:, lanes ^ m]
+        m //= 2
+    return acc[:, 0]
+
+
+def _cohort_host(top, k, skip, cohort, sigma_floor):
+    """The statement of fpm_cohort_decide's statistics and z-scores on a CPU tensor -> (z (P, k), mu, sigma (P,),
+    n (P,) int32).  Every line is one rounded fp32 operation per element; the square is a product of its own,
+    not fused into the sum."""
+    P, K = int(top.shape[0]), int(top.shape[1])
+    qnan = torch.full((), float("nan"), dtype=torch.float32)
+    win = top[:, skip:min(K, skip + cohort)]
+    W = int(win.shape[1])
+    pad = max(1, (W + 63) // 64) * 64
+    ok = ~torch.isnan(win)
+    n = ok.sum(1)
+    # the non-NaN values in column order, then +0.0 up to a multiple of 64
+    front = torch.argsort((~ok).to(torch.int8), dim=1, stable=True)
+    x = torch.zeros(P, pad, dtype=torch.float32)
+    live = torch.zeros(P, pad, dtype=torch.bool)
+    x[:, :W] = torch.where(torch.arange(W).view(1, -1) < n.view(-1, 1), torch.gather(win, 1, front),
+                           torch.zeros((), dtype=torch.float32))
+    live[:, :W] = torch.arange(W).view(1, -1) < n.view(-1, 1)
+    fn = n.clamp(min=1).to(torch.float32)
+    mu = _lane_sum64(x) / fn
+    d = x - mu.view(-1, 1)
+    q = torch.where(live, d * d, torch.zeros((), dtype=torch.float32))
+    var = _lane_sum64(q) / fn
+    # the correctly rounded fp32 root by way of float64 (53 >= 2 * 24 + 2 bits: rounding twice is exact for a square
+    # root); torch's own fp32 sqrt is a vector-library call on some hosts, within an ulp but not correctly rounded
+    sigma = torch.sqrt(var.to(torch.float64)).to(torch.float32)
+    mu = torch.where((n < 2) | torch.isnan(mu), qnan, mu)
+    sigma = torch.where((n < 2) | torch.isnan(sigma), qnan, sigma)
+    s = torch.where(torch.isnan(sigma), qnan, torch.maximum(sigma, torch.full((), sigma_floor, dtype=torch.float32)))
+    z = (top[:, :k] - mu.view(-1, 1)) / s.view(-1, 1)
+    return torch.where(torch.isnan(z), qnan, z), mu, sigma, n.to(torch.int32)
+
+
+def cohort_decide(top, k, skip=1, cohort=32, sigma_floor=1e-6, threshold=None, normalize=True):
+    """z-scores of ranked rows against their own impostor cohorts, and an accept decision (fpm_cohort_decide;
+    open-set search: scores are not comparable from probe to probe, a probe's candidates are judged against that
+    probe's next-best candidates).  top (P, K) fp32 contiguous, each row as ``rank_select`` returns it (descending,
+    NaN last); 1 <= k <= K, skip >= 0, cohort >= 2, skip + cohort <= COHORT_WINDOW
+    -> (z (P, k) fp32, mu (P,), sigma (P,), n (P,) int32, accept (P, k) int32), None for the parts not asked for:
+    ``normalize=False`` computes no statistics (z, mu, sigma, n are None), ``threshold=None`` no accept.
+
+    Row p's cohort: the non-NaN values among columns skip <= j < min(K, skip + cohort), in column order,
+    x[0..n).  mu = L(x) / fp32(n) (L: ``_lane_sum64``), d_j = x_j - mu, q_j = d_j * d_j, var = L(q) / fp32(n),
+    sigma = sqrt(var), each a single rounded fp32 operation; n < 2: mu = sigma = NaN and every z is NaN.
+    s = max(sigma, sigma_floor) (NaN if sigma is), z_j = (top[p, j] - mu) / s.  accept_j = (v_j >= threshold),
+    v = z, or top with ``normalize=False``; a NaN never accepts; 0 / 1.  ``sigma_floor`` and ``threshold`` are
+    taken as fp32.  Every NaN returned is 0x7FC00000.
+
+    CPU tensors take the statement (``_cohort_host``), device tensors the kernel, which equals it bit for bit.
+    Refused before any launch: dtype, shape, contiguity, the ranges above, a NaN threshold, a sigma_floor that is not a positive finite fp32 number, nothing asked for, P > 65535."""
+    op = "cohort_decide"
+    if not isinstance(top, torch.Tensor) or top.dim() != 2 or top.dtype != torch.float32:
+        raise _lib.FpmError("%s: top must be a (P, K) fp32 tensor" % op)
+    if not top.is_contiguous():
+        raise _lib.FpmError("%s: top must be contiguous" % op)
+    P, K = int(top.shape[0]), int(top.shape[1])
+    for name, v in (("k", k), ("skip", skip), ("cohort", cohort)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise _lib.FpmError("%s: %s must be an integer (got %r)" % (op, name, v))
+    if not 1 <= k <= K:
+        raise _lib.FpmError("%s: k = %d outside [1, K = %d]" % (op, k, K))
+    if skip < 0 or cohort < 2 or skip + cohort > COHORT_WINDOW:
+        raise _lib.FpmError("%s: skip = %d, cohort = %d (skip >= 0, cohort >= 2, skip + cohort <= %d)"
+                            % (op, skip, cohort, COHORT_WINDOW))
+    if not normalize and threshold is None:
+        raise _lib.FpmError("%s: nothing to compute (normalize=False and threshold=None)" % op)
+    floor32 = float(torch.tensor(float(sigma_floor), dtype=torch.float32))
+    if normalize and not 0.0 < floor32 < float("inf"):
+        raise _lib.FpmError("%s: sigma_floor must be a positive finite fp32 number (got %r)" % (op, sigma_floor))
+    thr32 = None
+    if threshold is not None:
+        thr32 = float(torch.tensor(float(threshold), dtype=torch.float32))
+        if thr32 != thr32:
+            raise _lib.FpmError("%s: threshold is NaN" % op)
+    if P > 65535:
+        raise _lib.FpmError("%s: at most 65535 rows per call" % op)
+    if not top.is_cuda:
+        z = mu = sigma = n = accept = None
+        if normalize:
+            z, mu, sigma, n = _cohort_host(top, k, skip, cohort, floor32)
+        if thr32 is not None:
+            accept = ((z if normalize else top[:, :k]) >= thr32).to(torch.int32)
+        return z, mu, sigma, n, accept
+    new = lambda shape, dt: torch.empty(shape, device=top.device, dtype=dt)
+    z = mu = sigma = n = accept = None
+    if normalize:
+        z, mu, sigma, n = new((P, k), torch.float32), new((P,), torch.float32), new((P,), torch.float32), new((P,), torch.int32)
+    if thr32 is not None:
+        accept = new((P, k), torch.int32)
+    if P:
+        _lib.call("fpm_cohort_decide", _p(top), P, K, k, skip, cohort, floor32 if normalize else 1.0, int(bool(normalize)),
+                  int(thr32 is not None), 0.0 if thr32 is None else thr32, _p(z), _p(mu), _p(sigma), _p(n), _p(accept),
+                  _stream(top))
+    return z, mu, sigma, n, accept
 
 
 COARSE_NMAX = 128

@@ -568,6 +568,39 @@ int fpm_rank_select(const float* scores, long ld, int P, int G, int k, int* top_
  * scratch.  P <= 65535. */
 int fpm_group_scores(const float* scores, long ld, int P, int G, const int* grp_off, long off_ld,
                      const int* grp_pos, long pos_ld, int S, int fuse, float* gscore, int* gbest, void* stream);
+/* ---- open-set search: top-r fusion, cohort z-scores, accept ---------------------------------------
+ * The mean of each group's r best entries, 1 <= r <= FPM_TOPR_MAX; every other argument, the structures
+ * and gbest as fpm_group_scores takes and gives them.  For a group of c >= 1 entries: r' = min(r, c); the r'
+ * entries that rank first (score descending as fpm_rank_topk orders scores, NaN last; entries that tie have
+ * one value, so their order changes no bit), x1 .. x_r'; s = +0.0, s = s + x1, ..., s = s + x_r', each one
+ * fp32 addition in that order; gscore = s / fp32(r'), correctly rounded, a NaN as 0x7FC00000.  NaN ranks
+ * last, so it enters (and propagates) only when the group holds fewer than r' numbers; infinities
+ * propagate.  An empty group gives 0x7FC00000, -1.  A group's result depends on its own entries and their
+ * order alone.  The selection runs r rounds of a scan and an xor butterfly per team (16 lanes, 64 over 1024
+ * entries); one launch, no atomics, no LDS, no scratch.  P <= 65535. */
+#define FPM_TOPR_MAX 16
+int fpm_group_topr(const float* scores, long ld, int P, int G, const int* grp_off, long off_ld, const int* grp_pos,
+                   long pos_ld, int S, int r, float* gscore, int* gbest, void* stream);
+/* z-scores of the first k columns of ranked rows against each row's own impostor cohort, and an accept
+ * decision.  top: P rows of K fp32 values, contiguous, each as fpm_rank_select returns it (descending, NaN
+ * last); 1 <= k <= K, skip >= 0, cohort >= 2, skip + cohort <= FPM_COHORT_WINDOW.  Row p's cohort: the
+ * non-NaN values among columns skip <= j < min(K, skip + cohort), in column order, x[0 .. n).
+ *   L(v): 64 lanes; lane t starts at +0.0 and adds v[t], v[t + 64], ... in order; then for m = 32 .. 1 every
+ *   lane takes v + v[lane ^ m]; lane 0 holds the sum.
+ *   mu = L(x) / fp32(n); d_j = x_j - mu; q_j = d_j * d_j (not fused into the sum); var = L(q) / fp32(n);
+ *   sigma = sqrt(var); every operation one correctly rounded fp32 operation.  n < 2: mu = sigma = NaN.
+ *   s = max(sigma, sigma_floor), NaN if sigma is; z[p][j] = (top[p][j] - mu) / s for j < k.
+ *   accept[p][j] = (v >= threshold) as int32 0 / 1, v = z[p][j] with normalize, top[p][j] without; a NaN
+ *   never accepts.
+ * normalize (0 / 1): compute and write z (P, k), mu, sigma (P) and n (P, int32: the cohort's size); with 0
+ * they are not touched and may be NULL.  decide (0 / 1): write accept (P, k); with 0 it may be NULL and
+ * threshold is not read.  At least one of the two; sigma_floor a positive finite number; threshold not NaN
+ * (either infinity is fine).  Every NaN written is 0x7FC00000.  One wave per row, four rows per workgroup, 4 KB
+ * of LDS per wave (the compacted cohort); P <= 65535. */
+#define FPM_COHORT_WINDOW 1024
+int fpm_cohort_decide(const float* top, int P, int K, int k, int skip, int cohort, float sigma_floor, int normalize,
+                      int decide, float threshold, float* z, float* mu, float* sigma, int* n, int* accept,
+                      void* stream);
 
 /* ---- coarse 1:N score (the first pass of a shortlisted identification) ---------------------------
  * One scalar per (probe, enrolled entry) pair, one workgroup per pair, B pairs per launch:
