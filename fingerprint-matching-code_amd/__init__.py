@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == "GalleryIndex":
         from .gallery import GalleryIndex
         return GalleryIndex
+    if name == "ShardedGallery":
+        from .sharded_gallery import ShardedGallery
+        return ShardedGallery
     raise AttributeError(name)

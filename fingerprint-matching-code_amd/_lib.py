@@ -51,6 +51,7 @@ SIGNATURES = {
     "fpm_group_scores": (I, [P, L, I, I, P, L, P, L, I, I, P, P, P]),
     "fpm_group_topr": (I, [P, L, I, I, P, L, P, L, I, I, P, P, P]),
     "fpm_cohort_decide": (I, [P, I, I, I, I, I, F, I, I, F, P, P, P, P, P, P]),
+    "fpm_topk_merge": (I, [P, P, L, I, ctypes.POINTER(I), I, I, P, P, P, P]),
     "fpm_coarse_score_wide_ws_bytes": (L, [I]),
     "fpm_coarse_score_stream_ws_bytes": (L, [I, I, I]),
     "fpm_rows_fetch": (I, [P, L, P, P, I, I, I, P, L, P, P]),

@@ -59,6 +59,11 @@ Open set (``top_r``, ``normalize="cohort"``, ``threshold``; all off by default, 
 ``top_r`` makes the exact-stage fuse the mean of a subject's r best impressions (``ops.group_topr``);
 ``_open_set`` takes ``ops.rank_select`` of the row the ranking ranked and ``ops.cohort_decide``: z-scores of the
 top k against the next-best candidates of the same list, ``accept`` per rank and one ``match`` per probe.
+
+Several GPUs (``sharded_gallery.ShardedGallery``): ``GalleryIndex.slice`` cuts an index into parts; ``identify``
+over a sharded gallery branches to ``identify_sharded`` there, which runs the stages above per shard and merges the
+shards' shortlists (``ops.topk_merge``); ``probe_batch(pad_to=...)`` lays a shard's part of a list out in the whole
+list's box, so that the parts' outputs are the one-index forward's.
 """
 import contextlib
 import hashlib
@@ -271,25 +276,70 @@ class GalleryIndex:
         self._stage = (sel, buf, buf[:total], off_d, off_h)
         return self._stage[2:]
 
-    def _selection(self, select):
+    def slice(self, entries, device=None):
+        """A new GalleryIndex holding the entries ``entries`` (host int64, ascending, no repeats) in that
+        order, on ``device`` (default: this index's): the rows (``y``, ``y16``, ``P``) and edges (``src``,
+        ``dst``, ``pseudo``) of those entries copied by their row and edge ranges, ``n``, ``w`` and ``subject``
+        by entry, the offsets rebuilt; layout, ``sc_mode``, ``_pack_gen`` and ``weights_id`` kept.  A
+        "bf16+host" slice gets pinned host rows of its own.  Every field of the slice holds the parent's
+        bytes for those entries (``ShardedGallery.split`` cuts an index into shards with it)."""
+        ent = torch.as_tensor(entries)
+        if ent.dtype != torch.int64 or ent.is_cuda or ent.dim() != 1 or ent.numel() == 0:
+            raise FpmError("GalleryIndex.slice: entries must be a non-empty 1-D host int64 tensor")
+        if int(ent[0]) < 0 or int(ent[-1]) >= self.G or bool((ent[1:] <= ent[:-1]).any()):
+            raise FpmError("GalleryIndex.slice: entries must ascend without repeats inside [0, %d)" % self.G)
+        dev = self.device if device is None else torch.device(device)
+        src_dev = self.device
+
+        def ranges(off):
+            # the numbers off[e] .. off[e + 1] of every entry e, concatenated -> (host int64 index, new offsets)
+            cnt = off[ent + 1] - off[ent]
+            new = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
+            at = torch.arange(int(new[-1]), dtype=torch.int64)
+            return at + torch.repeat_interleave(off[ent] - new[:-1], cnt), new
+
+        rows, row_off = ranges(self.row_off_host)
+        edges, edge_off = ranges(self.edge_off)
+        rows_d, edges_d, ent_d = rows.to(src_dev), edges.to(src_dev), ent.to(src_dev)
+        take = lambda t, at: t[at].to(dev)
+        if self.layout == "bf16+host":
+            y = _host_rows((int(rows.numel()), self.y.shape[1]), dev)
+            torch.index_select(self.y, 0, rows, out=y)
+        else:
+            y = take(self.y, rows_d)
+        return GalleryIndex(y, row_off.to(dev), self.n[ent], take(self.src, edges_d), take(self.dst, edges_d),
+                            take(self.pseudo, edges_d), edge_off, take(self.w, ent_d),
+                            None if self.P is None else take(self.P, rows_d), self.sc_mode, self._pack_gen,
+                            self.weights_id, y16=None if self.y16 is None else take(self.y16, rows_d),
+                            layout=self.layout, subject=None if self.subject is None else self.subject[ent])
+
+    def _selection(self, select, pad_to=None):
         """Side 1 of a probe x gallery batch over the entries ``select`` (None: all), in that order,
         as DeviceBatch.from_pairs lays it out: (sel host int64, dict of batch fields).  Independent
-        of the probe, so the last selection's data is kept for the next query."""
+        of the probe, so the last selection's data is kept for the next query (``pad_to``, see
+        ``_gather``, is part of what is kept)."""
         sel = _select_host(self, select, "identify")
-        if self._sel is not None and torch.equal(self._sel[0], sel):
-            return self._sel
-        self._sel = (sel, self._gather(sel))
-        return self._sel
+        if self._sel is not None and torch.equal(self._sel[0], sel) and self._sel[2] == pad_to:
+            return self._sel[:2]
+        self._sel = (sel, self._gather(sel, pad_to), pad_to)
+        return self._sel[:2]
 
-    def _gather(self, sel):
+    def _gather(self, sel, pad_to=None):
         """One side's batch fields of the pairs whose graph on that side is entry sel[b] (host int64,
         checked by the caller; repeats are fine), as DeviceBatch.from_pairs lays that side out.  Reads
         and writes no cache: ``_selection`` keeps the last one-probe selection, a pair batch
-        (``pair_batch``) gathers each side afresh."""
+        (``pair_batch``) gathers each side afresh.  ``pad_to`` (None: the selection's own largest
+        keypoint count, as ever): the side's padded size, at least that count -- a part of a list laid
+        out in the whole list's box (``ShardedGallery``)."""
         dev = self.device
         B = int(sel.numel())
         n2 = self.n[sel]
         nmax = int(n2.max())
+        if pad_to is not None:
+            if int(pad_to) < nmax:
+                raise FpmError("identify: pad_to = %d below the selection's largest graph (%d keypoints)"
+                               % (int(pad_to), nmax))
+            nmax = int(pad_to)
         cnt = self.edge_off[sel + 1] - self.edge_off[sel]
         eo = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
         E = int(eo[-1])
@@ -646,10 +696,11 @@ def _probe_tensors(probe, dev):
     return int(probe["n"]), x.contiguous(), ei, ps.reshape(-1, 2), w.reshape(-1)
 
 
-def probe_batch(probe, index, select=None):
-    """The probe x gallery batch of one probe graph over ``index`` -> (_CachedBatch, sel host int64)."""
+def probe_batch(probe, index, select=None, pad_to=None):
+    """The probe x gallery batch of one probe graph over ``index`` -> (_CachedBatch, sel host int64).
+    ``pad_to``: the gallery side's padded size (``GalleryIndex._gather``; None: the selection's own)."""
     dev = index.device
-    sel, f = index._selection(select)
+    sel, f = index._selection(select, pad_to)
     n0, x0, ei, ps, w0 = _probe_tensors(probe, dev)
     B = int(sel.numel())
     e0 = int(ei.shape[1])
@@ -1073,8 +1124,16 @@ def _check_eager(net, what):
 
 def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None, shortlist=None,
              coarse="fused", by=None, fuse="max", impressions="all", top_r=None, normalize=None, cohort=32,
-             cohort_skip=1, sigma_floor=1e-6, threshold=None):
+             cohort_skip=1, sigma_floor=1e-6, threshold=None, coarse_all=True):
     """``Net.identify``: see there."""
+    from .sharded_gallery import ShardedGallery, identify_sharded
+    if isinstance(index, ShardedGallery):
+        return identify_sharded(net, probes, index, topk=topk, select=select, score=score, chunks=chunks,
+                                shortlist=shortlist, coarse=coarse, by=by, fuse=fuse, impressions=impressions,
+                                top_r=top_r, normalize=normalize, cohort=cohort, cohort_skip=cohort_skip,
+                                sigma_floor=sigma_floor, threshold=threshold, coarse_all=coarse_all)
+    if coarse_all is not True:
+        raise FpmError("identify: coarse_all is a keyword of the query over a ShardedGallery")
     _check_coarse(coarse, "identify")
     subj = _check_by("identify", index, by, fuse, impressions, shortlist)
     opt = _check_open("identify", subj, fuse, top_r, normalize, cohort, cohort_skip, sigma_floor, threshold)
@@ -1158,6 +1217,10 @@ def _check_probe_set(probes, index, what):
 def _check_many(net, probes, index, what):
     """The refusals shared by ``match_pairs``, ``coarse_scores_many`` and ``identify_many``: the probe
     set's own (they need no net), then those of ``identify``."""
+    from .sharded_gallery import ShardedGallery
+    if isinstance(index, ShardedGallery) or isinstance(probes, ShardedGallery):
+        raise FpmError("%s: not supported over a ShardedGallery (probe sets over shards are not built; query it "
+                       "with identify(probes, sharded, shortlist=M))" % what)
     if not isinstance(index, GalleryIndex):
         raise FpmError("%s: index must be a GalleryIndex (Net.enroll)" % what)
     _check_probe_set(probes, index, what)

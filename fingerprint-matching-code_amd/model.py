@@ -1551,7 +1551,7 @@ class Net(nn.Module):
 
     def identify(self, probes, index, topk=10, select=None, shortlist=None, score="cls_prob", chunks=None,
                  coarse="fused", by=None, fuse="max", impressions="all", top_r=None, normalize=None, cohort=32,
-                 cohort_skip=1, sigma_floor=1e-6, threshold=None):
+                 cohort_skip=1, sigma_floor=1e-6, threshold=None, coarse_all=True):
         """1:N identification against an enrolled gallery: for each probe graph (one dict, or a list)
         the shared-probe forward over the gallery entries ``select`` (an index list; default all),
         with side 1's operand rows gathered from ``index`` (no SplineConv for the gallery side) --
@@ -1622,12 +1622,24 @@ class Net(nn.Module):
         subject-level search over a labelled index is the intended use.  Refused: ``top_r`` without
         ``by="subject"`` or with another fuse, r outside [1, 16], an unknown ``normalize``, cohort < 2,
         cohort_skip < 0, cohort_skip + cohort > 1024, a sigma_floor that is not positive and finite, a NaN
-        threshold."""
+        threshold.
+
+        A gallery over several GPUs: ``index`` may be an ``fpm.ShardedGallery`` (shards of the gallery, each a
+        ``GalleryIndex`` on its own device).  ``shortlist=M`` is then required; every shard runs the coarse pass
+        and its own shortlist on its device, the lists are merged on the gallery's ``output_device``
+        (``ops.topk_merge``), the exact forward runs on the shards that hold the shortlisted entries, and the
+        ranking, the subject fusion and the open-set stage are the ones above, on ``output_device``.  Every
+        query key equals the same call over the same gallery in one index, entry numbers being the gallery's
+        global ones; of the forward's outputs the per-pair ones are carried (``s``, ``ss``, ``ds_mat``,
+        ``perm_mat``, ``k_prob``, ``cls_prob``, ``cls_logits``), the batch-level ones (the losses, ``lsa``,
+        ``sk_steps``, ``Kp``, ``coef``, ``ss64``) are not.  ``coarse_all=False`` (sharded only) drops the (G,) row
+        of all coarse scores.  Refused there: ``shortlist=None``, ``select``, and ``by="subject"`` when a
+        subject's impressions sit in more than one shard."""
         from . import gallery
         return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
                                 shortlist=shortlist, coarse=coarse, by=by, fuse=fuse, impressions=impressions,
                                 top_r=top_r, normalize=normalize, cohort=cohort, cohort_skip=cohort_skip,
-                                sigma_floor=sigma_floor, threshold=threshold)
+                                sigma_floor=sigma_floor, threshold=threshold, coarse_all=coarse_all)
 
     # Probe sets: a *probe set* is a GalleryIndex enrolled from the probe graphs (``enroll``), with its
     # fp32 rows on the device (layout "f32" or "f32+bf16"), on the gallery's device, enrolled with the

@@ -2,10 +2,11 @@
 
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
-no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``group_scores``,
-``group_topr``, ``cohort_decide``, ``coarse_score`` / ``coarse_pairs``, ``rows_fetch`` and ``rows_pack`` alone keep a
-plain-torch host path for CPU tensors: the statements of the ordering, of the group fusions, of the cohort statistics,
-of the coarse score and of the ragged copies, which the tests hold the kernels to).
+no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``topk_merge``,
+``group_scores``, ``group_topr``, ``cohort_decide``, ``coarse_score`` / ``coarse_pairs``, ``rows_fetch`` and
+``rows_pack`` alone keep a plain-torch host path for CPU tensors: the statements of the ordering and of the merge of
+sorted lists, of the group fusions, of the cohort statistics, of the coarse score and of the ragged copies, which the
+tests hold the kernels to).
 """
 import ctypes
 
@@ -483,16 +484,20 @@ def rows_pack(src, n, nmax, out_off, out32=None, out16=None, n_host=None, out_of
     return out32, out16
 
 
-def rank_key(scores):
+def rank_key(scores, ids=None):
     """The 64-bit ranking key of fpm_rank_topk for a (P, G) fp32 tensor, as int64 whose signed order
     is the key's unsigned order shifted by 2^63: (order-preserving bits of the score) << 32 |
-    (0xFFFFFFFF - index); NaN maps below -inf, -0 below +0."""
+    (0xFFFFFFFF - index); NaN maps below -inf, -0 below +0.  ``ids`` (integers of scores' shape, each in
+    [0, 2^32)): taken in place of the column number (``topk_merge``'s key)."""
     s = scores.detach().to(torch.float32)
     u = s.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
     neg = u >= 0x80000000
     bits = torch.where(neg, 0xFFFFFFFF - u, u + 0x80000000)
     bits = torch.where(torch.isnan(s), torch.zeros_like(bits), bits)
-    i = torch.arange(s.shape[-1], device=s.device, dtype=torch.int64).expand_as(bits)
+    if ids is None:
+        i = torch.arange(s.shape[-1], device=s.device, dtype=torch.int64).expand_as(bits)
+    else:
+        i = ids.to(torch.int64) & 0xFFFFFFFF
     return ((bits - 0x80000000) << 32) | (0xFFFFFFFF - i)
 
 
@@ -573,6 +578,87 @@ def rank_select(scores, k, top_idx=None, top_score=None):
     ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
     _lib.call("fpm_rank_select", _p(scores), ld, P, G, k, _p(top_idx), _p(top_score), _p(ws), wsb, _stream(scores))
     return top_idx, top_score
+
+
+TOPK_MERGE_SMAX = 16
+
+
+def topk_merge(score, ids, list_off, k, top_id=None, top_score=None, top_col=None):
+    """Per row, the k best of S sorted candidate lists (fpm_topk_merge; a gallery spread over several
+    devices merges its shards' shortlists with it).  score (P, L) fp32 and ids (P, L) int32 >= 0 (any row
+    stride, the columns dense); ``list_off``: S + 1 host integers rising from 0 to L, list t the columns
+    [list_off[t], list_off[t + 1]), possibly empty; S <= 16, a list at most 1024 long, P <= 65535,
+    1 <= k <= min(L, 1024).  The key of a candidate is ``rank_key(score, ids)``: ``rank_select``'s key with the
+    id in place of the column, so ties go to the lower id.  Precondition: every list strictly descending by
+    key, the ids of a row distinct.
+    -> (top_id (P, k) int32, top_score (P, k) fp32, top_col (P, k) int32): the k largest keys, descending:
+    their ids, scores (the same bits) and columns (caller-allocated on the device path when given).
+
+    CPU tensors take the statement: a stable descending sort of the key; the precondition is checked there
+    and a violation raises.  Device tensors run the kernel, which equals the statement bit for bit and does
+    not check the precondition (it stays inside its buffers whatever the data)."""
+    op = "topk_merge"
+    if not isinstance(score, torch.Tensor) or score.dim() != 2 or score.dtype != torch.float32:
+        raise _lib.FpmError("%s: score must be a (P, L) fp32 tensor" % op)
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or tuple(ids.shape) != tuple(score.shape):
+        raise _lib.FpmError("%s: ids must be an int32 tensor of score's shape %s" % (op, tuple(score.shape)))
+    if ids.device != score.device:
+        raise _lib.FpmError("%s: ids is on %s, score on %s" % (op, ids.device, score.device))
+    off = torch.as_tensor(list_off).detach().cpu().view(-1)
+    if off.dtype not in (torch.int64, torch.int32) or off.numel() < 2:
+        raise _lib.FpmError("%s: list_off must be S + 1 >= 2 host integers" % op)
+    off = off.to(torch.int64)
+    S = int(off.numel()) - 1
+    if S > TOPK_MERGE_SMAX:
+        raise _lib.FpmError("%s: S = %d lists, at most %d" % (op, S, TOPK_MERGE_SMAX))
+    length = off[1:] - off[:-1]
+    if int(off[0]) != 0 or bool((length < 0).any()):
+        raise _lib.FpmError("%s: list_off must start at 0 and must not fall" % op)
+    if int(length.max()) > RANK_SELECT_KMAX:
+        raise _lib.FpmError("%s: a list of %d candidates, at most %d" % (op, int(length.max()), RANK_SELECT_KMAX))
+    P, L = int(score.shape[0]), int(score.shape[1])
+    if int(off[-1]) != L:
+        raise _lib.FpmError("%s: list_off ends at %d, a row holds %d candidates" % (op, int(off[-1]), L))
+    k = int(k)
+    if not 1 <= k <= min(L, RANK_SELECT_KMAX):
+        raise _lib.FpmError("%s: k = %d outside [1, min(L, %d) = %d]" % (op, k, RANK_SELECT_KMAX, min(L, RANK_SELECT_KMAX)))
+    if P > 65535:
+        raise _lib.FpmError("%s: at most 65535 rows per call" % op)
+    if not score.is_cuda:
+        if P and int(ids.min()) < 0:
+            raise _lib.FpmError("%s: a negative id" % op)
+        keys = rank_key(score, ids)
+        inner = torch.ones(L, dtype=torch.bool)
+        inner[off[:-1][length > 0]] = False                      # a list's first column has no left neighbour
+        if P and L > 1 and bool(((keys[:, 1:] >= keys[:, :-1]) & inner[1:]).any()):
+            raise _lib.FpmError("%s: a list is not strictly descending by key" % op)
+        srt = torch.sort(ids, dim=1).values
+        if P and L > 1 and bool((srt[:, 1:] == srt[:, :-1]).any()):
+            raise _lib.FpmError("%s: an id twice in one row" % op)
+        col = torch.argsort(keys, dim=1, descending=True, stable=True)[:, :k]
+        return torch.gather(ids, 1, col), torch.gather(score, 1, col), col.to(torch.int32)
+    if L > 1 and (score.stride(1) != 1 or ids.stride(1) != 1):
+        score, ids = score.contiguous(), ids.contiguous()
+    ld = int(score.stride(0)) if P > 1 else L
+    if ld < L or (P > 1 and int(ids.stride(0)) != ld):
+        score, ids, ld = score.contiguous(), ids.contiguous(), L
+    dev = score.device
+    outs = []
+    for name, t, dt in (("top_id", top_id, torch.int32), ("top_score", top_score, torch.float32),
+                        ("top_col", top_col, torch.int32)):
+        if t is None:
+            t = torch.empty(P, k, device=dev, dtype=dt)
+        _shape(t, (P, k), "%s %s" % (op, name))
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise _lib.FpmError("%s: %s must be contiguous %s on score's device" % (op, name, dt))
+        outs.append(t)
+    top_id, top_score, top_col = outs
+    if P == 0:
+        return top_id, top_score, top_col
+    offs = (ctypes.c_int * (S + 1))(*off.tolist())
+    _lib.call("fpm_topk_merge", _p(score), _p(ids), ld, P, offs, S, k, _p(top_id), _p(top_score), _p(top_col),
+              _stream(score))
+    return top_id, top_score, top_col
 
 
 GROUP_FUSE = ("max", "mean")

@@ -601,6 +601,25 @@ int fpm_group_topr(const float* scores, long ld, int P, int G, const int* grp_of
 int fpm_cohort_decide(const float* top, int P, int K, int k, int skip, int cohort, float sigma_floor, int normalize,
                       int decide, float threshold, float* z, float* mu, float* sigma, int* n, int* accept,
                       void* stream);
+/* ---- merge of sorted candidate lists (a gallery over several devices) -------------------------------
+ * Per row, the k best of S sorted candidate lists.  Row p holds L = list_off[S] candidates: scores at
+ * score + p * ld (fp32), ids at id + p * ld (int32, >= 0); list t is the columns [list_off[t], list_off[t + 1])
+ * and may be empty.  list_off: S + 1 offsets on the host, checked there and carried to the kernel by value.
+ *   key(c) = bits(score) << 32 | (0xFFFFFFFF - id): the key of fpm_rank_topk / fpm_rank_select (NaN lowest,
+ *   -0 below +0) with the candidate's id in place of its column, so a tie goes to the lower id wherever
+ *   the candidates sit in the row.
+ * Precondition: every list strictly descending by key, ids distinct within a row -- what fpm_rank_select
+ * over a part of a gallery and an ascending table from local to global entry numbers give.  Not verified on
+ * the device; for other data the kernel still ends and stays inside its buffers, with unspecified outputs.
+ * Outputs (P, k), contiguous, 1 <= k <= min(L, 1024): the k candidates with the largest keys in descending
+ * key order: top_id, top_score (the same bits) and top_col (the candidate's column in the row).
+ * Merge by ranking: a candidate's slot is the number of greater keys, one binary search per list; no sort,
+ * no atomics, no scratch.  One workgroup of 1024 threads per row, the keys in LDS (8 bytes a column: 128 KB
+ * at the limit).  S <= FPM_TOPK_MERGE_SMAX, every list at most 1024 long, P <= 65535; everything else is
+ * refused before a launch. */
+#define FPM_TOPK_MERGE_SMAX 16
+int fpm_topk_merge(const float* score, const int* id, long ld, int P, const int* list_off, int S, int k, int* top_id,
+                   float* top_score, int* top_col, void* stream);
 
 /* ---- coarse 1:N score (the first pass of a shortlisted identification) ---------------------------
  * One scalar per (probe, enrolled entry) pair, one workgroup per pair, B pairs per launch:
