@@ -56,6 +56,7 @@ SIGNATURES = {
     "fpm_coarse_score_stream_ws_bytes": (L, [I, I, I]),
     "fpm_rows_fetch": (I, [P, L, P, P, I, I, I, P, L, P, P]),
     "fpm_rows_pack": (I, [P, L, P, I, I, P, P, P, L, P]),
+    "fpm_rows_move": (I, [P, P, L, P, P, P, I, I, P, P, L, P]),
     "fpm_edge_diff_padded":(I, [P, P, P, P, P, P, L, I, P, P]),
     "fpm_kron_gnn_layer_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fpm_kron_gnn_layer_fwd_ord": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),

@@ -64,6 +64,14 @@ Several GPUs (``sharded_gallery.ShardedGallery``): ``GalleryIndex.slice`` cuts a
 over a sharded gallery branches to ``identify_sharded`` there, which runs the stages above per shard and merges the
 shards' shortlists (``ops.topk_merge``); ``probe_batch(pad_to=...)`` lays a shard's part of a list out in the whole
 list's box, so that the parts' outputs are the one-index forward's.
+
+A mutable index (``GalleryIndex.reserve``, ``enroll*(capacity=...)``; ``Net.enroll_into`` and its keypoint and image
+forms; ``remove``, ``compact``): storage with capacity, of which the public fields are prefix views, re-made by the one
+``_commit``; appends write past ``used`` and commit at the end; ``remove`` sets tombstones and every query then runs
+over ``live`` (``_select_host`` defines "all entries"); ``compact`` moves the live rows to the front inside the same
+storage with ``ops.rows_move``, in ascending blocks, storage to storage where a block's destination ends before its
+source begins and through a staging buffer otherwise.  No mutation allocates or frees row storage, and no launch reads
+rows that it writes.
 """
 import contextlib
 import hashlib
@@ -79,6 +87,7 @@ from .model import _CachedSide
 
 FORMAT = 1                    # a saved "f32" index; the other layouts write FORMAT_LAYOUTS
 FORMAT_LAYOUTS = 2
+FORMAT_TOMBSTONES = 3         # any layout, with the table ``removed`` (an index saved with removed slots)
 SCORES = ("cls_prob", "cls_logits", "k_prob")
 LAYOUTS = ("f32", "f32+bf16", "bf16+host")
 ROW_BYTES = 4 * C.NODE_FEATURE_DIM
@@ -91,6 +100,57 @@ def _host_rows(shape, dev):
     """An uninitialised fp32 host tensor for an index on ``dev``: pinned when that is a GPU (the
     kernels read it through its device mapping), plain on a CPU "device"."""
     return torch.empty(shape, dtype=torch.float32, pin_memory=torch.device(dev).type == "cuda")
+
+
+# the rows of the device buffer ``GalleryIndex.compact`` stages blocks in whose destination meets their source
+COMPACT_STAGE_BYTES = 64 << 20
+COMPACT_HOST_ROWS = 4096      # rows per piece (12 MB) of a host-side move whose destination meets its source
+
+
+def _check_capacity(what, capacity, G, R, E=0):
+    """``capacity`` as given, (entries, keypoints[, edges]) -> (entries, rows, edges), each at least what is
+    held already (G entries, R rows, E edges); ``edges`` defaults to 6 per row."""
+    try:
+        cap = [int(v) for v in capacity]
+    except TypeError:
+        cap = []
+    if len(cap) not in (2, 3):
+        raise FpmError("%s: capacity must be (entries, keypoints) or (entries, keypoints, edges)" % what)
+    if len(cap) == 2:
+        cap.append(6 * cap[1])
+    if cap[0] < max(G, 1) or cap[1] < max(R, 1) or cap[2] < max(E, 1):
+        raise FpmError("%s: capacity %s below the %d entries, %d rows and %d edges to hold" % (what, tuple(cap), G, R, E))
+    if cap[0] > 2 ** 31 - 2:
+        raise FpmError("%s: entry numbers must fit int32" % what)
+    return tuple(cap)
+
+
+def _make_store(cap, layout, dev, has_P, has_subject):
+    """The buffers of an index with capacity ``cap`` = (entries, rows, edges): the device arrays (in
+    "bf16+host" the fp32 rows pinned on the host), and the host tables.  Rows and edges are uninitialised,
+    the small tables zero.  The public fields of the index are prefix views of these."""
+    ents, rows, edges = cap
+    D = C.NODE_FEATURE_DIM
+    new = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)
+    return dict(cap=tuple(cap),
+                y=_host_rows((rows, D), dev) if layout == "bf16+host" else new((rows, D), torch.float32),
+                y16=None if layout == "f32" else new((rows, D), torch.bfloat16),
+                P=new((rows, 2), torch.float32) if has_P else None,
+                src=new((edges,), torch.int32), dst=new((edges,), torch.int32), pseudo=new((edges, 2), torch.float32),
+                w=new((ents, C.GLOBAL_FEATURE_DIM), torch.float32),
+                row_off=torch.zeros(ents + 1, device=dev, dtype=torch.int64),
+                n=torch.zeros(ents, dtype=torch.int32), edge_off=torch.zeros(ents + 1, dtype=torch.int64),
+                row_off_host=torch.zeros(ents + 1, dtype=torch.int64),
+                subject=torch.zeros(ents, dtype=torch.int64) if has_subject else None)
+
+
+def _entry_ranges(off, ent):
+    """The numbers off[e] .. off[e + 1] of every entry e of ``ent``, concatenated -> (host int64 index, the
+    entries' new offsets)."""
+    cnt = off[ent + 1] - off[ent]
+    new = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
+    at = torch.arange(int(new[-1]), dtype=torch.int64)
+    return at + torch.repeat_interleave(off[ent] - new[:-1], cnt), new
 
 
 class GalleryIndex:
@@ -147,6 +207,11 @@ class GalleryIndex:
         self._sel = None            # the last selection's side-1 batch data (_selection)
         self.subject = None         # (G,) int64 host subject labels (set_subjects), or None
         self._groups = None         # the last selection's group tables (subject_groups)
+        self._store = None          # the buffers at capacity the fields are prefix views of (reserve), or None
+        self._removed = None        # host bool table over the slots (remove); None: nothing was ever removed
+        self._live = None           # the live slots, while the table above is unchanged
+        self.generation = 0         # bumped by every mutation (enroll_into, remove, compact)
+        self.last_compact = None    # the last compaction's launches by route (compact)
         G = self.G
         if (row_off.dtype != torch.int64 or self.row_off_host.numel() != G + 1 or self.edge_off.numel() != G + 1
                 or int(self.row_off_host[-1]) != y.shape[0] or int(self.edge_off[-1]) != src.numel()
@@ -167,51 +232,393 @@ class GalleryIndex:
     def nbytes(self):
         """Device bytes held: the rows (3 KB per keypoint in the "f32" layout, 4.5 KB in "f32+bf16",
         1.5 KB in "bf16+host"), plus edges and global features."""
-        ts = [self.row_off, self.src, self.dst, self.pseudo, self.w] + ([] if self.P is None else [self.P])
-        ts += ([] if self.layout == "bf16+host" else [self.y]) + ([] if self.y16 is None else [self.y16])
+        f = self._store or dict(row_off=self.row_off, src=self.src, dst=self.dst, pseudo=self.pseudo, w=self.w,
+                                P=self.P, y=self.y, y16=self.y16)
+        ts = [f[k] for k in ("row_off", "src", "dst", "pseudo", "w")] + ([] if f["P"] is None else [f["P"]])
+        ts += ([] if self.layout == "bf16+host" else [f["y"]]) + ([] if f["y16"] is None else [f["y16"]])
         if self._groups is not None:
             ts += [self._groups[1][k] for k in ("labels_d", "off_d", "pos_d")]
         return sum(t.numel() * t.element_size() for t in ts)
 
     def host_nbytes(self):
         """Host bytes held: the fp32 rows of the "bf16+host" layout (3 KB per keypoint), else 0."""
-        return self.y.numel() * self.y.element_size() if self.layout == "bf16+host" else 0
+        y = self.y if self._store is None else self._store["y"]
+        return y.numel() * y.element_size() if self.layout == "bf16+host" else 0
+
+    # ---- a mutable index: capacity, enrolment into it (Net.enroll_into), tombstones, compaction ----
+    @property
+    def used(self):
+        """(entries, rows, edges) the index holds; removed slots count until ``compact``."""
+        return self.G, int(self.y.shape[0]), int(self.src.numel())
+
+    @property
+    def capacity(self):
+        """(entries, rows, edges) the storage is sized for (``reserve``, ``enroll*(capacity=...)``), or None:
+        an index that holds exactly what it was enrolled with.  ``compact`` on such an index makes its own
+        tensors its storage: afterwards ``capacity`` is what the index held before, and the room the removed
+        entries left can be enrolled into."""
+        return None if self._store is None else self._store["cap"]
+
+    @property
+    def removed(self):
+        """(G,) host bool: the slots ``remove`` marked dead."""
+        if self._removed is None:
+            return torch.zeros(self.G, dtype=torch.bool)
+        return self._removed[:self.G]
+
+    @property
+    def tombstones(self):
+        """Whether some slot is marked dead."""
+        return self._removed is not None and int(self.live.numel()) != self.G
+
+    @property
+    def live(self):
+        """The live slots, ascending (host int64): what a query with ``select=None`` searches."""
+        if self._removed is None:
+            return torch.arange(self.G, dtype=torch.int64)
+        if self._live is None:
+            self._live = torch.nonzero(~self._removed[:self.G]).view(-1)
+        return self._live
+
+    def _check_live(self, sel, what):
+        """Refuse entry numbers ``sel`` (host int64, in range) that name a removed slot."""
+        if self.tombstones and bool(self._removed[sel].any()):
+            raise FpmError("%s: entry %d was removed from the index" % (what, int(sel[self._removed[sel]][0])))
+
+    def _touch(self):
+        """What every mutation ends with: the caches of the last selection go (the staging buffer of
+        ``fetch`` stays, without its key) and ``generation`` is bumped."""
+        self._sel = self._groups = self._live = None
+        if self._stage is not None:
+            self._stage = (torch.empty(0, dtype=torch.int64), self._stage[1], None, None, None)
+        self.generation += 1
+
+    def _commit(self, G, R, E, lo=0):
+        """The one writer of the public fields of an index with storage: they become the prefix views of
+        the storage for ``G`` entries, ``R`` rows and ``E`` edges, the device offsets of the slots from
+        ``lo`` on are uploaded from the host table, and the caches are dropped (``_touch``)."""
+        st = self._store
+        st["row_off"][lo:G + 1].copy_(st["row_off_host"][lo:G + 1])
+        self.y, self.y16 = st["y"][:R], None if st["y16"] is None else st["y16"][:R]
+        self.P = None if st["P"] is None else st["P"][:R]
+        self.src, self.dst, self.pseudo = st["src"][:E], st["dst"][:E], st["pseudo"][:E]
+        self.w, self.row_off = st["w"][:G], st["row_off"][:G + 1]
+        self.n, self.edge_off, self.row_off_host = st["n"][:G], st["edge_off"][:G + 1], st["row_off_host"][:G + 1]
+        self.subject = None if st["subject"] is None else st["subject"][:G]
+        self._touch()
+
+    @staticmethod
+    def _over(st, G, R, E, sc_mode, pack_gen, weights_id, layout):
+        """The index over the first G entries, R rows and E edges of the storage ``st`` (``_make_store``)."""
+        st["row_off"][:G + 1].copy_(st["row_off_host"][:G + 1])
+        sub = st["subject"]
+        idx = GalleryIndex(st["y"][:R], st["row_off"][:G + 1], st["n"][:G], st["src"][:E], st["dst"][:E],
+                           st["pseudo"][:E], st["edge_off"][:G + 1], st["w"][:G],
+                           None if st["P"] is None else st["P"][:R], sc_mode, pack_gen, weights_id,
+                           y16=None if st["y16"] is None else st["y16"][:R], layout=layout,
+                           subject=None if sub is None else sub[:G])
+        idx._store = st
+        idx._commit(G, R, E, lo=G)
+        idx.generation = 0
+        return idx
+
+    def reserve(self, entries, keypoints, edges=None):
+        """A new index holding this index's entries (and tombstones) in storage sized for ``entries`` slots,
+        ``keypoints`` rows and ``edges`` edges (default 6 per row: a planar triangulation has at most 6n - 12
+        directed edges, which covers ``stg="tri"`` graphs; host-dict graphs with more pass ``edges``), so
+        that ``Net.enroll_into`` can add entries without enrolling the gallery again.  In the "bf16+host"
+        layout the pinned host rows are allocated here, once, at capacity.  This index is untouched; to
+        grow a full index, reserve a bigger one: nothing is ever re-allocated under a live index."""
+        G, R, E = self.used
+        cap = _check_capacity("GalleryIndex.reserve", (entries, keypoints) if edges is None else
+                              (entries, keypoints, edges), G, R, E)
+        dev = self.device
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+            st = _make_store(cap, self.layout, dev, self.P is not None, self.subject is not None)
+            for key in ("y", "y16", "P"):
+                if st[key] is not None:
+                    st[key][:R].copy_(getattr(self, key))
+            for key in ("src", "dst", "pseudo"):
+                st[key][:E].copy_(getattr(self, key))
+            st["w"][:G].copy_(self.w)
+            st["n"][:G], st["edge_off"][:G + 1], st["row_off_host"][:G + 1] = self.n, self.edge_off, self.row_off_host
+            if self.subject is not None:
+                st["subject"][:G] = self.subject
+            idx = GalleryIndex._over(st, G, R, E, self.sc_mode, self._pack_gen, self.weights_id, self.layout)
+        if self._removed is not None:
+            idx._removed = torch.zeros(cap[0], dtype=torch.bool)
+            idx._removed[:G] = self._removed[:G]
+        return idx
+
+    def _adopt(self):
+        """The storage of an index that has none: its own tensors, full (capacity = used)."""
+        if self._store is None:
+            self._store = dict(cap=self.used, y=self.y, y16=self.y16, P=self.P, src=self.src, dst=self.dst,
+                               pseudo=self.pseudo, w=self.w, row_off=self.row_off, n=self.n, edge_off=self.edge_off,
+                               row_off_host=self.row_off_host, subject=self.subject)
+        return self._store
+
+    def _need_capacity(self, what):
+        if self._store is None:
+            raise FpmError("%s: the index has no capacity; make one with GalleryIndex.reserve(entries, keypoints) "
+                           "or enroll*(capacity=...)" % what)
+
+    def _begin_append(self, what, Gn, Rn, subjects, has_P):
+        """The refusals of an append of ``Gn`` entries of ``Rn`` rows, before anything is written -> (G, R, E)
+        now: the slot, row and edge where the new entries' data goes, past ``used``."""
+        self._need_capacity(what)
+        if (subjects is None) != (self.subject is None):
+            raise FpmError("%s: the index %s, the call %s" % (
+                what, "has subject labels" if subjects is None else "has no subject labels",
+                "gives none (subjects=...)" if subjects is None else "gives subjects"))
+        if has_P != (self.P is not None):
+            raise FpmError("%s: the index %s keypoints P, the new graphs %s" % (
+                what, "keeps" if not has_P else "keeps no", "carry none" if not has_P else "carry them"))
+        G, R, E = self.used
+        cap = self._store["cap"]
+        if G + Gn > cap[0] or R + Rn > cap[1]:
+            raise FpmError("%s: %d entries and %d rows more pass the index's capacity (%d of %d entries, %d of %d rows "
+                           "used); reserve a bigger index (GalleryIndex.reserve)" % (what, Gn, Rn, G, cap[0], R, cap[1]))
+        return G, R, E
+
+    def _finish_append(self, what, at, n, w, P, src, dst, pseudo, cnt, subjects):
+        """The end of an append whose rows are written (past ``used``, from ``at`` = ``_begin_append``'s):
+        the new entries' small arrays go into the storage's tail -- n host int32, w (Gn, 512), P (Rn, 2) or
+        None, the edges with graph-local ids and their host counts per entry -- and the index is committed.
+        Until the commit no field has changed: an error before it leaves the index as it was."""
+        G, R, E = at
+        st = self._store
+        n = torch.as_tensor(n, dtype=torch.int32).view(-1).cpu()
+        cnt = torch.as_tensor(cnt, dtype=torch.int64).view(-1).cpu()
+        Gn, Rn, En = int(n.numel()), int(n.sum()), int(src.numel())
+        if int(cnt.numel()) != Gn or int(cnt.sum()) != En:
+            raise FpmError("%s: %d edges, their counts per entry sum to %d" % (what, En, int(cnt.sum())))
+        _edge_room(what, En, st["cap"][2] - E)
+        st["w"][G:G + Gn].copy_(w)
+        if P is not None:
+            st["P"][R:R + Rn].copy_(P)
+        for key, t in (("src", src), ("dst", dst), ("pseudo", pseudo)):
+            st[key][E:E + En].copy_(t)
+        if self.layout == "bf16+host" and self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()   # the host rows are complete before they are read
+        st["n"][G:G + Gn] = n
+        st["row_off_host"][G + 1:G + Gn + 1] = R + n.long().cumsum(0)
+        st["edge_off"][G + 1:G + Gn + 1] = E + cnt.cumsum(0)
+        if subjects is not None:
+            st["subject"][G:G + Gn] = subjects
+        self._commit(G + Gn, R + Rn, E + En, lo=G)
+        return torch.arange(G, G + Gn, dtype=torch.int64)
+
+    def remove(self, entries):
+        """Mark the entries ``entries`` dead (tombstones in the host table ``removed``).  Entry numbers stay
+        as they are and ``G`` still counts slots; no row is touched.  Every query then searches ``live``:
+        ``select=None`` means the live entries, and a ``select``, ``probe_select``, pair, ``slice`` or
+        ``fetch`` that names a removed slot is refused.  ``compact`` squeezes the dead slots out.  Refused:
+        an entry outside [0, G), named twice or removed already, and removing the last live entry."""
+        ent = torch.as_tensor(entries, dtype=torch.int64).view(-1).cpu()
+        if ent.numel() == 0 or int(ent.min()) < 0 or int(ent.max()) >= self.G:
+            raise FpmError("GalleryIndex.remove: entries must name entries in [0, %d)" % self.G)
+        if int(torch.unique(ent).numel()) != int(ent.numel()):
+            raise FpmError("GalleryIndex.remove: an entry is named twice")
+        if bool(self.removed[ent].any()):
+            raise FpmError("GalleryIndex.remove: entry %d was removed already" % int(ent[self.removed[ent]][0]))
+        if int(ent.numel()) >= int(self.live.numel()):
+            raise FpmError("GalleryIndex.remove: this would remove the last live entry of the index")
+        if self._removed is None:
+            self._removed = torch.zeros(self.G if self._store is None else self._store["cap"][0], dtype=torch.bool)
+        self._removed[ent] = True
+        self._touch()
+
+    def compact(self, stage_rows=None):
+        """Squeeze the removed slots out, inside the same storage -> ``new_of_old`` (G_old,) host int64: the
+        new number of every old entry, -1 for a removed one.  Afterwards every field equals
+        ``slice(live)`` of the index before; capacity is unchanged and nothing is allocated but the stage.
+        An index without capacity keeps its own tensors as its storage from here on (``capacity``: what it
+        held before; the freed room can be enrolled into; ``slice(live)`` instead makes a tight copy).
+
+        Unlike an append, a compaction is not atomic: rows are overwritten as it goes and the tables change
+        at the end, so an error midway (none is expected once the first launch is out: every refusal and
+        the one allocation, the stage, come before it) would leave rows that the tables no longer describe.
+
+        The rows (97 % of the bytes) move by ``ops.rows_move``, in blocks of consecutive live entries of at
+        most ``stage_rows`` rows (default COMPACT_STAGE_BYTES worth, never less than the largest entry; a
+        given value below the largest moved entry is refused).  Live entries only move towards the front
+        and blocks ascend, so a block's destination covers only rows that are dead or were read already.  A
+        block whose destination ends at or before its source begins moves in one launch, storage to
+        storage; any other block in two on one stream, storage to stage, stage to storage (the stage: one
+        device buffer reused by every such block).  No launch reads rows that it writes; ``ops.rows_move``
+        checks that on the host each time.  ``last_compact`` counts the blocks by route.  The small arrays
+        (P, edges, w, offsets, the host tables; 3 % of the bytes) are gathered out of place with torch
+        indexing and copied back over the prefix.  The host fp32 rows of "bf16+host" are moved by host
+        code after a device synchronise (kernels read that memory through its mapping): ascending, one
+        copy per run of adjacent live entries, a run that lands on rows it still occupies in pieces of
+        COMPACT_HOST_ROWS rows through a temporary."""
+        G, R, E = self.used
+        live = self.live
+        L = int(live.numel())
+        new_of_old = torch.full((G,), -1, dtype=torch.int64)
+        new_of_old[live] = torch.arange(L, dtype=torch.int64)
+        self.last_compact = dict(direct=0, staged=0, launches=0, rows=0)
+        if L == G:
+            return new_of_old
+        ro, eo = self.row_off_host, self.edge_off
+        cnt, src = ro[live + 1] - ro[live], ro[live]
+        new_ro = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
+        dst = new_ro[:-1]
+        first = int(torch.nonzero(live != torch.arange(L)).view(-1)[0]) if L and int(live[-1]) != L - 1 else L
+        big = int(cnt[first:].max()) if first < L else 0
+        if stage_rows is None:
+            stage_rows = max(COMPACT_STAGE_BYTES // ROW_BYTES, big)
+        stage_rows = int(stage_rows)
+        if stage_rows < max(big, 1):
+            raise FpmError("GalleryIndex.compact: stage_rows = %d below the largest entry to move (%d rows)"
+                           % (stage_rows, big))
+        # blocks [a, b) of the moved live entries: at most stage_rows rows and 65535 segments each
+        blocks, a, rows = [], first, 0
+        for i in range(first, L):
+            k = int(cnt[i])
+            if i > a and (rows + k > stage_rows or i - a >= 65535):
+                blocks.append((a, i))
+                a, rows = i, 0
+            rows += k
+        if a < L:
+            blocks.append((a, L))
+        st = self._adopt()
+        dev = self.device
+        host_rows = self.layout == "bf16+host"
+        y32, y16 = None if host_rows else st["y"], st["y16"]
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+            if blocks:
+                stg = torch.cat([dst[a:b] - dst[a] for a, b in blocks])          # offsets into the stage
+                src_h, dst_h, cnt_h = src[first:].contiguous(), dst[first:].contiguous(), cnt[first:].contiguous()
+                src_d, dst_d, cnt_d, stg_d = src_h.to(dev), dst_h.to(dev), cnt_h.to(dev), stg.to(dev)
+            # the stage, before the first launch: once rows have moved nothing may fail
+            s32 = s16 = None
+            if any(int(new_ro[b]) > int(src[a]) for a, b in blocks):
+                if y32 is not None:
+                    s32 = torch.empty(stage_rows, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
+                if y16 is not None:
+                    s16 = torch.empty(stage_rows, C.NODE_FEATURE_DIM, device=dev, dtype=torch.bfloat16)
+            for a, b in blocks:
+                u, v = a - first, b - first
+                host = dict(cnt_host=cnt_h[u:v])
+                tabs = (src_d[u:v], dst_d[u:v], stg_d[u:v], src_h[u:v], dst_h[u:v], stg[u:v])
+                self.last_compact["rows"] += int(cnt_h[u:v].sum())
+                if int(new_ro[b]) <= int(src[a]):
+                    ops.rows_move(tabs[0], tabs[1], cnt_d[u:v], src32=y32, dst32=y32, src16=y16, dst16=y16,
+                                  src_off_host=tabs[3], dst_off_host=tabs[4], **host)
+                    self.last_compact["direct"] += 1
+                    self.last_compact["launches"] += 1
+                    continue
+                ops.rows_move(tabs[0], tabs[2], cnt_d[u:v], src32=y32, dst32=s32, src16=y16, dst16=s16,
+                              src_off_host=tabs[3], dst_off_host=tabs[5], **host)
+                ops.rows_move(tabs[2], tabs[1], cnt_d[u:v], src32=s32, dst32=y32, src16=s16, dst16=y16,
+                              src_off_host=tabs[5], dst_off_host=tabs[4], **host)
+                self.last_compact["staged"] += 1
+                self.last_compact["launches"] += 2
+            if host_rows:
+                if dev.type == "cuda":
+                    torch.cuda.synchronize(dev)              # no kernel still reads the host rows through the mapping
+                y = st["y"]
+                # runs of adjacent live entries: each is one range of rows before and after
+                head = torch.ones(L - first, dtype=torch.bool)
+                head[1:] = src[first + 1:] != src[first:-1] + cnt[first:-1]
+                at = (torch.nonzero(head).view(-1) + first).tolist() + [L]
+                for i, j in zip(at[:-1], at[1:]):
+                    s, d, k = int(src[i]), int(dst[i]), int(new_ro[j] - new_ro[i])
+                    step = max(s - d, COMPACT_HOST_ROWS)     # a piece no longer than the shift lands on rows already read
+                    for o in range(0, k, step):
+                        part = y[s + o:s + min(k, o + step)]
+                        y[d + o:d + min(k, o + step)].copy_(part.clone() if step > s - d else part)
+            # the small arrays: gathered out of place (the right sides are whole before anything is written)
+            rows_at, _ = _entry_ranges(ro, live)
+            edges_at, new_eo = _entry_ranges(eo, live)
+            Rn, En = int(new_ro[-1]), int(new_eo[-1])
+            rows_d, edges_d, live_d = rows_at.to(dev), edges_at.to(dev), live.to(dev)
+            if st["P"] is not None:
+                st["P"][:Rn] = st["P"][rows_d]
+            for key in ("src", "dst", "pseudo"):
+                st[key][:En] = st[key][edges_d]
+            st["w"][:L] = st["w"][live_d]
+            st["n"][:L] = st["n"][live]
+            if st["subject"] is not None:
+                st["subject"][:L] = st["subject"][live]
+            st["row_off_host"][:L + 1], st["edge_off"][:L + 1] = new_ro, new_eo
+            self._removed[:] = False
+            self._commit(L, Rn, En)
+        return new_of_old
 
     def save(self, path):
         """``torch.save`` of a dict of tensors and scalars (no pickled code objects).  An "f32" index
-        writes format 1, as ever; the other layouts write format 2, with ``layout`` and ``y16``."""
-        d = dict(format=FORMAT, y=self.y.cpu(), row_off=self.row_off_host, n=self.n, src=self.src.cpu(),
-                 dst=self.dst.cpu(), pseudo=self.pseudo.cpu(), edge_off=self.edge_off, w=self.w.cpu(),
+        writes format 1, as ever; the other layouts write format 2, with ``layout`` and ``y16``.  Of an
+        index with capacity the used part is written; one with removed slots writes format 3, which adds
+        the table ``removed``."""
+        # a field of an index with storage is a view: a host view is copied, so that only its part is written
+        host = (lambda t: t.cpu()) if self._store is None else (lambda t: t.cpu() if t.is_cuda else t.clone())
+        d = dict(format=FORMAT, y=host(self.y), row_off=host(self.row_off_host), n=host(self.n), src=host(self.src),
+                 dst=host(self.dst), pseudo=host(self.pseudo), edge_off=host(self.edge_off), w=host(self.w),
                  sc_mode=self.sc_mode, pack_gen=self._pack_gen, weights_id=self.weights_id)
         if self.P is not None:
-            d["P"] = self.P.cpu()
+            d["P"] = host(self.P)
         if self.layout != "f32":
-            d.update(format=FORMAT_LAYOUTS, layout=self.layout, y16=self.y16.cpu())
+            d.update(format=FORMAT_LAYOUTS, layout=self.layout, y16=host(self.y16))
         if self.subject is not None:
-            d["subject"] = self.subject
+            d["subject"] = host(self.subject)
+        if self.tombstones:
+            d.update(format=FORMAT_TOMBSTONES, layout=self.layout, removed=self.removed.clone())
         torch.save(d, path)
 
     @staticmethod
-    def load(path, device):
+    def load(path, device, capacity=None):
+        """The index ``save`` wrote, on ``device``.  ``capacity``: (entries, keypoints[, edges]) -- the index
+        is restored into storage of that size (as ``reserve`` makes it), without a second copy of it."""
         d = torch.load(path, map_location="cpu", weights_only=True)
-        if d.get("format") not in (FORMAT, FORMAT_LAYOUTS):
-            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d or %d"
-                           % (path, FORMAT, FORMAT_LAYOUTS))
-        mv = lambda k: d[k].to(device)
-        layout = d["layout"] if d["format"] == FORMAT_LAYOUTS else "f32"
-        if layout == "bf16+host":
-            y = _host_rows(d["y"].shape, device).copy_(d["y"])
+        if d.get("format") not in (FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES) or (
+                d["format"] == FORMAT_TOMBSTONES and not ("removed" in d and "layout" in d)):
+            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d, %d or %d"
+                           % (path, FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES))
+        layout = d["layout"] if d["format"] != FORMAT else "f32"
+        if capacity is None:
+            mv = lambda k: d[k].to(device)
+            if layout == "bf16+host":
+                y = _host_rows(d["y"].shape, device).copy_(d["y"])
+            else:
+                y = mv("y")
+            idx = GalleryIndex(y, mv("row_off"), d["n"], mv("src"), mv("dst"), mv("pseudo"), d["edge_off"], mv("w"),
+                               mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"],
+                               y16=mv("y16") if layout != "f32" else None, layout=layout, subject=d.get("subject"))
         else:
-            y = mv("y")
-        return GalleryIndex(y, mv("row_off"), d["n"], mv("src"), mv("dst"), mv("pseudo"), d["edge_off"], mv("w"),
-                            mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"],
-                            y16=mv("y16") if layout != "f32" else None, layout=layout, subject=d.get("subject"))
+            G, R, E = int(d["n"].numel()), int(d["y"].shape[0]), int(d["src"].numel())
+            cap = _check_capacity("GalleryIndex.load", capacity, G, R, E)
+            dev = torch.device(device)
+            with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+                st = _make_store(cap, layout, dev, "P" in d, "subject" in d)
+                for key, k in (("y", R), ("y16", R), ("P", R), ("src", E), ("dst", E), ("pseudo", E), ("w", G),
+                               ("n", G), ("edge_off", G + 1), ("subject", G)):
+                    if st[key] is not None:
+                        st[key][:k].copy_(d[key])
+                st["row_off_host"][:G + 1] = d["row_off"]
+                idx = GalleryIndex._over(st, G, R, E, d["sc_mode"], d["pack_gen"], d["weights_id"], layout)
+        if "removed" in d:
+            idx._removed = torch.zeros(idx.G if capacity is None else idx.capacity[0], dtype=torch.bool)
+            idx._removed[:idx.G] = d["removed"]
+        return idx
 
     def set_subjects(self, labels):
         """Label (or relabel) the entries: ``labels`` (G,) integers >= 0, the subject of each entry (the
-        impressions of one finger share a label).  Kept as a host int64 tensor (``subject``); the
-        cached group tables are dropped.  None removes the labels."""
-        self.subject = None if labels is None else _check_subjects("set_subjects", labels, self.G)
+        impressions of one finger share a label; removed slots are labelled too).  Kept as a host int64
+        tensor (``subject``); the cached group tables are dropped.  None removes the labels."""
+        lab = None if labels is None else _check_subjects("set_subjects", labels, self.G)
+        if self._store is not None:
+            st = self._store
+            if lab is None:
+                st["subject"] = None
+            else:
+                if st["subject"] is None:
+                    st["subject"] = torch.zeros(st["cap"][0], dtype=torch.int64)
+                st["subject"][:self.G] = lab
+                lab = st["subject"][:self.G]
+        self.subject = lab
         self._groups = None
 
     def subject_groups(self, select=None):
@@ -252,6 +659,7 @@ class GalleryIndex:
         sel = torch.as_tensor(sel, dtype=torch.int64).view(-1).cpu()
         if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= self.G:
             raise FpmError("GalleryIndex.fetch: sel must name entries in [0, %d)" % self.G)
+        self._check_live(sel, "GalleryIndex.fetch")
         if self._stage is not None and torch.equal(self._stage[0], sel):
             return self._stage[2:]
         ng = self.n[sel].long()
@@ -288,18 +696,11 @@ class GalleryIndex:
             raise FpmError("GalleryIndex.slice: entries must be a non-empty 1-D host int64 tensor")
         if int(ent[0]) < 0 or int(ent[-1]) >= self.G or bool((ent[1:] <= ent[:-1]).any()):
             raise FpmError("GalleryIndex.slice: entries must ascend without repeats inside [0, %d)" % self.G)
+        self._check_live(ent, "GalleryIndex.slice")
         dev = self.device if device is None else torch.device(device)
         src_dev = self.device
-
-        def ranges(off):
-            # the numbers off[e] .. off[e + 1] of every entry e, concatenated -> (host int64 index, new offsets)
-            cnt = off[ent + 1] - off[ent]
-            new = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
-            at = torch.arange(int(new[-1]), dtype=torch.int64)
-            return at + torch.repeat_interleave(off[ent] - new[:-1], cnt), new
-
-        rows, row_off = ranges(self.row_off_host)
-        edges, edge_off = ranges(self.edge_off)
+        rows, row_off = _entry_ranges(self.row_off_host, ent)
+        edges, edge_off = _entry_ranges(self.edge_off, ent)
         rows_d, edges_d, ent_d = rows.to(src_dev), edges.to(src_dev), ent.to(src_dev)
         take = lambda t, at: t[at].to(dev)
         if self.layout == "bf16+host":
@@ -432,14 +833,93 @@ def spline_weights_id(net):
     return net._sc_weights_id[1]
 
 
-def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None):
+def _alloc_rows(layout, dev, rows):
+    """The row buffers of a new index of exactly ``rows`` rows -> (y fp32 device or None, y16 or None, the
+    pinned host fp32 rows of "bf16+host" or None): what the enrolment loops write into."""
+    D = C.NODE_FEATURE_DIM
+    return (None if layout == "bf16+host" else torch.empty(rows, D, device=dev, dtype=torch.float32),
+            None if layout == "f32" else torch.empty(rows, D, device=dev, dtype=torch.bfloat16),
+            _host_rows((rows, D), dev) if layout == "bf16+host" else None)
+
+
+def _store_rows(index):
+    """The same three of an index with capacity: its storage, which the loops write past ``used``."""
+    st, host = index._store, index.layout == "bf16+host"
+    return None if host else st["y"], st["y16"], st["y"] if host else None
+
+
+def _edge_room(what, seen, room):
+    """Refuse an enrolment into an index whose edges (``seen`` so far) pass the ``room`` left (None: no bound)."""
+    if room is not None and seen > room:
+        raise FpmError("%s: the graphs' edges pass the index's capacity (%d so far, room for %d); reserve a bigger "
+                       "index (GalleryIndex.reserve(..., edges=...))" % (what, seen, room))
+
+
+def _enroll_dicts(net, what, graphs, dev, sc_mode, batch, rows, r0, room=None):
+    """The enrolment loop of ``enroll`` and ``enroll_into``: the two SplineConv layers over the graph dicts in
+    sub-batches of ``batch``, each sub-batch's ragged rows written from row ``r0`` on into ``rows``
+    (``_alloc_rows`` / ``_store_rows``) -> the edges (graph-local src, dst, pseudo on the device, host counts
+    per graph).  ``room``: the edges the index has room for (None: a new index)."""
+    y, y16, y_host = rows
+    wp = net.packed(dev)
+    srcs, dsts, pss, cnts, seen = [], [], [], [], 0
+    for g0 in range(0, len(graphs), max(1, int(batch))):
+        sub = graphs[g0:g0 + max(1, int(batch))]
+        n, nmax, x0, src, dst, ps, cnt = _graph_side(sub, dev)
+        Bs, nn_, E = len(sub), len(sub) * nmax, int(src.numel())
+        seen += E
+        _edge_room(what, seen, room)
+        nv = n.to(dev)
+        plan = ops.spline_plan(src, dst, ps, nn_, nmax, int(cnt.max()))
+        yb = net._spline_layers(wp, sc_mode == "f32", x0, plan, E, nn_, nmax, nv)
+        # padded -> ragged rows, edges back to graph-local ids (off the hot path: torch indexing)
+        keep = (torch.arange(nmax, device=dev)[None, :] < nv.view(-1, 1)).reshape(-1)
+        yr = yb[keep]
+        r1 = r0 + int(yr.shape[0])
+        if y16 is not None:
+            ops.cast_bf16(yr, out=y16[r0:r1])
+        if y_host is not None:
+            y_host[r0:r1].copy_(yr, non_blocking=True)
+        else:
+            y[r0:r1].copy_(yr)
+        r0 = r1
+        shift = torch.repeat_interleave(torch.arange(Bs, device=dev) * nmax, torch.from_numpy(cnt).to(dev),
+                                        output_size=E).to(torch.int32)
+        srcs.append(src - shift)
+        dsts.append(dst - shift)
+        pss.append(ps)
+        cnts.append(torch.from_numpy(cnt))
+    return torch.cat(srcs), torch.cat(dsts), torch.cat(pss), torch.cat(cnts)
+
+
+def _dict_tables(graphs, dev):
+    """The per-graph fields of graph dicts -> (n host int32, w (G, 512) device, P (sum n, 2) device or None)."""
+    n_all = torch.tensor([int(g["n"]) for g in graphs], dtype=torch.int32)
+    w = torch.from_numpy(np.stack([np.asarray(g["w"], dtype=np.float32) for g in graphs])).to(dev)
+    P = None
+    if all("P" in g for g in graphs):
+        P = torch.from_numpy(np.concatenate([np.asarray(g["P"], dtype=np.float32).reshape(-1, 2) for g in graphs])).to(dev)
+    return n_all, w, P
+
+
+def _empty_index(net, what, capacity, G, R, layout, dev, sc_mode, has_P, has_subject):
+    """An index of no entries over storage of ``capacity`` (checked against the G entries and R rows to come):
+    ``enroll*(capacity=...)`` is an enrolment into it."""
+    cap = _check_capacity(what, capacity, G, R)
+    with torch.cuda.device(dev):
+        st = _make_store(cap, layout, dev, has_P, has_subject)
+        return GalleryIndex._over(st, 0, 0, 0, sc_mode, net._pack_gen, spline_weights_id(net), layout)
+
+
+def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None, capacity=None):
     """``Net.enroll``: the two SplineConv layers over ``graphs`` (dicts as ``fpm.synth.make_graph``
     returns: n, x, w, edge_index, pseudo, optionally P) in sub-batches of ``batch`` graphs -> GalleryIndex.
     ``layout`` (LAYOUTS): where the rows are kept.  The bf16 copy is rounded per sub-batch on the device
     (``ops.cast_bf16``: the coarse kernels' own rounding); for "bf16+host" each sub-batch's fp32 rows go
     straight to the pinned host tensor, so the device holds the bf16 rows plus one sub-batch at most.
     ``subjects``: one integer label >= 0 per graph (``GalleryIndex.subject``), checked before any GPU work;
-    every other field of the index is the same with or without it."""
+    every other field of the index is the same with or without it.  ``capacity``: (entries, keypoints[,
+    edges]), the storage to enrol into (``GalleryIndex.reserve``'s sizes), for an index that will grow."""
     sc_mode = _check_enroll(net, "enroll", layout, sc_mode)
     dev = torch.device(device)
     graphs = list(graphs)
@@ -447,51 +927,48 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
         raise FpmError("enroll: empty gallery")
     if subjects is not None:
         subjects = _check_subjects("enroll", subjects, len(graphs))
-    wp = net.packed(dev)
-    ys, srcs, dsts, pss, cnts = [], [], [], [], []
     total = sum(int(g["n"]) for g in graphs)
-    y16 = y_host = None
-    if layout != "f32":
-        y16 = torch.empty(total, C.NODE_FEATURE_DIM, device=dev, dtype=torch.bfloat16)
-    if layout == "bf16+host":
-        y_host = _host_rows((total, C.NODE_FEATURE_DIM), dev)
-    r0 = 0
+    if capacity is not None:
+        index = _empty_index(net, "enroll", capacity, len(graphs), total, layout, dev, sc_mode,
+                             all("P" in g for g in graphs), subjects is not None)
+        enroll_into(net, index, graphs, batch=batch, subjects=subjects, what="enroll")
+        index.generation, index._pack_gen = 0, net._pack_gen    # a new index: as the constructor call below records it
+        return index
     with torch.cuda.device(dev):
-        for g0 in range(0, len(graphs), max(1, int(batch))):
-            sub = graphs[g0:g0 + max(1, int(batch))]
-            n, nmax, x0, src, dst, ps, cnt = _graph_side(sub, dev)
-            Bs, nn_, E = len(sub), len(sub) * nmax, int(src.numel())
-            nv = n.to(dev)
-            plan = ops.spline_plan(src, dst, ps, nn_, nmax, int(cnt.max()))
-            y = net._spline_layers(wp, sc_mode == "f32", x0, plan, E, nn_, nmax, nv)
-            # padded -> ragged rows, edges back to graph-local ids (off the hot path: torch indexing)
-            keep = (torch.arange(nmax, device=dev)[None, :] < nv.view(-1, 1)).reshape(-1)
-            yr = y[keep]
-            if y16 is not None:
-                ops.cast_bf16(yr, out=y16[r0:r0 + yr.shape[0]])
-            if y_host is not None:
-                y_host[r0:r0 + yr.shape[0]].copy_(yr, non_blocking=True)
-            else:
-                ys.append(yr)
-            r0 += int(yr.shape[0])
-            shift = torch.repeat_interleave(torch.arange(Bs, device=dev) * nmax, torch.from_numpy(cnt).to(dev),
-                                            output_size=E).to(torch.int32)
-            srcs.append(src - shift)
-            dsts.append(dst - shift)
-            pss.append(ps)
-            cnts.append(cnt)
-    n_all = torch.tensor([int(g["n"]) for g in graphs], dtype=torch.int32)
+        y, y16, y_host = rows = _alloc_rows(layout, dev, total)
+        src, dst, ps, cnt = _enroll_dicts(net, "enroll", graphs, dev, sc_mode, batch, rows, 0)
+    n_all, w, P = _dict_tables(graphs, dev)
     row_off = torch.cat([torch.zeros(1, dtype=torch.int64), n_all.long().cumsum(0)])
-    edge_off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.from_numpy(np.concatenate(cnts)).cumsum(0)])
-    w = torch.from_numpy(np.stack([np.asarray(g["w"], dtype=np.float32) for g in graphs])).to(dev)
-    P = None
-    if all("P" in g for g in graphs):
-        P = torch.from_numpy(np.concatenate([np.asarray(g["P"], dtype=np.float32).reshape(-1, 2) for g in graphs])).to(dev)
+    edge_off = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
     if y_host is not None:
         torch.cuda.current_stream(dev).synchronize()       # the host rows are complete before they are read
-    return GalleryIndex(torch.cat(ys) if y_host is None else y_host, row_off.to(dev), n_all, torch.cat(srcs),
-                        torch.cat(dsts), torch.cat(pss), edge_off, w, P, sc_mode, net._pack_gen,
-                        spline_weights_id(net), y16=y16, layout=layout, subject=subjects)
+    return GalleryIndex(y if y_host is None else y_host, row_off.to(dev), n_all, src, dst, ps, edge_off, w, P, sc_mode,
+                        net._pack_gen, spline_weights_id(net), y16=y16, layout=layout, subject=subjects)
+
+
+def _check_into(net, index, what):
+    """The refusals of an enrolment into ``index`` that need no graphs."""
+    if not isinstance(index, GalleryIndex):
+        raise FpmError("%s: index must be a GalleryIndex (Net.enroll)" % what)
+    index._need_capacity(what)
+    _check_query(net, index, what)
+
+
+def enroll_into(net, index, graphs, batch=256, subjects=None, what="enroll_into"):
+    """``Net.enroll_into``: see there."""
+    _check_into(net, index, what)
+    graphs = list(graphs)
+    if not graphs:
+        raise FpmError("%s: no graphs" % what)
+    if subjects is not None:
+        subjects = _check_subjects(what, subjects, len(graphs))
+    dev = index.device
+    n_all, w, P = _dict_tables(graphs, dev)
+    at = index._begin_append(what, len(graphs), int(n_all.sum()), subjects, P is not None)
+    with torch.cuda.device(dev):
+        edges = _enroll_dicts(net, what, graphs, dev, index.sc_mode, batch, _store_rows(index), at[1],
+                              index.capacity[2] - at[2])
+        return index._finish_append(what, at, n_all, w, P, *edges, subjects)
 
 
 def _check_enroll(net, what, layout, sc_mode):
@@ -546,29 +1023,36 @@ def _device_of(device, *ts):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subjects=None):
-    """The enrolment loop of ``enroll_keypoints`` / ``enroll_images`` -> GalleryIndex.  ``feats(g0, g1, m)``:
+def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, subjects=None, capacity=None,
+                   into=None):
+    """The enrolment loop of ``enroll_keypoints`` / ``enroll_images`` and their ``_into`` forms -> a new
+    GalleryIndex, or (``into``: an index with capacity, whose ``sc_mode`` and layout are taken) the new
+    entries' numbers.  ``feats(g0, g1, m)``:
     the features of graphs [g0, g1) on the device, (x (g1 - g0, >= m, 768) fp32, w (g1 - g0, 512) fp32).  Per
     sub-batch: trim to its own largest count m (the shapes ``enroll`` runs at), the graphs on the device
     (``graphs.build_graph_batch``), the two SplineConv layers as ``enroll`` calls them, and one
-    ``ops.rows_pack`` from the padded output into the index's rows, allocated once before the loop."""
+    ``ops.rows_pack`` from the padded output into the index's rows, allocated once before the loop (a new
+    index) or reserved (``into``: the rows past ``used``; the edge count is known only per sub-batch, so the
+    index changes at the end, in ``_finish_append``)."""
     from . import graphs
     G, nmax, D = int(n_h.numel()), int(P.shape[1]), C.NODE_FEATURE_DIM
     step = max(1, int(batch))
-    wp = net.packed(dev)
     row_off_h = torch.cat([torch.zeros(1, dtype=torch.int64), n_h.cumsum(0)])
     total = int(row_off_h[-1])
-    srcs, dsts, pss, cnts = [], [], [], []
+    if into is None and capacity is not None:
+        into = _empty_index(net, what, capacity, G, total, layout, dev, sc_mode, True, subjects is not None)
+    base, room = 0, None
+    if into is not None:
+        at = into._begin_append(what, G, total, subjects, True)
+        sc_mode, layout, base, room = into.sc_mode, into.layout, at[1], into.capacity[2] - at[2]
+    wp = net.packed(dev)
+    srcs, dsts, pss, cnts, seen = [], [], [], [], 0
     with torch.cuda.device(dev):
         row_off = row_off_h.to(dev)
         n_d = n_h.to(torch.int32).to(dev)
-        y = y16 = y_host = stage = None
-        if layout != "bf16+host":
-            y = torch.empty(total, D, device=dev, dtype=torch.float32)
-        if layout != "f32":
-            y16 = torch.empty(total, D, device=dev, dtype=torch.bfloat16)
-        if layout == "bf16+host":
-            y_host = _host_rows((total, D), dev)
+        y, y16, y_host = _alloc_rows(layout, dev, total) if into is None else _store_rows(into)
+        stage = None
+        if y_host is not None:
             # one sub-batch of fp32 rows on the device, reused: the copies to the host are ordered on the stream
             stage = torch.empty(max(int(row_off_h[min(G, g0 + step)] - row_off_h[g0]) for g0 in range(0, G, step)), D,
                                 device=dev, dtype=torch.float32)
@@ -584,15 +1068,17 @@ def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subject
             gb = graphs.build_graph_batch(P[g0:g1, :m].to(dev).contiguous(), nv, stg=stg)
             cnt = gb.edge_off_host[1:] - gb.edge_off_host[:-1]
             nn_, E = Bs * m, int(gb.src.numel())
+            seen += E
+            _edge_room(what, seen, room)
             plan = ops.spline_plan(gb.src, gb.dst, gb.pseudo, nn_, m, int(cnt.max()))
             yb = net._spline_layers(wp, sc_mode == "f32", x0, plan, E, nn_, m, nv)
             # padded -> ragged rows (and their bf16 copy) in one pass, into their place in the index
             r0, r1 = int(row_off_h[g0]), int(row_off_h[g1])
-            ops.rows_pack(yb, nv, m, row_off[g0:g1 + 1] - r0, out32=stage if y is None else y[r0:r1],
-                          out16=None if y16 is None else y16[r0:r1], n_host=nsub,
+            ops.rows_pack(yb, nv, m, row_off[g0:g1 + 1] - r0, out32=stage if y is None else y[base + r0:base + r1],
+                          out16=None if y16 is None else y16[base + r0:base + r1], n_host=nsub,
                           out_off_host=row_off_h[g0:g1 + 1] - r0)
             if y_host is not None:
-                y_host[r0:r1].copy_(stage[:r1 - r0], non_blocking=True)
+                y_host[base + r0:base + r1].copy_(stage[:r1 - r0], non_blocking=True)
             srcs.append(gb.src % m)                          # edges back to graph-local ids
             dsts.append(gb.dst % m)
             pss.append(gb.pseudo)
@@ -600,6 +1086,13 @@ def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subject
         Pk = P if P.device == dev else P.cpu()
         keep = torch.arange(nmax, device=Pk.device)[None, :] < n_h.to(Pk.device).view(-1, 1)
         Pr = Pk[keep].to(dev)
+        if into is not None:
+            new = into._finish_append(what, at, n_h.to(torch.int32), w_all, Pr, torch.cat(srcs), torch.cat(dsts),
+                                      torch.cat(pss), torch.cat(cnts), subjects)
+            if capacity is None:
+                return new
+            into.generation, into._pack_gen = 0, net._pack_gen   # a new index: as the constructor call below records it
+            return into
         edge_off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cat(cnts).cumsum(0)])
         if y_host is not None:
             torch.cuda.current_stream(dev).synchronize()   # the host rows are complete before they are read
@@ -608,7 +1101,23 @@ def _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subject
                             spline_weights_id(net), y16=y16, layout=layout, subject=subjects)
 
 
-def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri", subjects=None):
+def _keypoint_feats(x, w, dev):
+    return lambda g0, g1, m: (x[g0:g1, :m].to(dev), w[g0:g1].to(dev))
+
+
+def _image_feats(net, images, P, n_h):
+    nmax = int(P.shape[1])
+
+    def feats(g0, g1, m):
+        # one side of the pair front end, a sub-batch at a time: the backbone's memory is bounded by ``batch``
+        xs, gs = net.image_features([images[g0:g1]], [P[g0:g1]], [n_h[g0:g1]])
+        return xs[0].view(g1 - g0, nmax, C.NODE_FEATURE_DIM), gs[0]
+
+    return feats
+
+
+def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri", subjects=None,
+                     capacity=None):
     """``Net.enroll_keypoints``: see there."""
     what = "enroll_keypoints"
     sc_mode = _check_enroll(net, what, layout, sc_mode)
@@ -617,11 +1126,21 @@ def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layo
     P, n_h = _keypoint_args(what, P, n)
     x, w = _feature_args(what, x, w, int(P.shape[0]), int(P.shape[1]))
     dev = _device_of(device, P, x)
+    return _enroll_device(net, what, P, n_h, _keypoint_feats(x, w, dev), dev, sc_mode, batch, layout, stg, subjects,
+                          capacity)
 
-    def feats(g0, g1, m):
-        return x[g0:g1, :m].to(dev), w[g0:g1].to(dev)
 
-    return _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subjects)
+def enroll_keypoints_into(net, index, P, n, x, w, batch=256, stg="tri", subjects=None):
+    """``Net.enroll_keypoints_into``: see there."""
+    what = "enroll_keypoints_into"
+    _check_into(net, index, what)
+    if subjects is not None:
+        subjects = _check_subjects(what, subjects, int(torch.as_tensor(P).shape[0]))
+    P, n_h = _keypoint_args(what, P, n)
+    x, w = _feature_args(what, x, w, int(P.shape[0]), int(P.shape[1]))
+    dev = index.device
+    return _enroll_device(net, what, P, n_h, _keypoint_feats(x, w, dev), dev, None, batch, None, stg, subjects,
+                          into=index)
 
 
 def _check_images(what, images, G):
@@ -631,7 +1150,8 @@ def _check_images(what, images, G):
     return images
 
 
-def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri", subjects=None):
+def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri", subjects=None,
+                  capacity=None):
     """``Net.enroll_images``: see there."""
     what = "enroll_images"
     net._need_backbone()
@@ -641,14 +1161,21 @@ def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layou
     P, n_h = _keypoint_args(what, P, n)
     images = _check_images(what, images, int(P.shape[0]))
     dev = _device_of(device, P, images)
-    nmax = int(P.shape[1])
+    return _enroll_device(net, what, P, n_h, _image_feats(net, images, P, n_h), dev, sc_mode, batch, layout, stg,
+                          subjects, capacity)
 
-    def feats(g0, g1, m):
-        # one side of the pair front end, a sub-batch at a time: the backbone's memory is bounded by ``batch``
-        xs, gs = net.image_features([images[g0:g1]], [P[g0:g1]], [n_h[g0:g1]])
-        return xs[0].view(g1 - g0, nmax, C.NODE_FEATURE_DIM), gs[0]
 
-    return _enroll_device(net, P, n_h, feats, dev, sc_mode, batch, layout, stg, subjects)
+def enroll_images_into(net, index, images, P, n, batch=256, stg="tri", subjects=None):
+    """``Net.enroll_images_into``: see there."""
+    what = "enroll_images_into"
+    net._need_backbone()
+    _check_into(net, index, what)
+    if subjects is not None:
+        subjects = _check_subjects(what, subjects, int(torch.as_tensor(P).shape[0]))
+    P, n_h = _keypoint_args(what, P, n)
+    images = _check_images(what, images, int(P.shape[0]))
+    return _enroll_device(net, what, P, n_h, _image_feats(net, images, P, n_h), index.device, None, batch, None, stg,
+                          subjects, into=index)
 
 
 def probe_graphs(net, P, n, x=None, w=None, images=None, device=None, stg="tri"):
@@ -760,11 +1287,14 @@ class _ProbeSide:
 
 
 def _select_host(index, select, what):
+    """The entries a query runs over (host int64): ``select`` as given, or all entries: the live ones of an
+    index with removed slots (the one place that defines "all entries"); a removed entry is refused."""
     if select is None:
-        return torch.arange(index.G, dtype=torch.int64)
+        return index.live
     sel = torch.as_tensor(select, dtype=torch.int64).view(-1).cpu()
     if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= index.G:
         raise FpmError("%s: select must name entries in [0, %d)" % (what, index.G))
+    index._check_live(sel, what)
     return sel
 
 
@@ -1269,6 +1799,8 @@ def match_pairs(net, probes, index, pairs, chunks=None):
         raise FpmError("match_pairs: a probe number outside [0, %d)" % probes.G)
     if int(pairs[:, 1].min()) < 0 or int(pairs[:, 1].max()) >= index.G:
         raise FpmError("match_pairs: an entry number outside [0, %d)" % index.G)
+    probes._check_live(pairs[:, 0], "match_pairs (probe)")
+    index._check_live(pairs[:, 1], "match_pairs")
     return _run_pairs(net, probes, index, pairs, chunks)
 
 

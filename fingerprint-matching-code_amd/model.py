@@ -1465,7 +1465,7 @@ class Net(nn.Module):
                                 chunk_timeline_ms=timeline)
         return res
 
-    def enroll(self, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None):
+    def enroll(self, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None, capacity=None):
         """Enrol a gallery for 1:N identification (inference only): run the two SplineConv layers over
         ``graphs`` (dicts as ``fpm.synth.make_graph`` returns) once, in sub-batches of ``batch``, and
         keep their fp32 output rows -> ``fpm.gallery.GalleryIndex`` (3 KB per keypoint).  ``sc_mode``:
@@ -1485,12 +1485,44 @@ class Net(nn.Module):
 
         ``subjects``: one integer label >= 0 per graph, the subject (finger) each impression belongs to;
         kept on the index (``GalleryIndex.subject``, ``set_subjects`` relabels) for
-        ``identify(by="subject")``.  Every other field of the index is the same with or without it."""
+        ``identify(by="subject")``.  Every other field of the index is the same with or without it.
+
+        ``capacity``: (entries, keypoints[, edges]) -- enrol into storage of that size (the sizes of
+        ``GalleryIndex.reserve``), so that ``enroll_into`` can add entries later and a large index need not
+        be copied once to become mutable.  Every field is the same with or without it."""
         from . import gallery
-        return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch, layout=layout, subjects=subjects)
+        return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch, layout=layout, subjects=subjects,
+                              capacity=capacity)
+
+    def enroll_into(self, index, graphs, batch=256, subjects=None):
+        """Enrol ``graphs`` (dicts, as ``enroll`` takes them) into ``index``, an index with capacity
+        (``GalleryIndex.reserve``, ``enroll*(capacity=...)``) -> the new entries' numbers (host int64).  The
+        loop is ``enroll``'s, with the index's own layout and ``sc_mode``; the new rows are written into the
+        free tail of the index's storage and the index changes once, at the end: afterwards every field is
+        the index's fields followed by those of ``enroll(graphs, batch=batch)``, offsets shifted.
+
+        Refused before any launch: an index without capacity, a net with other SplineConv weights,
+        ``subjects`` missing on a labelled index or given on an unlabelled one, graphs with keypoints ``P``
+        on an index without them and the reverse, entries or rows over capacity.  An overflow of the edge
+        capacity, or any error, midway raises ``FpmError`` and leaves the index as it was.  To grow a
+        full index, ``reserve`` a bigger one."""
+        from . import gallery
+        return gallery.enroll_into(self, index, graphs, batch=batch, subjects=subjects)
+
+    def enroll_keypoints_into(self, index, P, n, x, w, batch=256, stg="tri", subjects=None):
+        """``enroll_into`` from keypoints and features on the device: the loop of ``enroll_keypoints`` (one
+        ``ops.rows_pack`` per sub-batch, straight into the index's free rows).  The edge count of graphs
+        built on the device is known only per sub-batch, so the index is committed at the end."""
+        from . import gallery
+        return gallery.enroll_keypoints_into(self, index, P, n, x, w, batch=batch, stg=stg, subjects=subjects)
+
+    def enroll_images_into(self, index, images, P, n, batch=256, stg="tri", subjects=None):
+        """``enroll_keypoints_into`` from images (needs ``Net(backbone=True)``)."""
+        from . import gallery
+        return gallery.enroll_images_into(self, index, images, P, n, batch=batch, stg=stg, subjects=subjects)
 
     def enroll_keypoints(self, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri",
-                         subjects=None):
+                         subjects=None, capacity=None):
         """``enroll`` from keypoints and features, on the device: no host graph dicts.  P: (G, nmax, 2)
         fp32 padded keypoints, n: (G,) counts in [1, nmax], x: (G, nmax, 768) or (G * nmax, 768) fp32
         node features (padding rows are ignored), w: (G, 512) global features; tensors or arrays, host
@@ -1501,19 +1533,19 @@ class Net(nn.Module):
         writes the sub-batch's ragged rows -- fp32, bf16 or both, by ``layout`` -- into their place in
         the index, whose rows are allocated once: the device peak is the index plus one sub-batch.
         -> ``GalleryIndex``, every field equal to ``enroll`` on the same graphs as host dicts with the
-        same ``batch``.  ``sc_mode`` / ``layout`` / ``subjects``: as ``enroll``."""
+        same ``batch``.  ``sc_mode`` / ``layout`` / ``subjects`` / ``capacity``: as ``enroll``."""
         from . import gallery
         return gallery.enroll_keypoints(self, P, n, x, w, device=device, sc_mode=sc_mode, batch=batch, layout=layout,
-                                        stg=stg, subjects=subjects)
+                                        stg=stg, subjects=subjects, capacity=capacity)
 
     def enroll_images(self, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri",
-                      subjects=None):
+                      subjects=None, capacity=None):
         """``enroll_keypoints`` from images (needs ``Net(backbone=True)``): images (G, 3, H, W), P and n as
         there.  Per sub-batch ``image_features`` (backbone + feature_align, one side) makes x and w, so
         the backbone's memory is bounded by ``batch``."""
         from . import gallery
         return gallery.enroll_images(self, images, P, n, device=device, sc_mode=sc_mode, batch=batch, layout=layout,
-                                     stg=stg, subjects=subjects)
+                                     stg=stg, subjects=subjects, capacity=capacity)
 
     def probe_graphs(self, P, n, x=None, w=None, images=None, device=None, stg="tri"):
         """Probe graphs for ``identify`` / ``coarse_scores`` from keypoints, on the device -> a list of

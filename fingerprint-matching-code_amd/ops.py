@@ -3,8 +3,8 @@
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
 no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``topk_merge``,
-``group_scores``, ``group_topr``, ``cohort_decide``, ``coarse_score`` / ``coarse_pairs``, ``rows_fetch`` and
-``rows_pack`` alone keep a plain-torch host path for CPU tensors: the statements of the ordering and of the merge of
+``group_scores``, ``group_topr``, ``cohort_decide``, ``coarse_score`` / ``coarse_pairs``, ``rows_fetch``,
+``rows_pack`` and ``rows_move`` alone keep a plain-torch host path for CPU tensors: the statements of the ordering and of the merge of
 sorted lists, of the group fusions, of the cohort statistics, of the coarse score and of the ragged copies, which the
 tests hold the kernels to).
 """
@@ -482,6 +482,102 @@ def rows_pack(src, n, nmax, out_off, out32=None, out16=None, n_host=None, out_of
         _lib.call("fpm_rows_pack", _p(src), int(src.shape[0]), _p(n), B, nmax, _p(out_off), _p(out32), _p(out16),
                   int(out_rows), _stream(src))
     return out32, out16
+
+
+def _ranges_meet(a0, a1, b0, b1):
+    """Whether some range [a0[i], a1[i]) meets some range [b0[j], b1[j]) (host int64, none empty)."""
+    if a0.numel() == 0 or b0.numel() == 0:
+        return False
+    order = torch.argsort(a0)
+    start, reach = a0[order], torch.cummax(a1[order], 0)[0]
+    # the ranges a that start before b's end: the furthest any of them reaches is past b's start
+    before = torch.searchsorted(start, b1, right=False)
+    return bool(((before > 0) & (reach[(before - 1).clamp(min=0)] > b0)).any())
+
+
+def rows_move(src_off, dst_off, cnt, src32=None, dst32=None, src16=None, dst16=None, src_off_host=None,
+              dst_off_host=None, cnt_host=None):
+    """Ragged segment copy (fpm_rows_move): segment k goes from rows [src_off[k], src_off[k] + cnt[k]) of the
+    source to rows [dst_off[k], dst_off[k] + cnt[k]) of the destination (int64 [K] each, K <= 65535) -- the
+    fp32 rows ``src32`` -> ``dst32``, the bf16 rows ``src16`` -> ``dst16`` (as bits: nothing is rounded), or
+    both pairs from the one offset table, in one launch -> (dst32, dst16).  Rows outside the destination
+    ranges are not written.
+
+    Everything lives on one device.  Checked on the host before anything is launched: dtypes, contiguity,
+    devices, every range inside its tensor, destination ranges that do not meet each other, and -- a pair's
+    source and destination may be the same tensor, which is how an index is compacted inside its storage --
+    that then no destination range meets a source range: the segments are copied in no particular order, so
+    nothing that is read may be written.  A source and a destination that share memory without being the
+    same rows are refused.  (``*_host``: host copies of the tables, so the check needs no device
+    synchronisation; without them the device tensors are copied back.)  All-CPU tensors take the torch
+    statement of the copy."""
+    _check_index_tensors("rows_move", (("src_off", src_off, torch.int64), ("dst_off", dst_off, torch.int64),
+                                       ("cnt", cnt, torch.int64)))
+    if (src32 is None) != (dst32 is None) or (src16 is None) != (dst16 is None):
+        raise _lib.FpmError("rows_move: src32 goes with dst32, src16 with dst16")
+    if src32 is None and src16 is None:
+        raise _lib.FpmError("rows_move: give the fp32 rows (src32, dst32), the bf16 rows (src16, dst16) or both")
+    pairs = [(s, d, dt) for s, d, dt in ((src32, dst32, torch.float32), (src16, dst16, torch.bfloat16))
+             if s is not None]
+    for s, d, dt in pairs:
+        for name, t in (("src", s), ("dst", d)):
+            name += "32" if dt == torch.float32 else "16"
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 768 \
+                    or not t.is_contiguous():
+                raise _lib.FpmError("rows_move: %s must be contiguous %s rows of 768 channels"
+                                    % (name, "bf16" if dt == torch.bfloat16 else "fp32"))
+    dev = pairs[0][1].device
+    for name, t in (("src_off", src_off), ("dst_off", dst_off), ("cnt", cnt), ("src32", src32), ("dst32", dst32),
+                    ("src16", src16), ("dst16", dst16)):
+        if t is not None and t.device != dev:
+            raise _lib.FpmError("rows_move: %s is on %s, the destination on %s" % (name, t.device, dev))
+    K = int(cnt.numel())
+    if src_off.numel() != K or dst_off.numel() != K:
+        raise _lib.FpmError("rows_move: %d source offsets, %d destination offsets and %d counts (one of each per "
+                            "segment)" % (src_off.numel(), dst_off.numel(), K))
+    if K > 65535:
+        raise _lib.FpmError("rows_move: at most 65535 segments per call")
+    sh, dh, ch = _host_copy(src_off_host, src_off), _host_copy(dst_off_host, dst_off), _host_copy(cnt_host, cnt)
+    if sh.numel() != K or dh.numel() != K or ch.numel() != K:
+        raise _lib.FpmError("rows_move: host copies of src_off / dst_off / cnt do not match the device tensors")
+    src_rows = min(int(s.shape[0]) for s, _, _ in pairs)
+    dst_rows = min(int(d.shape[0]) for _, d, _ in pairs)
+    if K:
+        if int(ch.min()) < 0:
+            raise _lib.FpmError("rows_move: a negative row count (%d)" % int(ch.min()))
+        if int(sh.min()) < 0 or int((sh + ch).max()) > src_rows:
+            raise _lib.FpmError("rows_move: a source range outside the %d rows of the source" % src_rows)
+        if int(dh.min()) < 0 or int((dh + ch).max()) > dst_rows:
+            raise _lib.FpmError("rows_move: a destination range outside the %d rows of the destination" % dst_rows)
+    some = ch > 0
+    s0, d0, c = sh[some], dh[some], ch[some]
+    order = torch.argsort(d0)
+    if bool((d0[order][1:] < (d0 + c)[order][:-1]).any()):
+        raise _lib.FpmError("rows_move: two destination ranges meet")
+    for s, d, dt in pairs:
+        lo_s, lo_d = s.data_ptr(), d.data_ptr()
+        hi_s, hi_d = lo_s + s.numel() * s.element_size(), lo_d + d.numel() * d.element_size()
+        if s.device != d.device or lo_s >= hi_d or lo_d >= hi_s:
+            continue                                         # two buffers
+        if lo_s != lo_d:
+            raise _lib.FpmError("rows_move: the source and the destination share memory without being the same "
+                                "rows; pass the one tensor as both")
+        if _ranges_meet(s0, s0 + c, d0, d0 + c):
+            raise _lib.FpmError("rows_move: source and destination are one tensor and a destination range meets a "
+                                "source range (the segments are copied in no particular order; move such rows "
+                                "through a staging buffer)")
+    total = int(c.sum())
+    if not dev.type == "cuda":
+        if total:
+            at = lambda o: torch.cat([torch.arange(a, a + k) for a, k in zip(o.tolist(), c.tolist())])
+            rs, rd = at(s0), at(d0)
+            for s, d, _ in pairs:
+                d[rd] = s[rs]                                # the right side is gathered before anything is written
+        return dst32, dst16
+    if total:
+        _lib.call("fpm_rows_move", _p(src32), _p(src16), src_rows, _p(src_off), _p(dst_off), _p(cnt), K, int(c.max()),
+                  _p(dst32), _p(dst16), dst_rows, _stream(pairs[0][1]))
+    return dst32, dst16
 
 
 def rank_key(scores, ids=None):

@@ -54,6 +54,10 @@ class ShardedGallery:
     (``Net.enroll(part, device)``), and the parts are passed here; ``split`` cuts an index that does fit one
     device (the convenience and test route).  The shards save and load as they do alone.
 
+    The shards are taken as they are now: a shard with removed entries is refused (``compact`` it first), and
+    a query after a shard was mutated is refused (build the ShardedGallery again); a mutable shard set is not
+    built.
+
     Refused: no shard or more than 16; shards that differ in ``sc_mode``, ``weights_id`` or layout; some shards
     with subject labels and others without; an ``entry`` table that does not ascend, collides with another
     shard's or leaves a number out.
@@ -73,6 +77,8 @@ class ShardedGallery:
         for s in shards:
             if not isinstance(s, GalleryIndex):
                 raise FpmError("%s: every shard must be a GalleryIndex (Net.enroll, GalleryIndex.slice)" % what)
+        if any(s.tombstones for s in shards):
+            raise FpmError("%s: a shard has removed entries; compact it first (GalleryIndex.compact)" % what)
         first = shards[0]
         for name in ("sc_mode", "weights_id", "layout"):
             if any(getattr(s, name) != getattr(first, name) for s in shards):
@@ -133,6 +139,15 @@ class ShardedGallery:
             self.subject_d = [p.to(torch.int32).to(s.device) for p, s in zip(places, shards)]
             self._labels_out = self.labels.to(self.output_device)
         self._replicas = {}                                                # device -> (the net, its replica)
+        self._generation = [s.generation for s in shards]                  # the tables above describe these shards
+
+    def _check_unchanged(self, what):
+        """Refuse a query over shards that were mutated (``enroll_into``, ``remove``, ``compact``) after this
+        ShardedGallery was built: its tables describe the shards as they were."""
+        for i, (s, g) in enumerate(zip(self.shards, self._generation)):
+            if s.generation != g:
+                raise FpmError("%s: shard %d has changed since this ShardedGallery was built (generation %d, then %d); "
+                               "build the ShardedGallery again" % (what, i, s.generation, g))
 
     @property
     def G(self):
@@ -216,6 +231,7 @@ def identify_sharded(net, probes, sharded, topk=10, select=None, score="cls_prob
         _refuse("shortlist=None", "a sharded gallery is searched through a shortlist; pass shortlist=M")
     if select is not None:
         _refuse("select", "a selection of entries is not built for shards")
+    sharded._check_unchanged(what)
     shards = sharded.shards
     subj = G_._check_by(what, shards[0], by, fuse, impressions, shortlist)
     if subj and sharded.subject_split:

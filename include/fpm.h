@@ -276,6 +276,18 @@ int fpm_rows_fetch(const float* src, long src_rows, const long* row_off, const i
  * outside the outputs).  Padding rows are not read; n[b] = 0 writes nothing. */
 int fpm_rows_pack(const float* src, long src_rows, const int* n, int B, int nmax, const long* out_off, float* out32,
                   void* out16, long out_rows, void* stream);
+/* Ragged segment copy (compaction of a mutable gallery index: the live entries' rows moved towards the
+ * front of their storage, or to and from a staging buffer).  K <= 65535 segments in one launch; segment k
+ * goes from rows [src_off[k], src_off[k] + cnt[k]) of the source to rows [dst_off[k], dst_off[k] + cnt[k]) of
+ * the destination (src_off, dst_off, cnt: K int64 each, device): src32 -> dst32 (src_rows / dst_rows x 768
+ * fp32), src16 -> dst16 (x 768 bf16, copied as bits: nothing is rounded), or both pairs from the one offset
+ * table; a pair is given whole or not at all (NULL, NULL).  band_rows: the largest cnt (the grid's extent).
+ * All rows 16-byte aligned.  Source and destination may be one buffer when no destination range meets a
+ * source range and the destination ranges are disjoint: the caller checks that, and every range; a segment
+ * that violates its bounds is not copied (nothing is read outside the source or written outside the
+ * destination).  cnt[k] = 0 copies nothing. */
+int fpm_rows_move(const float* src32, const void* src16, long src_rows, const long* src_off, const long* dst_off,
+                  const long* cnt, int K, int band_rows, float* dst32, void* dst16, long dst_rows, void* stream);
 /* vertex_attr_to_edge_attr (spline_conv.py:73-81): out[e] = x[src[e]] - x[dst[e]] */
 int fpm_edge_diff(const float* x, const int* src, const int* dst, long E, int D, float* out, void* stream);
 /* same, written into a padded per-pair layout and scaled: out[row[e]] = (x[src]-x[dst]) o c[pair[e]]
