@@ -57,6 +57,8 @@ SIGNATURES = {
     "fpm_rows_fetch": (I, [P, L, P, P, I, I, I, P, L, P, P]),
     "fpm_rows_pack": (I, [P, L, P, I, I, P, P, P, L, P]),
     "fpm_rows_move": (I, [P, P, L, P, P, P, I, I, P, P, L, P]),
+    "fpm_rows_move8": (I, [P, P, L, P, P, P, I, I, P, P, L, P]),
+    "fpm_rows_quant8": (I, [P, L, P, P, P]),
     "fpm_edge_diff_padded":(I, [P, P, P, P, P, P, L, I, P, P]),
     "fpm_kron_gnn_layer_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fpm_kron_gnn_layer_fwd_ord": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
@@ -134,14 +136,14 @@ SIGNATURES = {
                              ctypes.POINTER(I)]),
 }
 
-# The coarse kernels' entry points (fpm_coarse_{score,pairs}[_wide|_stream][_rows16]): one probe (yp, n0) or
-# a pair list (yq, qrow_off, qidx, Q) after (y, row_off, idx, G, B), then (coef, iters, tau, score), the
-# wide and streamed kernels' (ws, ws_bytes), and the stream.
+# The coarse kernels' entry points (fpm_coarse_{score,pairs}[_wide|_stream][_rows16|_rows8]): one probe (yp, n0)
+# or a pair list (yq, qrow_off, qidx, Q) after (y, row_off, idx, G, B) -- _rows8: (y8, s8, row_off, ...) --, then
+# (coef, iters, tau, score), the wide and streamed kernels' (ws, ws_bytes), and the stream.
 for _op, _probe in (("score", [P, I]), ("pairs", [P, P, P, I])):
     for _kernel, _ws in (("", []), ("_wide", [P, L]), ("_stream", [P, L])):
-        for _rows in ("", "_rows16"):
+        for _rows in ("", "_rows16", "_rows8"):
             SIGNATURES["fpm_coarse_%s%s%s" % (_op, _kernel, _rows)] = (
-                I, [P, P, P, I, I] + _probe + [P, I, F, P] + _ws + [P])
+                I, [P] * (2 if _rows == "_rows8" else 1) + [P, P, I, I] + _probe + [P, I, F, P] + _ws + [P])
 
 _lib = None
 

@@ -53,12 +53,14 @@ using namespace fpm::coarse;
 // a K tile: 8 float4 (128 rows) or 4 vectors of 8 bf16 per thread (coarse_tile.h)
 using KTile = Tile<CT, CBK, CROW>;
 
-// YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment).
+// YT: the entry rows' type, float (rounded on the way into LDS), bf16_t (rounded at enrolment) or fp8_t
+// (e4m3 with a row scale, quantised at enrolment and dequantised, exactly, on the way into LDS).
 // PAIRS: the probe of pair b comes from a second row store (a pair list: coarse_probe.h); the lookup
 // below is the only code that differs.
 // two workgroups per CU (LDS allows it): hold the registers to two waves per SIMD
 template <typename YT, bool PAIRS>
-__global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void coarse_score_kernel(const YT* __restrict__ y,
+__global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void coarse_score_kernel(
+                                                           typename EntryRows<YT>::arg y,
                                                            const long* __restrict__ row_off,
                                                            const int* __restrict__ idx, int G,
                                                            const float* __restrict__ yp, int n0,
@@ -98,15 +100,15 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     // the Sinkhorn works on the transpose when n0 > n_g: its rows are the smaller side
     const bool tr = n0 > ng;
     const int R = tr ? ng : n0, C = tr ? n0 : ng;
-    constexpr bool F32 = sizeof(YT) == 4;
-    const YT* ye = y + r0 * CK;                      // the entry's rows
+    constexpr bool F32 = sizeof(YT) == 4, F8 = sizeof(YT) == 1;
+    const auto ye = y + r0 * CK;                   // the entry's rows
     const float* xa = nullptr;                       // rows side (MFMA A)
     const float* xb = nullptr;                       // columns side (MFMA B)
     if constexpr (F32) {
         xa = tr ? ye : yp;
         xb = tr ? yp : ye;
     }
-    // bf16 entry rows: the probe's tile is At and the entry's Bt, the other way round when transposed
+    // bf16 and fp8 entry rows: the probe's tile is At and the entry's Bt, the other way round when transposed
     unsigned char* Pt = tr ? Bt : At;
     unsigned char* Et = tr ? At : Bt;
     const float* cf = coef + (long)b * CK;
@@ -122,9 +124,15 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
     float4 ra[8], rb[8], sc;
     uint4 re[4];
+    uint2 r8[4];
+    float s8[4];
     if constexpr (F32) {
         KTile::load(xa, R, 0, 0, tid, ra);
         KTile::load(xb, C, 0, 0, tid, rb);
+    } else if constexpr (F8) {
+        KTile::load(yp, n0, 0, 0, tid, ra);
+        KTile::load8(ye, ng, 0, 0, tid, r8);
+        KTile::load8_scale(ye, ng, 0, tid, s8);
     } else {
         KTile::load(yp, n0, 0, 0, tid, ra);
         KTile::load16(ye, ng, 0, 0, tid, re);
@@ -135,6 +143,9 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         if constexpr (F32) {
             KTile::store(At, tid, ra, tr ? one : sc);
             KTile::store(Bt, tid, rb, tr ? sc : one);
+        } else if constexpr (F8) {
+            KTile::store(Pt, tid, ra, sc);
+            KTile::store8(Et, tid, r8, s8);
         } else {
             KTile::store(Pt, tid, ra, sc);
             KTile::store16(Et, tid, re);
@@ -144,6 +155,9 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             if constexpr (F32) {
                 KTile::load(xa, R, 0, (kt + 1) * CBK, tid, ra);
                 KTile::load(xb, C, 0, (kt + 1) * CBK, tid, rb);
+            } else if constexpr (F8) {
+                KTile::load(yp, n0, 0, (kt + 1) * CBK, tid, ra);
+                KTile::load8(ye, ng, 0, (kt + 1) * CBK, tid, r8);
             } else {
                 KTile::load(yp, n0, 0, (kt + 1) * CBK, tid, ra);
                 KTile::load16(ye, ng, 0, (kt + 1) * CBK, tid, re);
@@ -308,8 +322,8 @@ struct Fused {
     static constexpr const char *score_op = "coarse_score", *pairs_op = "coarse_pairs", *bound = "COARSE_NMAX";
     static constexpr int nmax = FPM_COARSE_NMAX;
     template <typename YT, bool PAIRS>
-    static int launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B, const float* ypq,
-                      int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
+    static int launch(const char* what, typename EntryRows<YT>::host y, const long* row_off, const int* idx, int G,
+                      int B, const float* ypq, int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
                       float* score, void* ws, long ws_bytes, void* stream) {
         constexpr int lds = LDS_FLOATS * (int)sizeof(float);
         if (hipFuncSetAttribute((const void*)coarse_score_kernel<YT, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -327,27 +341,43 @@ struct Fused {
 
 extern "C" int fpm_coarse_score(const float* y, const long* row_off, const int* idx, int G, int B, const float* yp,
                                 int n0, const float* coef, int iters, float tau, float* score, void* stream) {
-    return fpm::coarse_score_entry<Fused>("fpm_coarse_score", y, row_off, idx, G, B, yp, n0, coef, iters, tau, score,
+    return fpm::coarse_score_entry<Fused, float>("fpm_coarse_score", y, row_off, idx, G, B, yp, n0, coef, iters, tau, score,
                                           nullptr, 0, stream);
 }
 
 extern "C" int fpm_coarse_score_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                        const float* yp, int n0, const float* coef, int iters, float tau, float* score,
                                        void* stream) {
-    return fpm::coarse_score_entry<Fused>("fpm_coarse_score_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0,
+    return fpm::coarse_score_entry<Fused, bf16_t>("fpm_coarse_score_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0,
                                           coef, iters, tau, score, nullptr, 0, stream);
 }
 
 extern "C" int fpm_coarse_pairs(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
                                 const long* qrow_off, const int* qidx, int Q, const float* coef, int iters, float tau,
                                 float* score, void* stream) {
-    return fpm::coarse_pairs_entry<Fused>("fpm_coarse_pairs", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef, iters,
+    return fpm::coarse_pairs_entry<Fused, float>("fpm_coarse_pairs", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef, iters,
                                           tau, score, nullptr, 0, stream);
 }
 
 extern "C" int fpm_coarse_pairs_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                        const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
                                        int iters, float tau, float* score, void* stream) {
-    return fpm::coarse_pairs_entry<Fused>("fpm_coarse_pairs_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
+    return fpm::coarse_pairs_entry<Fused, bf16_t>("fpm_coarse_pairs_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
                                           qrow_off, qidx, Q, coef, iters, tau, score, nullptr, 0, stream);
+}
+
+extern "C" int fpm_coarse_score_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G, int B,
+                                      const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                                      void* stream) {
+    return fpm::coarse_score_entry<Fused, fp8_t>("fpm_coarse_score_rows8", rows8_t{(const unsigned char*)y8, s8},
+                                                 row_off, idx, G, B, yp, n0, coef, iters, tau, score, nullptr, 0,
+                                                 stream);
+}
+
+extern "C" int fpm_coarse_pairs_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G, int B,
+                                      const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
+                                      int iters, float tau, float* score, void* stream) {
+    return fpm::coarse_pairs_entry<Fused, fp8_t>("fpm_coarse_pairs_rows8", rows8_t{(const unsigned char*)y8, s8},
+                                                 row_off, idx, G, B, yq, qrow_off, qidx, Q, coef, iters, tau, score,
+                                                 nullptr, 0, stream);
 }

@@ -7,6 +7,7 @@
 #pragma once
 #include <vector>
 
+#include "coarse_tile.h"
 #include "fpm_common.h"
 
 namespace fpm {
@@ -66,20 +67,21 @@ inline int coarse_pairs_probe_range(const long* qrow_off, const int* qidx, int Q
 
 // The host side of the C entry points, once for the three kernels.  K is a kernel's traits: its op names
 // (``score_op``, ``pairs_op``) as the messages spell them, its bound (``bound``, ``nmax``), and
+// (YT: float, bf16_t or coarse::fp8_t; y: coarse::EntryRows<YT>::host, a pointer or the fp8 rows' pair)
 //     K::launch<YT, PAIRS>(what, y, row_off, idx, G, B, ypq, n0q, qrow_off, qidx, n0max, coef, iters, tau,
 //                          score, ws, ws_bytes, stream)
 // which checks the kernel's workspace (n0max: the largest probe of the launch), sizes the grid and
 // launches.  ws / ws_bytes are null / 0 for a kernel without a workspace.
 template <class K, typename YT>
-int coarse_score_entry(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B, const float* yp,
-                       int n0, const float* coef, int iters, float tau, float* score, void* ws, long ws_bytes,
-                       void* stream) {
+int coarse_score_entry(const char* what, typename coarse::EntryRows<YT>::host y, const long* row_off, const int* idx,
+                       int G, int B, const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                       void* ws, long ws_bytes, void* stream) {
     FPM_CHECK_ARG(G > 0 && B >= 0, "%s: bad sizes (G %d, B %d)", K::score_op, G, B);
     FPM_CHECK_ARG(n0 >= 1 && n0 <= K::nmax, "%s: probe of %d keypoints outside [1, %s = %d]", K::score_op, n0, K::bound,
                   K::nmax);
     FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "%s: iters >= 0 and tau > 0 required", K::score_op);
-    FPM_CHECK_ARG(y && row_off && idx && yp && coef && score, "%s: y, row_off, idx, yp, coef and score are required",
-                  K::score_op);
+    FPM_CHECK_ARG(coarse::rows_given(y) && row_off && idx && yp && coef && score,
+                  "%s: y (fp8 rows: and their scales), row_off, idx, yp, coef and score are required", K::score_op);
     if (B == 0) return 0;
     return K::template launch<YT, false>(what, y, row_off, idx, G, B, yp, n0, nullptr, nullptr, n0, coef, iters, tau,
                                          score, ws, ws_bytes, stream);
@@ -87,13 +89,14 @@ int coarse_score_entry(const char* what, const YT* y, const long* row_off, const
 
 // the pair list: the one-probe refusals, the probe sizes read back from the device
 template <class K, typename YT>
-int coarse_pairs_entry(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B, const float* yq,
-                       const long* qrow_off, const int* qidx, int Q, const float* coef, int iters, float tau,
-                       float* score, void* ws, long ws_bytes, void* stream) {
+int coarse_pairs_entry(const char* what, typename coarse::EntryRows<YT>::host y, const long* row_off, const int* idx,
+                       int G, int B, const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
+                       int iters, float tau, float* score, void* ws, long ws_bytes, void* stream) {
     FPM_CHECK_ARG(G > 0 && Q > 0 && B >= 0, "%s: bad sizes (G %d, Q %d, B %d)", K::pairs_op, G, Q, B);
     FPM_CHECK_ARG(iters >= 0 && tau > 0.f, "%s: iters >= 0 and tau > 0 required", K::pairs_op);
-    FPM_CHECK_ARG(y && row_off && idx && yq && qrow_off && qidx && coef && score,
-                  "%s: y, row_off, idx, yq, qrow_off, qidx, coef and score are required", K::pairs_op);
+    FPM_CHECK_ARG(coarse::rows_given(y) && row_off && idx && yq && qrow_off && qidx && coef && score,
+                  "%s: y (fp8 rows: and their scales), row_off, idx, yq, qrow_off, qidx, coef and score are required",
+                  K::pairs_op);
     if (B == 0) return 0;
     long lo, hi;
     if (coarse_pairs_probe_range(qrow_off, qidx, Q, B, stream, lo, hi)) return 1;

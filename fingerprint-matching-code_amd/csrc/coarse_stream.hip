@@ -70,12 +70,13 @@ __device__ __forceinline__ float lval(float kp, float s, float r1, float u, floa
     return __fsub_rn(__fsub_rn(__fsub_rn(__fmul_rn(kp, s), r1), u), v);
 }
 
-// YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment); the
+// YT: the entry rows' type, float (rounded on the way into LDS), bf16_t (rounded at enrolment) or fp8_t
+// (e4m3 with a row scale, quantised at enrolment and dequantised, exactly, on the way into LDS); the
 // probe side and everything after the tile store are the same code, so are the bits.  PAIRS: the probe
 // of pair b comes from a second row store (a pair list: coarse_probe.h), looked up per pair of the
 // persistent walk; that lookup is the only code that differs
 template <typename YT, bool PAIRS>
-__global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const YT* __restrict__ y,
+__global__ __launch_bounds__(ST) void coarse_score_stream_kernel(typename EntryRows<YT>::arg y,
                                                                  const long* __restrict__ row_off,
                                                                  const int* __restrict__ idx, int G, int B,
                                                                  const float* __restrict__ ypq, int n0q,
@@ -120,8 +121,8 @@ __global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const YT* __res
             if (tid == 0) score[b] = __uint_as_float(0x7FC00000u);
             continue;
         }
-        constexpr bool F32 = sizeof(YT) == 4;
-        const YT* xe = y + r0 * SK;                  // the entry's rows: MFMA A, tiles of 128
+        constexpr bool F32 = sizeof(YT) == 4, F8 = sizeof(YT) == 1;
+        const auto xe = y + r0 * SK;               // the entry's rows: MFMA A, tiles of 128
         const float* cf = coef + (long)b * SK;
         const int nd = C - R;                        // dummy rows (dummy_row = True)
         const float fnd = (float)nd;
@@ -138,14 +139,20 @@ __global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const YT* __res
                 const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
                 float4 ra[4], rb[8], s4;
                 uint4 re[2];                             // bf16 entry rows, in ra's place
+                uint2 r8[2];                             // fp8 entry rows and their rows' scales, in ra's place
+                float s8[2];
                 if constexpr (F32) KTile::load(xe, ng, te, 0, tid, ra);
-                else KTile::load16(xe, ng, te, 0, tid, re);
+                else if constexpr (F8) {
+                    KTile::load8(xe, ng, te, 0, tid, r8);
+                    KTile::load8_scale(xe, ng, te, tid, s8);
+                } else KTile::load16(xe, ng, te, 0, tid, re);
                 KTile::load(yp, n0, tp, 0, tid, rb);
                 s4 = *(const float4*)(cf + c4);
                 for (int kt = 0; kt < SK / SBK; ++kt) {
                     unsigned char* At = slds + (kt & 1) * SBUF;
                     unsigned char* Bt = At + ATILE;
                     if constexpr (F32) KTile::store(At, tid, ra, one);
+                    else if constexpr (F8) KTile::store8(At, tid, r8, s8);
                     else KTile::store16(At, tid, re);
                     KTile::store(Bt, tid, rb, s4);
                     // one barrier per K tile: the other buffer was last read before the previous barrier
@@ -153,6 +160,7 @@ __global__ __launch_bounds__(ST) void coarse_score_stream_kernel(const YT* __res
                     __syncthreads();
                     if (kt + 1 < SK / SBK) {
                         if constexpr (F32) KTile::load(xe, ng, te, (kt + 1) * SBK, tid, ra);
+                        else if constexpr (F8) KTile::load8(xe, ng, te, (kt + 1) * SBK, tid, r8);
                         else KTile::load16(xe, ng, te, (kt + 1) * SBK, tid, re);
                         KTile::load(yp, n0, tp, (kt + 1) * SBK, tid, rb);
                         s4 = *(const float4*)(cf + (kt + 1) * SBK + c4);
@@ -411,8 +419,8 @@ struct Stream {
                                 *bound = "COARSE_STREAM_NMAX";
     static constexpr int nmax = FPM_COARSE_STREAM_NMAX;
     template <typename YT, bool PAIRS>
-    static int launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B, const float* ypq,
-                      int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
+    static int launch(const char* what, typename EntryRows<YT>::host y, const long* row_off, const int* idx, int G,
+                      int B, const float* ypq, int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
                       float* score, void* ws, long ws_bytes, void* stream) {
         const int grid = B < SGRID ? B : SGRID;
         const long need = fpm_coarse_score_stream_ws_bytes(B, n0max, 1);
@@ -438,21 +446,21 @@ struct Stream {
 extern "C" int fpm_coarse_score_stream(const float* y, const long* row_off, const int* idx, int G, int B,
                                        const float* yp, int n0, const float* coef, int iters, float tau, float* score,
                                        void* ws, long ws_bytes, void* stream) {
-    return fpm::coarse_score_entry<Stream>("fpm_coarse_score_stream", y, row_off, idx, G, B, yp, n0, coef, iters, tau,
+    return fpm::coarse_score_entry<Stream, float>("fpm_coarse_score_stream", y, row_off, idx, G, B, yp, n0, coef, iters, tau,
                                            score, ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_score_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                               const float* yp, int n0, const float* coef, int iters, float tau,
                                               float* score, void* ws, long ws_bytes, void* stream) {
-    return fpm::coarse_score_entry<Stream>("fpm_coarse_score_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp,
+    return fpm::coarse_score_entry<Stream, bf16_t>("fpm_coarse_score_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp,
                                            n0, coef, iters, tau, score, ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_pairs_stream(const float* y, const long* row_off, const int* idx, int G, int B,
                                        const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
                                        int iters, float tau, float* score, void* ws, long ws_bytes, void* stream) {
-    return fpm::coarse_pairs_entry<Stream>("fpm_coarse_pairs_stream", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef,
+    return fpm::coarse_pairs_entry<Stream, float>("fpm_coarse_pairs_stream", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef,
                                            iters, tau, score, ws, ws_bytes, stream);
 }
 
@@ -460,6 +468,23 @@ extern "C" int fpm_coarse_pairs_stream_rows16(const void* y16, const long* row_o
                                               const float* yq, const long* qrow_off, const int* qidx, int Q,
                                               const float* coef, int iters, float tau, float* score, void* ws,
                                               long ws_bytes, void* stream) {
-    return fpm::coarse_pairs_entry<Stream>("fpm_coarse_pairs_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
+    return fpm::coarse_pairs_entry<Stream, bf16_t>("fpm_coarse_pairs_stream_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
                                            qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_score_stream_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G,
+                                             int B, const float* yp, int n0, const float* coef, int iters, float tau,
+                                             float* score, void* ws, long ws_bytes, void* stream) {
+    return fpm::coarse_score_entry<Stream, fp8_t>("fpm_coarse_score_stream_rows8",
+                                                  rows8_t{(const unsigned char*)y8, s8}, row_off, idx, G, B, yp, n0,
+                                                  coef, iters, tau, score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_pairs_stream_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G,
+                                             int B, const float* yq, const long* qrow_off, const int* qidx, int Q,
+                                             const float* coef, int iters, float tau, float* score, void* ws,
+                                             long ws_bytes, void* stream) {
+    return fpm::coarse_pairs_entry<Stream, fp8_t>("fpm_coarse_pairs_stream_rows8",
+                                                  rows8_t{(const unsigned char*)y8, s8}, row_off, idx, G, B, yq,
+                                                  qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
 }

@@ -1,6 +1,7 @@
 // Device helpers shared by the three coarse-score kernels (coarse.hip, coarse_wide.hip,
-// coarse_stream.hip): the vector types, the 16-lane maximum, the native softplus, and the copy of one
-// side's K tile from global memory into LDS, written once over the kernel's geometry.
+// coarse_stream.hip): the vector types, the 16-lane maximum, the native softplus, the three forms of the
+// entry rows (fp32, bf16, fp8 with a row scale), and the copy of one side's K tile from global memory into
+// LDS, written once over the kernel's geometry.
 #pragma once
 #include "fpm_common.h"
 
@@ -31,6 +32,32 @@ __device__ __forceinline__ float softplus_native(float x) {
 __device__ __forceinline__ float finite_max(float m) { return m == -INFINITY ? 0.f : m; }
 
 constexpr int log2_of(int v) { return v <= 1 ? 0 : 1 + log2_of(v >> 1); }
+
+// The entry rows as a kernel takes them.  fp32 and bf16 rows: a pointer to YT.  fp8 rows (the _rows8 entry
+// points: an index that keeps e4m3 bytes and one power-of-two fp32 scale per row, ops.rows_quant8): the tag
+// type fp8_t stands for them and the kernel's argument is the pair of pointers, so that the fp32 and bf16
+// instantiations keep the argument list, and with it the registers, that they had.
+struct fp8_t {
+    unsigned char v;
+};
+struct rows8_t {
+    const unsigned char* y;   // (rows, 768) e4m3 (OCP: gfx950's own encoding)
+    const float* s;           // (rows,) 2^e
+};
+template <typename YT>
+struct EntryRows {
+    typedef const YT* __restrict__ arg;
+    typedef const YT* host;
+};
+template <>
+struct EntryRows<fp8_t> {
+    typedef rows8_t arg;
+    typedef rows8_t host;
+};
+// y + o: the rows from channel offset o (a multiple of 768) on, as for a pointer to fp32 or bf16 rows
+__device__ __forceinline__ rows8_t operator+(rows8_t y, long o) { return rows8_t{y.y + o, y.s + o / 768}; }
+inline bool rows_given(const void* y) { return y != nullptr; }
+inline bool rows_given(rows8_t y) { return y.y != nullptr && y.s != nullptr; }
 
 // One side's K tile of a workgroup of T threads: BK channels of up to NM passes of rows, each operand
 // row ROW bytes apart in LDS (BK bf16 + padding).  A thread's place is written as a shift and a mask of
@@ -89,6 +116,48 @@ struct Tile {
         const int row0 = tid >> SH16, c = 8 * (tid & (BK / 8 - 1));
 #pragma unroll
         for (int m = 0; m < NM; ++m) *(uint4*)(tile + (row0 + RP16 * m) * ROW + c * 2) = r[m];
+    }
+    // the entry's K tile from fp8 rows (the _rows8 entry points): load16's geometry, this thread's NM vectors
+    // of 8 e4m3 bytes (a row is 768 B, so every vector is 8-B aligned), zeros past n.  A thread's rows are the
+    // same in every K tile, so their scales are loaded once per block tile (load8_scale, under the same guard)
+    template <int NM>
+    static __device__ __forceinline__ void load8(rows8_t base, int n, int row_base, int k0, int tid, uint2 (&r)[NM]) {
+        const int row0 = row_base + (tid >> SH16), c = 8 * (tid & (BK / 8 - 1));
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {
+            const int row = row0 + RP16 * m;
+            r[m] = row < n ? *(const uint2*)(base.y + (long)row * CK + k0 + c) : make_uint2(0u, 0u);
+        }
+    }
+    template <int NM>
+    static __device__ __forceinline__ void load8_scale(rows8_t base, int n, int row_base, int tid, float (&s)[NM]) {
+        const int row0 = row_base + (tid >> SH16);
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {
+            const int row = row0 + RP16 * m;
+            s[m] = row < n ? base.s[row] : 0.f;
+        }
+    }
+    // e4m3 -> fp32 (the hardware conversion), times the row's power of two, to bf16, into the store() layout.
+    // Exact at every step: four significant bits, and the quantiser's exponent range keeps the product inside
+    // bf16's normal range, so the bits are those of bf16(float(y8) * s8) whatever the rounding mode
+    template <int NM>
+    static __device__ __forceinline__ void store8(unsigned char* tile, int tid, const uint2 (&r)[NM],
+                                                  const float (&s)[NM]) {
+        const int row0 = tid >> SH16, c = 8 * (tid & (BK / 8 - 1));
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {
+            const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[m].x, false);
+            const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[m].x, true);
+            const auto d = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[m].y, false);
+            const auto e = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[m].y, true);
+            uint4 o;
+            o.x = fpm::f2bf2(__fmul_rn(a[0], s[m]), __fmul_rn(a[1], s[m]));
+            o.y = fpm::f2bf2(__fmul_rn(b[0], s[m]), __fmul_rn(b[1], s[m]));
+            o.z = fpm::f2bf2(__fmul_rn(d[0], s[m]), __fmul_rn(d[1], s[m]));
+            o.w = fpm::f2bf2(__fmul_rn(e[0], s[m]), __fmul_rn(e[1], s[m]));
+            *(uint4*)(tile + (row0 + RP16 * m) * ROW + c * 2) = o;
+        }
     }
 };
 }  // namespace coarse

@@ -68,12 +68,13 @@ __device__ __forceinline__ Pos fresh_pos() {
     return Pos{t, t & 63, t & 15, (t >> 4) & 3};
 }
 
-// YT: the entry rows' type, float (rounded on the way into LDS) or bf16_t (rounded at enrolment); the
+// YT: the entry rows' type, float (rounded on the way into LDS), bf16_t (rounded at enrolment) or fp8_t
+// (e4m3 with a row scale, quantised at enrolment and dequantised, exactly, on the way into LDS); the
 // probe side and everything after the tile store are the same code, so are the bits.  PAIRS: the probe
 // of pair b comes from a second row store (a pair list: coarse_probe.h), looked up per pair of the
 // persistent walk; that lookup is the only code that differs
 template <typename YT, bool PAIRS>
-__global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restrict__ y,
+__global__ __launch_bounds__(WT) void coarse_score_wide_kernel(typename EntryRows<YT>::arg y,
                                                                const long* __restrict__ row_off,
                                                                const int* __restrict__ idx, int G, int B,
                                                                const float* __restrict__ ypq, int n0q,
@@ -112,8 +113,8 @@ __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restr
         // the Sinkhorn works on the transpose when n0 > n_g: its rows are the smaller side
         const bool tr = n0 > ng;
         const int R = tr ? ng : n0, C = tr ? n0 : ng;
-        constexpr bool F32 = sizeof(YT) == 4;
-        const YT* ye = y + r0 * WK;                      // the entry's rows
+        constexpr bool F32 = sizeof(YT) == 4, F8 = sizeof(YT) == 1;
+        const auto ye = y + r0 * WK;                   // the entry's rows
         const float* xa = nullptr;                       // rows side (MFMA A)
         const float* xb = nullptr;                       // columns side (MFMA B)
         if constexpr (F32) {
@@ -139,9 +140,15 @@ __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restr
             const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
             float4 ra[4], rb[4], sc;
             uint4 re[2];                                 // bf16 entry rows: ra is the probe's tile, re the entry's
+            uint2 r8[2];                                 // fp8 entry rows: r8 the entry's tile, s8 its rows' scales
+            float s8[2];
             if constexpr (F32) {
                 KTile::load(xa, R, 0, 0, tid, ra);
                 KTile::load(xb, C, 0, 0, tid, rb);
+            } else if constexpr (F8) {
+                KTile::load(yp, n0, 0, 0, tid, ra);
+                KTile::load8(ye, ng, 0, 0, tid, r8);
+                KTile::load8_scale(ye, ng, 0, tid, s8);
             } else {
                 KTile::load(yp, n0, 0, 0, tid, ra);
                 KTile::load16(ye, ng, 0, 0, tid, re);
@@ -153,6 +160,9 @@ __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restr
                 if constexpr (F32) {
                     KTile::store(At, tid, ra, tr ? one : sc);
                     KTile::store(Bt, tid, rb, tr ? sc : one);
+                } else if constexpr (F8) {
+                    KTile::store(tr ? Bt : At, tid, ra, sc);
+                    KTile::store8(tr ? At : Bt, tid, r8, s8);
                 } else {                                 // the entry is the MFMA's A when transposed, B otherwise
                     KTile::store(tr ? Bt : At, tid, ra, sc);
                     KTile::store16(tr ? At : Bt, tid, re);
@@ -163,6 +173,9 @@ __global__ __launch_bounds__(WT) void coarse_score_wide_kernel(const YT* __restr
                     if constexpr (F32) {
                         KTile::load(xa, R, 0, (kt + 1) * WBK, tid, ra);
                         KTile::load(xb, C, 0, (kt + 1) * WBK, tid, rb);
+                    } else if constexpr (F8) {
+                        KTile::load(yp, n0, 0, (kt + 1) * WBK, tid, ra);
+                        KTile::load8(ye, ng, 0, (kt + 1) * WBK, tid, r8);
                     } else {
                         KTile::load(yp, n0, 0, (kt + 1) * WBK, tid, ra);
                         KTile::load16(ye, ng, 0, (kt + 1) * WBK, tid, re);
@@ -384,8 +397,8 @@ struct Wide {
                                 *bound = "COARSE_WIDE_NMAX";
     static constexpr int nmax = FPM_COARSE_WIDE_NMAX;
     template <typename YT, bool PAIRS>
-    static int launch(const char* what, const YT* y, const long* row_off, const int* idx, int G, int B, const float* ypq,
-                      int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
+    static int launch(const char* what, typename EntryRows<YT>::host y, const long* row_off, const int* idx, int G,
+                      int B, const float* ypq, int n0q, const long* qrow_off, const int* qidx, int n0max, const float* coef, int iters, float tau,
                       float* score, void* ws, long ws_bytes, void* stream) {
         const long need = fpm_coarse_score_wide_ws_bytes(B);
         FPM_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
@@ -408,21 +421,21 @@ struct Wide {
 extern "C" int fpm_coarse_score_wide(const float* y, const long* row_off, const int* idx, int G, int B,
                                      const float* yp, int n0, const float* coef, int iters, float tau, float* score,
                                      void* ws, long ws_bytes, void* stream) {
-    return fpm::coarse_score_entry<Wide>("fpm_coarse_score_wide", y, row_off, idx, G, B, yp, n0, coef, iters, tau, score,
+    return fpm::coarse_score_entry<Wide, float>("fpm_coarse_score_wide", y, row_off, idx, G, B, yp, n0, coef, iters, tau, score,
                                          ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_score_wide_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                             const float* yp, int n0, const float* coef, int iters, float tau,
                                             float* score, void* ws, long ws_bytes, void* stream) {
-    return fpm::coarse_score_entry<Wide>("fpm_coarse_score_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0,
+    return fpm::coarse_score_entry<Wide, bf16_t>("fpm_coarse_score_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yp, n0,
                                          coef, iters, tau, score, ws, ws_bytes, stream);
 }
 
 extern "C" int fpm_coarse_pairs_wide(const float* y, const long* row_off, const int* idx, int G, int B, const float* yq,
                                      const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
                                      float tau, float* score, void* ws, long ws_bytes, void* stream) {
-    return fpm::coarse_pairs_entry<Wide>("fpm_coarse_pairs_wide", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef,
+    return fpm::coarse_pairs_entry<Wide, float>("fpm_coarse_pairs_wide", y, row_off, idx, G, B, yq, qrow_off, qidx, Q, coef,
                                          iters, tau, score, ws, ws_bytes, stream);
 }
 
@@ -430,6 +443,23 @@ extern "C" int fpm_coarse_pairs_wide_rows16(const void* y16, const long* row_off
                                             const float* yq, const long* qrow_off, const int* qidx, int Q,
                                             const float* coef, int iters, float tau, float* score, void* ws,
                                             long ws_bytes, void* stream) {
-    return fpm::coarse_pairs_entry<Wide>("fpm_coarse_pairs_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
+    return fpm::coarse_pairs_entry<Wide, bf16_t>("fpm_coarse_pairs_wide_rows16", (const bf16_t*)y16, row_off, idx, G, B, yq,
                                          qrow_off, qidx, Q, coef, iters, tau, score, ws, ws_bytes, stream);
+}
+
+extern "C" int fpm_coarse_score_wide_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G,
+                                           int B, const float* yp, int n0, const float* coef, int iters, float tau,
+                                           float* score, void* ws, long ws_bytes, void* stream) {
+    return fpm::coarse_score_entry<Wide, fp8_t>("fpm_coarse_score_wide_rows8", rows8_t{(const unsigned char*)y8, s8},
+                                                row_off, idx, G, B, yp, n0, coef, iters, tau, score, ws, ws_bytes,
+                                                stream);
+}
+
+extern "C" int fpm_coarse_pairs_wide_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G,
+                                           int B, const float* yq, const long* qrow_off, const int* qidx, int Q,
+                                           const float* coef, int iters, float tau, float* score, void* ws,
+                                           long ws_bytes, void* stream) {
+    return fpm::coarse_pairs_entry<Wide, fp8_t>("fpm_coarse_pairs_wide_rows8", rows8_t{(const unsigned char*)y8, s8},
+                                                row_off, idx, G, B, yq, qrow_off, qidx, Q, coef, iters, tau, score, ws,
+                                                ws_bytes, stream);
 }

@@ -22,7 +22,11 @@ rows, rounded once at enrolment (``y16``), serves the coarse kernels with the sa
 bytes ("f32+bf16": the copy beside the fp32 rows).  The exact forward needs fp32 rows only for the
 M <= 1024 shortlisted entries, so "bf16+host" keeps them in pinned host memory and ``fetch``es those M
 entries per query (``fpm_rows_fetch``): 1.5 KB per keypoint on the device, twice the gallery per GPU,
-and every output of ``identify(shortlist=M)`` the same bits as from the "f32" layout.
+and every output of ``identify(shortlist=M)`` the same bits as from the "f32" layout.  "fp8+host" holds the
+device rows as e4m3 bytes with one power-of-two fp32 scale per row (``y8``, ``s8``; ``ops.rows_quant8`` at
+enrolment): 772 B per keypoint.  The coarse operand is then b = bf16(float(y8) * s8), which is exact, so the coarse
+score is the bf16 kernels' on those rows (the _rows8 entry points); it differs from the other layouts' only in
+which entries a shortlist keeps, and every exact output of an entry is the same bits as from any layout.
 
 Probe sets (``Net.identify_many``, ``coarse_scores_many``, ``match_pairs``): the probes enrolled like a
 gallery, so that many probes are searched at once over (probe, entry) pair lists: the coarse kernels'
@@ -88,8 +92,13 @@ from .model import _CachedSide
 FORMAT = 1                    # a saved "f32" index; the other layouts write FORMAT_LAYOUTS
 FORMAT_LAYOUTS = 2
 FORMAT_TOMBSTONES = 3         # any layout, with the table ``removed`` (an index saved with removed slots)
+FORMAT_FP8 = 4                # the "fp8+host" layout: ``y8`` and ``s8`` for ``y16``; ``removed`` with tombstones
 SCORES = ("cls_prob", "cls_logits", "k_prob")
-LAYOUTS = ("f32", "f32+bf16", "bf16+host")
+LAYOUTS = ("f32", "f32+bf16", "bf16+host", "fp8+host")
+HOST_LAYOUTS = ("bf16+host", "fp8+host")      # the fp32 rows in (pinned) host memory: ``fetch``
+BF16_LAYOUTS = ("f32+bf16", "bf16+host")      # a bf16 copy of the rows on the device: ``y16``
+FP8_LAYOUT = "fp8+host"                       # e4m3 rows and their scales on the device: ``y8``, ``s8``
+ROW_BYTES_FP8 = C.NODE_FEATURE_DIM + 4        # device bytes per keypoint of the fp8 layout's rows
 ROW_BYTES = 4 * C.NODE_FEATURE_DIM
 # the fp32 rows one ``GalleryIndex.fetch`` stages on the device at most: those of the largest shortlist
 # the API allows (1.89 GB)
@@ -127,14 +136,16 @@ def _check_capacity(what, capacity, G, R, E=0):
 
 def _make_store(cap, layout, dev, has_P, has_subject):
     """The buffers of an index with capacity ``cap`` = (entries, rows, edges): the device arrays (in
-    "bf16+host" the fp32 rows pinned on the host), and the host tables.  Rows and edges are uninitialised,
+    "bf16+host" and "fp8+host" the fp32 rows pinned on the host), and the host tables.  Rows and edges are uninitialised,
     the small tables zero.  The public fields of the index are prefix views of these."""
     ents, rows, edges = cap
     D = C.NODE_FEATURE_DIM
     new = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)
     return dict(cap=tuple(cap),
-                y=_host_rows((rows, D), dev) if layout == "bf16+host" else new((rows, D), torch.float32),
-                y16=None if layout == "f32" else new((rows, D), torch.bfloat16),
+                y=_host_rows((rows, D), dev) if layout in HOST_LAYOUTS else new((rows, D), torch.float32),
+                y16=new((rows, D), torch.bfloat16) if layout in BF16_LAYOUTS else None,
+                y8=new((rows, D), torch.float8_e4m3fn) if layout == FP8_LAYOUT else None,
+                s8=new((rows,), torch.float32) if layout == FP8_LAYOUT else None,
                 P=new((rows, 2), torch.float32) if has_P else None,
                 src=new((edges,), torch.int32), dst=new((edges,), torch.int32), pseudo=new((edges, 2), torch.float32),
                 w=new((ents, C.GLOBAL_FEATURE_DIM), torch.float32),
@@ -157,13 +168,17 @@ class GalleryIndex:
     """Data of an enrolled gallery of G graphs (a container; ``Net.enroll`` fills it):
 
       y         (sum n, 768) fp32   SplineConv output rows, graph g at [row_off[g], row_off[g + 1]);
-                                    on the device, or ("bf16+host") in pinned host memory
+                                    on the device, or ("bf16+host", "fp8+host") in pinned host memory
       y16       (sum n, 768) bf16   device; the same rows rounded to nearest even (``ops.cast_bf16``),
-                                    what the coarse kernels read; None in the "f32" layout
+                                    what the coarse kernels read; None in the "f32" and "fp8+host" layouts
+      y8, s8    (sum n, 768) e4m3,  device, "fp8+host" only (else None): the rows quantised with one power-of-two
+                (sum n,) fp32       scale per row (``ops.rows_quant8``); the coarse operand is bf16(y8 * s8)
       layout    "f32"               y on the device (3 KB per keypoint), no y16
                 "f32+bf16"          y and y16 on the device (4.5 KB per keypoint)
                 "bf16+host"         y16 on the device (1.5 KB per keypoint), y on the host: the coarse
                                     pass reads y16, the exact forward ``fetch``es the rows it needs
+                "fp8+host"          y8 and s8 on the device (772 B per keypoint), y on the host: the coarse
+                                    pass reads y8 and s8, the exact forward ``fetch``es as above
       row_off   (G + 1,) int64      device (the index's device, whatever the layout); ``row_off_host``
                                     its host copy
       n         (G,) int32          keypoints per graph (host)
@@ -181,21 +196,30 @@ class GalleryIndex:
     """
 
     def __init__(self, y, row_off, n, src, dst, pseudo, edge_off, w, P, sc_mode, pack_gen, weights_id, y16=None,
-                 layout="f32", subject=None):
+                 layout="f32", subject=None, y8=None, s8=None):
         if sc_mode not in ("f32", "bf16"):
             raise FpmError("GalleryIndex: sc_mode must be 'f32' or 'bf16'")
         if layout not in LAYOUTS:
             raise FpmError("GalleryIndex: layout must be one of %s" % (LAYOUTS,))
-        if (y16 is None) != (layout == "f32"):
-            raise FpmError("GalleryIndex: layout %r %s" % (layout, "has no y16" if layout == "f32" else "needs y16"))
+        if (y16 is None) != (layout not in BF16_LAYOUTS):
+            raise FpmError("GalleryIndex: layout %r %s" % (layout, "needs y16" if y16 is None else "has no y16"))
+        if (y8 is None) != (layout != FP8_LAYOUT) or (s8 is None) != (layout != FP8_LAYOUT):
+            raise FpmError("GalleryIndex: layout %r %s" % (layout, "needs y8 and s8" if layout == FP8_LAYOUT else
+                                                           "has no y8 and no s8"))
+        if y8 is not None and (not isinstance(y8, torch.Tensor) or not isinstance(s8, torch.Tensor)
+                               or tuple(y8.shape) != tuple(y.shape) or y8.dtype != torch.float8_e4m3fn
+                               or tuple(s8.shape) != (y.shape[0],) or s8.dtype != torch.float32
+                               or y8.device != row_off.device or s8.device != row_off.device):
+            raise FpmError("GalleryIndex: inconsistent fields (y8 must be float8_e4m3fn of y's shape and s8 float32, one "
+                           "scale per row, both on the index device)")
         if y16 is not None and (not isinstance(y16, torch.Tensor) or tuple(y16.shape) != tuple(y.shape)
                                 or y16.dtype != torch.bfloat16 or y16.device != row_off.device):
             raise FpmError("GalleryIndex: inconsistent fields (y16 must be bfloat16 of y's shape on the index device)")
-        if layout == "bf16+host" and (y.is_cuda or (row_off.is_cuda and not y.is_pinned())):
-            raise FpmError("GalleryIndex: layout 'bf16+host' keeps y in host memory (pinned when the index is on a "
-                           "GPU)")
+        if layout in HOST_LAYOUTS and (y.is_cuda or (row_off.is_cuda and not y.is_pinned())):
+            raise FpmError("GalleryIndex: layout %r keeps y in host memory (pinned when the index is on a "
+                           "GPU)" % layout)
         self.y, self.src, self.dst, self.pseudo, self.w, self.P = y, src, dst, pseudo, w, P
-        self.y16, self.layout = y16, layout
+        self.y16, self.y8, self.s8, self.layout = y16, y8, s8, layout
         self._stage = None          # fetch: (sel, staging buffer, row offsets device / host) of the last selection
         self.row_off = row_off
         self.row_off_host = row_off.cpu()
@@ -231,19 +255,26 @@ class GalleryIndex:
 
     def nbytes(self):
         """Device bytes held: the rows (3 KB per keypoint in the "f32" layout, 4.5 KB in "f32+bf16",
-        1.5 KB in "bf16+host"), plus edges and global features."""
+        1.5 KB in "bf16+host", 772 B in "fp8+host"), plus edges and global features."""
         f = self._store or dict(row_off=self.row_off, src=self.src, dst=self.dst, pseudo=self.pseudo, w=self.w,
-                                P=self.P, y=self.y, y16=self.y16)
+                                P=self.P, y=self.y, y16=self.y16, y8=self.y8, s8=self.s8)
         ts = [f[k] for k in ("row_off", "src", "dst", "pseudo", "w")] + ([] if f["P"] is None else [f["P"]])
-        ts += ([] if self.layout == "bf16+host" else [f["y"]]) + ([] if f["y16"] is None else [f["y16"]])
+        ts += ([] if self.layout in HOST_LAYOUTS else [f["y"]]) + [f[k] for k in ("y16", "y8", "s8") if f[k] is not None]
         if self._groups is not None:
             ts += [self._groups[1][k] for k in ("labels_d", "off_d", "pos_d")]
         return sum(t.numel() * t.element_size() for t in ts)
 
     def host_nbytes(self):
-        """Host bytes held: the fp32 rows of the "bf16+host" layout (3 KB per keypoint), else 0."""
+        """Host bytes held: the fp32 rows of the "bf16+host" and "fp8+host" layouts (3 KB per keypoint), else 0."""
         y = self.y if self._store is None else self._store["y"]
-        return y.numel() * y.element_size() if self.layout == "bf16+host" else 0
+        return y.numel() * y.element_size() if self.layout in HOST_LAYOUTS else 0
+
+    def coarse_rows(self):
+        """What the coarse kernels read -> (rows, row_scale): the bf16 copy when the index keeps one, the e4m3
+        rows and their scales in "fp8+host", else the fp32 rows (``ops.coarse_score(rows, ..., row_scale=)``)."""
+        if self.y8 is not None:
+            return self.y8, self.s8
+        return (self.y if self.y16 is None else self.y16), None
 
     # ---- a mutable index: capacity, enrolment into it (Net.enroll_into), tombstones, compaction ----
     @property
@@ -300,6 +331,7 @@ class GalleryIndex:
         st = self._store
         st["row_off"][lo:G + 1].copy_(st["row_off_host"][lo:G + 1])
         self.y, self.y16 = st["y"][:R], None if st["y16"] is None else st["y16"][:R]
+        self.y8, self.s8 = (None, None) if st["y8"] is None else (st["y8"][:R], st["s8"][:R])
         self.P = None if st["P"] is None else st["P"][:R]
         self.src, self.dst, self.pseudo = st["src"][:E], st["dst"][:E], st["pseudo"][:E]
         self.w, self.row_off = st["w"][:G], st["row_off"][:G + 1]
@@ -316,7 +348,8 @@ class GalleryIndex:
                            st["pseudo"][:E], st["edge_off"][:G + 1], st["w"][:G],
                            None if st["P"] is None else st["P"][:R], sc_mode, pack_gen, weights_id,
                            y16=None if st["y16"] is None else st["y16"][:R], layout=layout,
-                           subject=None if sub is None else sub[:G])
+                           subject=None if sub is None else sub[:G], y8=None if st["y8"] is None else st["y8"][:R],
+                           s8=None if st["s8"] is None else st["s8"][:R])
         idx._store = st
         idx._commit(G, R, E, lo=G)
         idx.generation = 0
@@ -327,7 +360,7 @@ class GalleryIndex:
         ``keypoints`` rows and ``edges`` edges (default 6 per row: a planar triangulation has at most 6n - 12
         directed edges, which covers ``stg="tri"`` graphs; host-dict graphs with more pass ``edges``), so
         that ``Net.enroll_into`` can add entries without enrolling the gallery again.  In the "bf16+host"
-        layout the pinned host rows are allocated here, once, at capacity.  This index is untouched; to
+        and "fp8+host" layouts the pinned host rows are allocated here, once, at capacity.  This index is untouched; to
         grow a full index, reserve a bigger one: nothing is ever re-allocated under a live index."""
         G, R, E = self.used
         cap = _check_capacity("GalleryIndex.reserve", (entries, keypoints) if edges is None else
@@ -335,7 +368,7 @@ class GalleryIndex:
         dev = self.device
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
             st = _make_store(cap, self.layout, dev, self.P is not None, self.subject is not None)
-            for key in ("y", "y16", "P"):
+            for key in ("y", "y16", "y8", "s8", "P"):
                 if st[key] is not None:
                     st[key][:R].copy_(getattr(self, key))
             for key in ("src", "dst", "pseudo"):
@@ -353,7 +386,8 @@ class GalleryIndex:
     def _adopt(self):
         """The storage of an index that has none: its own tensors, full (capacity = used)."""
         if self._store is None:
-            self._store = dict(cap=self.used, y=self.y, y16=self.y16, P=self.P, src=self.src, dst=self.dst,
+            self._store = dict(cap=self.used, y=self.y, y16=self.y16, y8=self.y8, s8=self.s8, P=self.P, src=self.src,
+                               dst=self.dst,
                                pseudo=self.pseudo, w=self.w, row_off=self.row_off, n=self.n, edge_off=self.edge_off,
                                row_off_host=self.row_off_host, subject=self.subject)
         return self._store
@@ -399,7 +433,7 @@ class GalleryIndex:
             st["P"][R:R + Rn].copy_(P)
         for key, t in (("src", src), ("dst", dst), ("pseudo", pseudo)):
             st[key][E:E + En].copy_(t)
-        if self.layout == "bf16+host" and self.device.type == "cuda":
+        if self.layout in HOST_LAYOUTS and self.device.type == "cuda":
             torch.cuda.current_stream(self.device).synchronize()   # the host rows are complete before they are read
         st["n"][G:G + Gn] = n
         st["row_off_host"][G + 1:G + Gn + 1] = R + n.long().cumsum(0)
@@ -449,7 +483,8 @@ class GalleryIndex:
         device buffer reused by every such block).  No launch reads rows that it writes; ``ops.rows_move``
         checks that on the host each time.  ``last_compact`` counts the blocks by route.  The small arrays
         (P, edges, w, offsets, the host tables; 3 % of the bytes) are gathered out of place with torch
-        indexing and copied back over the prefix.  The host fp32 rows of "bf16+host" are moved by host
+        indexing and copied back over the prefix.  In "fp8+host" the e4m3 rows and their scales move as the
+        bf16 rows do (``ops.rows_move(src8=...)``).  The host fp32 rows of "bf16+host" / "fp8+host" are moved by host
         code after a device synchronise (kernels read that memory through its mapping): ascending, one
         copy per run of adjacent live entries, a run that lands on rows it still occupies in pieces of
         COMPACT_HOST_ROWS rows through a temporary."""
@@ -485,16 +520,26 @@ class GalleryIndex:
             blocks.append((a, L))
         st = self._adopt()
         dev = self.device
-        host_rows = self.layout == "bf16+host"
-        y32, y16 = None if host_rows else st["y"], st["y16"]
+        host_rows = self.layout in HOST_LAYOUTS
+        y32, y16, y8, s8 = None if host_rows else st["y"], st["y16"], st["y8"], st["s8"]
+        if y8 is not None:
+            # the fp8 layout's one row store on the device; (source, destination) -> the keywords of ops.rows_move
+            rows_kw = lambda s, d: dict(src8=y8 if s else g8, dst8=y8 if d else g8, srcs=s8 if s else gs,
+                                        dsts=s8 if d else gs)
+        else:
+            rows_kw = lambda s, d: dict(src32=y32 if s else s32, dst32=y32 if d else s32, src16=y16 if s else s16,
+                                        dst16=y16 if d else s16)
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
             if blocks:
                 stg = torch.cat([dst[a:b] - dst[a] for a, b in blocks])          # offsets into the stage
                 src_h, dst_h, cnt_h = src[first:].contiguous(), dst[first:].contiguous(), cnt[first:].contiguous()
                 src_d, dst_d, cnt_d, stg_d = src_h.to(dev), dst_h.to(dev), cnt_h.to(dev), stg.to(dev)
             # the stage, before the first launch: once rows have moved nothing may fail
-            s32 = s16 = None
+            s32 = s16 = g8 = gs = None
             if any(int(new_ro[b]) > int(src[a]) for a, b in blocks):
+                if y8 is not None:
+                    g8 = torch.empty(stage_rows, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float8_e4m3fn)
+                    gs = torch.empty(stage_rows, device=dev, dtype=torch.float32)
                 if y32 is not None:
                     s32 = torch.empty(stage_rows, C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
                 if y16 is not None:
@@ -505,15 +550,15 @@ class GalleryIndex:
                 tabs = (src_d[u:v], dst_d[u:v], stg_d[u:v], src_h[u:v], dst_h[u:v], stg[u:v])
                 self.last_compact["rows"] += int(cnt_h[u:v].sum())
                 if int(new_ro[b]) <= int(src[a]):
-                    ops.rows_move(tabs[0], tabs[1], cnt_d[u:v], src32=y32, dst32=y32, src16=y16, dst16=y16,
-                                  src_off_host=tabs[3], dst_off_host=tabs[4], **host)
+                    ops.rows_move(tabs[0], tabs[1], cnt_d[u:v], src_off_host=tabs[3], dst_off_host=tabs[4], **host,
+                                  **rows_kw(True, True))
                     self.last_compact["direct"] += 1
                     self.last_compact["launches"] += 1
                     continue
-                ops.rows_move(tabs[0], tabs[2], cnt_d[u:v], src32=y32, dst32=s32, src16=y16, dst16=s16,
-                              src_off_host=tabs[3], dst_off_host=tabs[5], **host)
-                ops.rows_move(tabs[2], tabs[1], cnt_d[u:v], src32=s32, dst32=y32, src16=s16, dst16=y16,
-                              src_off_host=tabs[5], dst_off_host=tabs[4], **host)
+                ops.rows_move(tabs[0], tabs[2], cnt_d[u:v], src_off_host=tabs[3], dst_off_host=tabs[5], **host,
+                              **rows_kw(True, False))
+                ops.rows_move(tabs[2], tabs[1], cnt_d[u:v], src_off_host=tabs[5], dst_off_host=tabs[4], **host,
+                              **rows_kw(False, True))
                 self.last_compact["staged"] += 1
                 self.last_compact["launches"] += 2
             if host_rows:
@@ -550,9 +595,10 @@ class GalleryIndex:
 
     def save(self, path):
         """``torch.save`` of a dict of tensors and scalars (no pickled code objects).  An "f32" index
-        writes format 1, as ever; the other layouts write format 2, with ``layout`` and ``y16``.  Of an
+        writes format 1, as ever; the bf16 layouts write format 2, with ``layout`` and ``y16``.  Of an
         index with capacity the used part is written; one with removed slots writes format 3, which adds
-        the table ``removed``."""
+        the table ``removed``.  "fp8+host" writes format 4: ``layout``, ``y8`` (as bytes: uint8) and ``s8`` in
+        ``y16``'s place, and ``removed`` when there are removed slots."""
         # a field of an index with storage is a view: a host view is copied, so that only its part is written
         host = (lambda t: t.cpu()) if self._store is None else (lambda t: t.cpu() if t.is_cuda else t.clone())
         d = dict(format=FORMAT, y=host(self.y), row_off=host(self.row_off_host), n=host(self.n), src=host(self.src),
@@ -560,12 +606,14 @@ class GalleryIndex:
                  sc_mode=self.sc_mode, pack_gen=self._pack_gen, weights_id=self.weights_id)
         if self.P is not None:
             d["P"] = host(self.P)
-        if self.layout != "f32":
+        if self.layout in BF16_LAYOUTS:
             d.update(format=FORMAT_LAYOUTS, layout=self.layout, y16=host(self.y16))
         if self.subject is not None:
             d["subject"] = host(self.subject)
         if self.tombstones:
             d.update(format=FORMAT_TOMBSTONES, layout=self.layout, removed=self.removed.clone())
+        if self.layout == FP8_LAYOUT:
+            d.update(format=FORMAT_FP8, layout=self.layout, y8=host(self.y8).view(torch.uint8), s8=host(self.s8))
         torch.save(d, path)
 
     @staticmethod
@@ -573,27 +621,34 @@ class GalleryIndex:
         """The index ``save`` wrote, on ``device``.  ``capacity``: (entries, keypoints[, edges]) -- the index
         is restored into storage of that size (as ``reserve`` makes it), without a second copy of it."""
         d = torch.load(path, map_location="cpu", weights_only=True)
-        if d.get("format") not in (FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES) or (
-                d["format"] == FORMAT_TOMBSTONES and not ("removed" in d and "layout" in d)):
-            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d, %d or %d"
-                           % (path, FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES))
+        if d.get("format") not in (FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8) or (
+                d["format"] == FORMAT_TOMBSTONES and not ("removed" in d and "layout" in d)) or (
+                d["format"] == FORMAT_FP8 and not (d.get("layout") == FP8_LAYOUT and "y8" in d and "s8" in d)) or (
+                d["format"] != FORMAT_FP8 and d.get("layout") == FP8_LAYOUT):
+            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d, %d, %d or %d"
+                           % (path, FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8))
         layout = d["layout"] if d["format"] != FORMAT else "f32"
+        if layout == FP8_LAYOUT:
+            d["y8"] = d["y8"].view(torch.float8_e4m3fn)
         if capacity is None:
             mv = lambda k: d[k].to(device)
-            if layout == "bf16+host":
+            if layout in HOST_LAYOUTS:
                 y = _host_rows(d["y"].shape, device).copy_(d["y"])
             else:
                 y = mv("y")
             idx = GalleryIndex(y, mv("row_off"), d["n"], mv("src"), mv("dst"), mv("pseudo"), d["edge_off"], mv("w"),
                                mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"],
-                               y16=mv("y16") if layout != "f32" else None, layout=layout, subject=d.get("subject"))
+                               y16=mv("y16") if layout in BF16_LAYOUTS else None, layout=layout,
+                               subject=d.get("subject"), y8=mv("y8") if layout == FP8_LAYOUT else None,
+                               s8=mv("s8") if layout == FP8_LAYOUT else None)
         else:
             G, R, E = int(d["n"].numel()), int(d["y"].shape[0]), int(d["src"].numel())
             cap = _check_capacity("GalleryIndex.load", capacity, G, R, E)
             dev = torch.device(device)
             with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
                 st = _make_store(cap, layout, dev, "P" in d, "subject" in d)
-                for key, k in (("y", R), ("y16", R), ("P", R), ("src", E), ("dst", E), ("pseudo", E), ("w", G),
+                for key, k in (("y", R), ("y16", R), ("y8", R), ("s8", R), ("P", R), ("src", E), ("dst", E),
+                               ("pseudo", E), ("w", G),
                                ("n", G), ("edge_off", G + 1), ("subject", G)):
                     if st[key] is not None:
                         st[key][:k].copy_(d[key])
@@ -648,13 +703,13 @@ class GalleryIndex:
         return t
 
     def fetch(self, sel):
-        """The fp32 rows of the entries ``sel`` (host int64, in that order) of a "bf16+host" index, copied
+        """The fp32 rows of the entries ``sel`` (host int64, in that order) of a "bf16+host" or "fp8+host" index, copied
         from the host into a device staging buffer (``ops.rows_fetch``: one kernel reads the pinned
         rows) -> (y_stage (sum of the selected n, 768) fp32 device, its row offsets (len(sel) + 1,)
         int64 on the device, the same on the host): entry sel[m] at rows [off[m], off[m + 1]).  The
         buffer is reused from call to call and grows as needed; a repeated selection is not copied
         again.  Selections over FETCH_MAX_BYTES of rows are refused."""
-        if self.layout != "bf16+host":
+        if self.layout not in HOST_LAYOUTS:
             raise FpmError("GalleryIndex.fetch: layout %r holds its fp32 rows on the device" % self.layout)
         sel = torch.as_tensor(sel, dtype=torch.int64).view(-1).cpu()
         if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= self.G:
@@ -666,7 +721,7 @@ class GalleryIndex:
         total = int(ng.sum())
         if total * ROW_BYTES > FETCH_MAX_BYTES:
             raise FpmError("identify: the %d selected entries' fp32 rows take %d bytes on the device, over "
-                           "FETCH_MAX_BYTES = %d; an index with its rows on the host (layout 'bf16+host') runs "
+                           "FETCH_MAX_BYTES = %d; an index with its rows on the host (layout 'bf16+host' or 'fp8+host') runs "
                            "the exact forward over a shortlist: pass shortlist=M, or a smaller select"
                            % (sel.numel(), total * ROW_BYTES, FETCH_MAX_BYTES))
         dev = self.device
@@ -686,10 +741,10 @@ class GalleryIndex:
 
     def slice(self, entries, device=None):
         """A new GalleryIndex holding the entries ``entries`` (host int64, ascending, no repeats) in that
-        order, on ``device`` (default: this index's): the rows (``y``, ``y16``, ``P``) and edges (``src``,
+        order, on ``device`` (default: this index's): the rows (``y``, ``y16``, ``y8``, ``s8``, ``P``) and edges (``src``,
         ``dst``, ``pseudo``) of those entries copied by their row and edge ranges, ``n``, ``w`` and ``subject``
         by entry, the offsets rebuilt; layout, ``sc_mode``, ``_pack_gen`` and ``weights_id`` kept.  A
-        "bf16+host" slice gets pinned host rows of its own.  Every field of the slice holds the parent's
+        "bf16+host" or "fp8+host" slice gets pinned host rows of its own.  Every field of the slice holds the parent's
         bytes for those entries (``ShardedGallery.split`` cuts an index into shards with it)."""
         ent = torch.as_tensor(entries)
         if ent.dtype != torch.int64 or ent.is_cuda or ent.dim() != 1 or ent.numel() == 0:
@@ -703,7 +758,7 @@ class GalleryIndex:
         edges, edge_off = _entry_ranges(self.edge_off, ent)
         rows_d, edges_d, ent_d = rows.to(src_dev), edges.to(src_dev), ent.to(src_dev)
         take = lambda t, at: t[at].to(dev)
-        if self.layout == "bf16+host":
+        if self.layout in HOST_LAYOUTS:
             y = _host_rows((int(rows.numel()), self.y.shape[1]), dev)
             torch.index_select(self.y, 0, rows, out=y)
         else:
@@ -712,7 +767,9 @@ class GalleryIndex:
                             take(self.pseudo, edges_d), edge_off, take(self.w, ent_d),
                             None if self.P is None else take(self.P, rows_d), self.sc_mode, self._pack_gen,
                             self.weights_id, y16=None if self.y16 is None else take(self.y16, rows_d),
-                            layout=self.layout, subject=None if self.subject is None else self.subject[ent])
+                            layout=self.layout, subject=None if self.subject is None else self.subject[ent],
+                            y8=None if self.y8 is None else take(self.y8, rows_d),
+                            s8=None if self.s8 is None else take(self.s8, rows_d))
 
     def _selection(self, select, pad_to=None):
         """Side 1 of a probe x gallery batch over the entries ``select`` (None: all), in that order,
@@ -835,17 +892,21 @@ def spline_weights_id(net):
 
 def _alloc_rows(layout, dev, rows):
     """The row buffers of a new index of exactly ``rows`` rows -> (y fp32 device or None, y16 or None, the
-    pinned host fp32 rows of "bf16+host" or None): what the enrolment loops write into."""
+    pinned host fp32 rows of "bf16+host" / "fp8+host" or None, y8 or None, s8 or None): what the enrolment loops
+    write into."""
     D = C.NODE_FEATURE_DIM
-    return (None if layout == "bf16+host" else torch.empty(rows, D, device=dev, dtype=torch.float32),
-            None if layout == "f32" else torch.empty(rows, D, device=dev, dtype=torch.bfloat16),
-            _host_rows((rows, D), dev) if layout == "bf16+host" else None)
+    fp8 = layout == FP8_LAYOUT
+    return (None if layout in HOST_LAYOUTS else torch.empty(rows, D, device=dev, dtype=torch.float32),
+            torch.empty(rows, D, device=dev, dtype=torch.bfloat16) if layout in BF16_LAYOUTS else None,
+            _host_rows((rows, D), dev) if layout in HOST_LAYOUTS else None,
+            torch.empty(rows, D, device=dev, dtype=torch.float8_e4m3fn) if fp8 else None,
+            torch.empty(rows, device=dev, dtype=torch.float32) if fp8 else None)
 
 
 def _store_rows(index):
-    """The same three of an index with capacity: its storage, which the loops write past ``used``."""
-    st, host = index._store, index.layout == "bf16+host"
-    return None if host else st["y"], st["y16"], st["y"] if host else None
+    """The same five of an index with capacity: its storage, which the loops write past ``used``."""
+    st, host = index._store, index.layout in HOST_LAYOUTS
+    return None if host else st["y"], st["y16"], st["y"] if host else None, st["y8"], st["s8"]
 
 
 def _edge_room(what, seen, room):
@@ -860,7 +921,7 @@ def _enroll_dicts(net, what, graphs, dev, sc_mode, batch, rows, r0, room=None):
     sub-batches of ``batch``, each sub-batch's ragged rows written from row ``r0`` on into ``rows``
     (``_alloc_rows`` / ``_store_rows``) -> the edges (graph-local src, dst, pseudo on the device, host counts
     per graph).  ``room``: the edges the index has room for (None: a new index)."""
-    y, y16, y_host = rows
+    y, y16, y_host, y8, s8 = rows
     wp = net.packed(dev)
     srcs, dsts, pss, cnts, seen = [], [], [], [], 0
     for g0 in range(0, len(graphs), max(1, int(batch))):
@@ -878,6 +939,8 @@ def _enroll_dicts(net, what, graphs, dev, sc_mode, batch, rows, r0, room=None):
         r1 = r0 + int(yr.shape[0])
         if y16 is not None:
             ops.cast_bf16(yr, out=y16[r0:r1])
+        if y8 is not None:
+            ops.rows_quant8(yr, y8[r0:r1], s8[r0:r1])
         if y_host is not None:
             y_host[r0:r1].copy_(yr, non_blocking=True)
         else:
@@ -915,8 +978,9 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
     """``Net.enroll``: the two SplineConv layers over ``graphs`` (dicts as ``fpm.synth.make_graph``
     returns: n, x, w, edge_index, pseudo, optionally P) in sub-batches of ``batch`` graphs -> GalleryIndex.
     ``layout`` (LAYOUTS): where the rows are kept.  The bf16 copy is rounded per sub-batch on the device
-    (``ops.cast_bf16``: the coarse kernels' own rounding); for "bf16+host" each sub-batch's fp32 rows go
-    straight to the pinned host tensor, so the device holds the bf16 rows plus one sub-batch at most.
+    (``ops.cast_bf16``: the coarse kernels' own rounding), the fp8 rows and their scales quantised per sub-batch
+    (``ops.rows_quant8``); for "bf16+host" and "fp8+host" each sub-batch's fp32 rows go straight to the pinned
+    host tensor, so the device holds the bf16 or fp8 rows plus one sub-batch at most.
     ``subjects``: one integer label >= 0 per graph (``GalleryIndex.subject``), checked before any GPU work;
     every other field of the index is the same with or without it.  ``capacity``: (entries, keypoints[,
     edges]), the storage to enrol into (``GalleryIndex.reserve``'s sizes), for an index that will grow."""
@@ -935,7 +999,7 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
         index.generation, index._pack_gen = 0, net._pack_gen    # a new index: as the constructor call below records it
         return index
     with torch.cuda.device(dev):
-        y, y16, y_host = rows = _alloc_rows(layout, dev, total)
+        y, y16, y_host, y8, s8 = rows = _alloc_rows(layout, dev, total)
         src, dst, ps, cnt = _enroll_dicts(net, "enroll", graphs, dev, sc_mode, batch, rows, 0)
     n_all, w, P = _dict_tables(graphs, dev)
     row_off = torch.cat([torch.zeros(1, dtype=torch.int64), n_all.long().cumsum(0)])
@@ -943,7 +1007,7 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
     if y_host is not None:
         torch.cuda.current_stream(dev).synchronize()       # the host rows are complete before they are read
     return GalleryIndex(y if y_host is None else y_host, row_off.to(dev), n_all, src, dst, ps, edge_off, w, P, sc_mode,
-                        net._pack_gen, spline_weights_id(net), y16=y16, layout=layout, subject=subjects)
+                        net._pack_gen, spline_weights_id(net), y16=y16, layout=layout, subject=subjects, y8=y8, s8=s8)
 
 
 def _check_into(net, index, what):
@@ -1031,7 +1095,8 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
     the features of graphs [g0, g1) on the device, (x (g1 - g0, >= m, 768) fp32, w (g1 - g0, 512) fp32).  Per
     sub-batch: trim to its own largest count m (the shapes ``enroll`` runs at), the graphs on the device
     (``graphs.build_graph_batch``), the two SplineConv layers as ``enroll`` calls them, and one
-    ``ops.rows_pack`` from the padded output into the index's rows, allocated once before the loop (a new
+    ``ops.rows_pack`` from the padded output into the index's rows (and, "fp8+host", one ``ops.rows_quant8`` of
+    the packed rows), allocated once before the loop (a new
     index) or reserved (``into``: the rows past ``used``; the edge count is known only per sub-batch, so the
     index changes at the end, in ``_finish_append``)."""
     from . import graphs
@@ -1050,7 +1115,7 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
     with torch.cuda.device(dev):
         row_off = row_off_h.to(dev)
         n_d = n_h.to(torch.int32).to(dev)
-        y, y16, y_host = _alloc_rows(layout, dev, total) if into is None else _store_rows(into)
+        y, y16, y_host, y8, s8 = _alloc_rows(layout, dev, total) if into is None else _store_rows(into)
         stage = None
         if y_host is not None:
             # one sub-batch of fp32 rows on the device, reused: the copies to the host are ordered on the stream
@@ -1077,6 +1142,8 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
             ops.rows_pack(yb, nv, m, row_off[g0:g1 + 1] - r0, out32=stage if y is None else y[base + r0:base + r1],
                           out16=None if y16 is None else y16[base + r0:base + r1], n_host=nsub,
                           out_off_host=row_off_h[g0:g1 + 1] - r0)
+            if y8 is not None:
+                ops.rows_quant8(stage[:r1 - r0], y8[base + r0:base + r1], s8[base + r0:base + r1])
             if y_host is not None:
                 y_host[base + r0:base + r1].copy_(stage[:r1 - r0], non_blocking=True)
             srcs.append(gb.src % m)                          # edges back to graph-local ids
@@ -1098,7 +1165,7 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
             torch.cuda.current_stream(dev).synchronize()   # the host rows are complete before they are read
         return GalleryIndex(y if y_host is None else y_host, row_off, n_h.to(torch.int32), torch.cat(srcs),
                             torch.cat(dsts), torch.cat(pss), edge_off, w_all, Pr, sc_mode, net._pack_gen,
-                            spline_weights_id(net), y16=y16, layout=layout, subject=subjects)
+                            spline_weights_id(net), y16=y16, layout=layout, subject=subjects, y8=y8, s8=s8)
 
 
 def _keypoint_feats(x, w, dev):
@@ -1240,7 +1307,7 @@ def probe_batch(probe, index, select=None, pad_to=None):
     bt = _CachedBatch(B, np.full(B, n0, np.int32), f["n"], [x0, x0.new_empty(0, C.NODE_FEATURE_DIM)], [w0, f["w"]],
                       [src0, f["src"]], [dst0, f["dst"]], [ps0, f["pseudo"]], dev, nmax=[n0, f["nmax"]],
                       edge_off=[eo0, f["edge_off"]], shared0=True)
-    if index.layout == "bf16+host":
+    if index.layout in HOST_LAYOUTS:
         # the selected entries' fp32 rows, staged on the device in selection order: pair b reads staged
         # entry b (f["idx"], top_idx and short_idx keep speaking gallery entry numbers)
         ys, off_d, off_h = index.fetch(sel)
@@ -1399,8 +1466,9 @@ def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk, coarse="fused"):
     ps = _ProbeSide(probe, index)
     yp = net._probe_rows(wp, ps)
     sel32 = sel.to(torch.int32)
-    # the bf16 copy of the rows when the index keeps one: half the bytes, the same operands
-    rows = index.y if index.y16 is None else index.y16
+    # the bf16 copy of the rows when the index keeps one: half the bytes, the same operands; the fp8 rows and
+    # their scales of an "fp8+host" index
+    rows, row_scale = index.coarse_rows()
     B = int(sel.numel())
     step = max(1, int(chunk))
     coef = torch.empty(min(B, step), C.NODE_FEATURE_DIM, device=index.device, dtype=torch.float32)
@@ -1410,7 +1478,7 @@ def _coarse_one(net, wp, probe, index, sel, sel_d, out, chunk, coarse="fused"):
 
         def launch(kernel, pos, pos_d, cf, dst):
             ops._coarse_score_op(kernel, rows, index.row_off, sel_d[b0:b1][pos_d].contiguous(), yp, cf, C.SK_ITER_NUM,
-                                 net.tau, dst, sel32[b0:b1][pos], index.row_off_host, None)
+                                 net.tau, dst, sel32[b0:b1][pos], index.row_off_host, None, row_scale)
 
         cf = _coef_rows(wp, w0[:b1 - b0], index.w[sel_d[b0:b1].long()], coef)
         _launch_by_route(rt[b0:b1], cf, out[b0:b1], launch)
@@ -1731,9 +1799,9 @@ def _check_probe_set(probes, index, what):
     if not isinstance(probes, GalleryIndex):
         raise FpmError("%s: probes must be a probe set: a GalleryIndex enrolled from the probe graphs (Net.enroll)"
                        % what)
-    if probes.layout == "bf16+host":
-        raise FpmError("%s: the probe set's layout is 'bf16+host'; a probe set keeps its fp32 rows on the device "
-                       "(layout 'f32' or 'f32+bf16')" % what)
+    if probes.layout in HOST_LAYOUTS:
+        raise FpmError("%s: the probe set's layout is %r; a probe set keeps its fp32 rows on the device "
+                       "(layout 'f32' or 'f32+bf16')" % (what, probes.layout))
     if probes.device != index.device:
         raise FpmError("%s: the probe set is on device %s, the gallery on %s" % (what, probes.device, index.device))
     if probes.sc_mode != index.sc_mode:
@@ -1760,7 +1828,7 @@ def _check_many(net, probes, index, what):
 
 def pair_batch(probes, index, pairs):
     """The batch of the pair list ``pairs`` ((B, 2) host int64: probe number, entry number, both in
-    range) over a probe set and a gallery index -> _CachedBatch.  On a "bf16+host" gallery the distinct
+    range) over a probe set and a gallery index -> _CachedBatch.  On a "bf16+host" or "fp8+host" gallery the distinct
     entries' fp32 rows are fetched and the pairs renumbered to the staging buffer."""
     dev = index.device
     q, g = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
@@ -1771,7 +1839,7 @@ def pair_batch(probes, index, pairs):
                       [f0["dst"], f1["dst"]], [f0["pseudo"], f1["pseudo"]], dev, nmax=[f0["nmax"], f1["nmax"]],
                       edge_off=[f0["edge_off"], f1["edge_off"]], shared0=False)
     c0 = _CachedSide(probes.y, probes.row_off, probes.row_off_host, f0["idx"], f0["idx_host"])
-    if index.layout == "bf16+host":
+    if index.layout in HOST_LAYOUTS:
         uniq, inv = torch.unique(g, return_inverse=True)
         ys, off_d, off_h = index.fetch(uniq)
         inv32 = inv.to(torch.int32).contiguous()
@@ -1828,7 +1896,7 @@ def coarse_scores_many(net, probes, index, probe_select=None, select=None, coars
     total = Qs * Gs
     out = torch.empty(Qs, Gs, device=dev, dtype=torch.float32)
     flat = out.view(-1)                      # pair (i, j) at i * Gs + j: a launch's pairs are one slice of it
-    rows = index.y if index.y16 is None else index.y16
+    rows, row_scale = index.coarse_rows()
     step = max(1, int(COARSE_PAIRS_CHUNK))
     coef = torch.empty(min(total, step), C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
 
@@ -1846,7 +1914,8 @@ def coarse_scores_many(net, probes, index, probe_select=None, select=None, coars
                 qk, gk = q32[pos].contiguous(), g32[pos].contiguous()
                 ops.coarse_pairs(rows, index.row_off, gk.to(dev), probes.y, probes.row_off, qk.to(dev), cf,
                                  kernel=kernel, iters=C.SK_ITER_NUM, tau=net.tau, out=dst, gidx_host=gk,
-                                 qidx_host=qk, row_off_host=index.row_off_host, qrow_off_host=probes.row_off_host)
+                                 qidx_host=qk, row_off_host=index.row_off_host, qrow_off_host=probes.row_off_host,
+                                 row_scale=row_scale)
 
             _launch_by_route(rt, cf, dst, launch)
             if where is not None:

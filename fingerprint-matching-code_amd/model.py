@@ -1481,7 +1481,12 @@ class Net(nn.Module):
         the fp32 rows in pinned host memory (3 KB per keypoint of host RAM), written sub-batch by
         sub-batch, so the device never holds the whole fp32 gallery; the exact forward copies the
         rows of the entries it runs over to the device per query.  Every output of ``identify`` and
-        ``coarse_scores`` is the same bits whatever the layout.
+        ``coarse_scores`` is the same bits in these three layouts.
+        "fp8+host" (opt-in, denser still): the device rows as e4m3 bytes with one power-of-two fp32 scale
+        per row (772 B per keypoint; ``ops.rows_quant8`` per sub-batch), the fp32 rows on the host as in
+        "bf16+host".  The coarse pass scores with the dequantised rows, so its scores, and with them which
+        entries a shortlist keeps, differ slightly from the other layouts'; the exact forward is untouched,
+        so every exact output of an entry is the same bits as from any layout.
 
         ``subjects``: one integer label >= 0 per graph, the subject (finger) each impression belongs to;
         kept on the index (``GalleryIndex.subject``, ``set_subjects`` relabels) for
@@ -1609,6 +1614,9 @@ class Net(nn.Module):
         memory into a reused staging buffer (``GalleryIndex.fetch``): the same outputs bit for bit.
         ``shortlist=M`` is the intended use there; without one the selection's rows must fit
         ``gallery.FETCH_MAX_BYTES`` (1.89 GB, the largest shortlist's), larger ones are refused.
+        An "fp8+host" index is queried the same way; its coarse pass reads the e4m3 rows and their
+        scales, so ``coarse_all`` and the shortlist's membership are that format's, and the outputs
+        of the exact forward for an entry are the other layouts' bits.
 
         ``by="subject"`` (an index with subject labels: ``enroll(subjects=...)``) ranks subjects, not
         entries; ``by=None`` (the default) is everything above, unchanged.  The exact forward runs over

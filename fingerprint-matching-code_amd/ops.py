@@ -4,7 +4,8 @@ Every op takes device tensors, checks shapes/dtypes on the host, and launches on
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
 no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``topk_merge``,
 ``group_scores``, ``group_topr``, ``cohort_decide``, ``coarse_score`` / ``coarse_pairs``, ``rows_fetch``,
-``rows_pack`` and ``rows_move`` alone keep a plain-torch host path for CPU tensors: the statements of the ordering and of the merge of
+``rows_pack``, ``rows_move`` and ``rows_quant8`` alone keep a plain-torch host path for CPU tensors: the statements
+of the ordering and of the merge of
 sorted lists, of the group fusions, of the cohort statistics, of the coarse score and of the ragged copies, which the
 tests hold the kernels to).
 """
@@ -496,12 +497,14 @@ def _ranges_meet(a0, a1, b0, b1):
 
 
 def rows_move(src_off, dst_off, cnt, src32=None, dst32=None, src16=None, dst16=None, src_off_host=None,
-              dst_off_host=None, cnt_host=None):
+              dst_off_host=None, cnt_host=None, src8=None, dst8=None, srcs=None, dsts=None):
     """Ragged segment copy (fpm_rows_move): segment k goes from rows [src_off[k], src_off[k] + cnt[k]) of the
     source to rows [dst_off[k], dst_off[k] + cnt[k]) of the destination (int64 [K] each, K <= 65535) -- the
     fp32 rows ``src32`` -> ``dst32``, the bf16 rows ``src16`` -> ``dst16`` (as bits: nothing is rounded), or
     both pairs from the one offset table, in one launch -> (dst32, dst16).  Rows outside the destination
-    ranges are not written.
+    ranges are not written.  The rows of an fp8 index (fpm_rows_move8): ``src8`` -> ``dst8`` ((rows, 768)
+    float8_e4m3fn, as bytes) with their scales ``srcs`` -> ``dsts`` ((rows,) fp32), all four and no other rows
+    -> (dst8, dsts).
 
     Everything lives on one device.  Checked on the host before anything is launched: dtypes, contiguity,
     devices, every range inside its tensor, destination ranges that do not meet each other, and -- a pair's
@@ -515,20 +518,32 @@ def rows_move(src_off, dst_off, cnt, src32=None, dst32=None, src16=None, dst16=N
                                        ("cnt", cnt, torch.int64)))
     if (src32 is None) != (dst32 is None) or (src16 is None) != (dst16 is None):
         raise _lib.FpmError("rows_move: src32 goes with dst32, src16 with dst16")
-    if src32 is None and src16 is None:
+    fp8 = any(t is not None for t in (src8, dst8, srcs, dsts))
+    if fp8 and (any(t is None for t in (src8, dst8, srcs, dsts)) or src32 is not None or src16 is not None):
+        raise _lib.FpmError("rows_move: the fp8 rows go as src8, dst8, srcs and dsts together, without other rows")
+    if src32 is None and src16 is None and not fp8:
         raise _lib.FpmError("rows_move: give the fp32 rows (src32, dst32), the bf16 rows (src16, dst16) or both")
-    pairs = [(s, d, dt) for s, d, dt in ((src32, dst32, torch.float32), (src16, dst16, torch.bfloat16))
-             if s is not None]
+    pairs = [(s, d, dt) for s, d, dt in ((src32, dst32, torch.float32), (src16, dst16, torch.bfloat16),
+                                         (src8, dst8, torch.float8_e4m3fn)) if s is not None]
     for s, d, dt in pairs:
         for name, t in (("src", s), ("dst", d)):
-            name += "32" if dt == torch.float32 else "16"
+            name += {torch.float32: "32", torch.bfloat16: "16", torch.float8_e4m3fn: "8"}[dt]
             if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 768 \
                     or not t.is_contiguous():
                 raise _lib.FpmError("rows_move: %s must be contiguous %s rows of 768 channels"
-                                    % (name, "bf16" if dt == torch.bfloat16 else "fp32"))
+                                    % (name, {torch.float32: "fp32", torch.bfloat16: "bf16",
+                                              torch.float8_e4m3fn: "float8_e4m3fn"}[dt]))
+    if fp8:
+        for name, t, rows in (("srcs", srcs, src8), ("dsts", dsts, dst8)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() \
+                    or t.numel() != rows.shape[0]:
+                raise _lib.FpmError("rows_move: %s must be a contiguous fp32 tensor of one scale per row of its rows"
+                                    % name)
+        pairs.append((srcs, dsts, None))                     # the scales move with their rows: the same checks
     dev = pairs[0][1].device
     for name, t in (("src_off", src_off), ("dst_off", dst_off), ("cnt", cnt), ("src32", src32), ("dst32", dst32),
-                    ("src16", src16), ("dst16", dst16)):
+                    ("src16", src16), ("dst16", dst16), ("src8", src8), ("dst8", dst8), ("srcs", srcs),
+                    ("dsts", dsts)):
         if t is not None and t.device != dev:
             raise _lib.FpmError("rows_move: %s is on %s, the destination on %s" % (name, t.device, dev))
     K = int(cnt.numel())
@@ -573,11 +588,76 @@ def rows_move(src_off, dst_off, cnt, src32=None, dst32=None, src16=None, dst16=N
             rs, rd = at(s0), at(d0)
             for s, d, _ in pairs:
                 d[rd] = s[rs]                                # the right side is gathered before anything is written
-        return dst32, dst16
+        return (dst8, dsts) if fp8 else (dst32, dst16)
+    if fp8:
+        if total:
+            _lib.call("fpm_rows_move8", _p(src8), _p(srcs), src_rows, _p(src_off), _p(dst_off), _p(cnt), K,
+                      int(c.max()), _p(dst8), _p(dsts), dst_rows, _stream(dst8))
+        return dst8, dsts
     if total:
         _lib.call("fpm_rows_move", _p(src32), _p(src16), src_rows, _p(src_off), _p(dst_off), _p(cnt), K, int(c.max()),
                   _p(dst32), _p(dst16), dst_rows, _stream(pairs[0][1]))
     return dst32, dst16
+
+
+QUANT8_MAX = 448.0             # the largest e4m3fn value
+QUANT8_EMAX = 110              # |e| of a row scale 2^e at most: float(y8) * 2^e stays a normal bf16
+
+
+def _quant8_host(y):
+    """The definition of the fp8 row format in plain torch -> (y8 float8_e4m3fn, s8 fp32); see ``rows_quant8``."""
+    amax = y.abs().amax(dim=1) if y.shape[0] else y.new_zeros(0)
+    m, x = torch.frexp(amax)                                 # amax = m 2^x, 0.5 <= m < 1;  448 = 0.875 x 2^9
+    e = torch.where(amax == 0, torch.zeros_like(x), x - 9 + (m > 0.875).to(x.dtype)).clamp(-QUANT8_EMAX, QUANT8_EMAX)
+    one = torch.ones_like(amax)
+    y8 = (y * torch.ldexp(one, -e)[:, None]).clamp(-QUANT8_MAX, QUANT8_MAX).to(torch.float8_e4m3fn)
+    return y8, torch.ldexp(one, e)
+
+
+def rows_dequant8(y8, s8):
+    """The coarse operand of fp8 rows, (y8 * s8[:, None]) as bf16: exact (four significant bits, a power-of-two
+    scale, a normal bf16 result), so no rounding happens here."""
+    return (y8.to(torch.float32) * s8[:, None]).to(torch.bfloat16)
+
+
+def rows_quant8(y, y8=None, s8=None):
+    """Index rows to fp8 with a power-of-two scale per row (fpm_rows_quant8) -> (y8, s8): for a row of
+    ``y`` ((rows, 768) fp32), amax = max |y[r]|; e = 0 if amax == 0, else with (m, x) = frexp(amax),
+    e = x - 9 + (m > 0.875), the smallest e with amax <= 448 * 2^e, clamped to [-QUANT8_EMAX, QUANT8_EMAX];
+    ``s8[r]`` = 2^e (fp32) and ``y8[r]`` = float8_e4m3fn(clamp(y[r] * 2^-e, -448, 448)), round to nearest even
+    (the OCP encoding, torch's ``.to(torch.float8_e4m3fn)``).  The coarse operand of such a row,
+    bf16(float(y8) * s8) (``rows_dequant8``), is exact.  Non-finite rows are the caller's error.
+
+    Everything lives on one device.  Checked on the host before anything is launched: dtypes, contiguity,
+    devices, sizes and 16-byte alignment.  ``rows`` = 0 launches nothing.  CPU tensors take the torch
+    statement of the definition."""
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != 768 \
+            or not y.is_contiguous():
+        raise _lib.FpmError("rows_quant8: y must be contiguous fp32 rows of 768 channels")
+    rows = int(y.shape[0])
+    if y8 is None:
+        y8 = torch.empty(rows, 768, device=y.device, dtype=torch.float8_e4m3fn)
+    if s8 is None:
+        s8 = torch.empty(rows, device=y.device, dtype=torch.float32)
+    if not isinstance(y8, torch.Tensor) or y8.dtype != torch.float8_e4m3fn or tuple(y8.shape) != (rows, 768) \
+            or not y8.is_contiguous():
+        raise _lib.FpmError("rows_quant8: y8 must be contiguous float8_e4m3fn rows of y's shape (%d, 768)" % rows)
+    if not isinstance(s8, torch.Tensor) or s8.dtype != torch.float32 or tuple(s8.shape) != (rows,) \
+            or not s8.is_contiguous():
+        raise _lib.FpmError("rows_quant8: s8 must be a contiguous fp32 tensor of %d row scales" % rows)
+    for name, t in (("y8", y8), ("s8", s8)):
+        if t.device != y.device:
+            raise _lib.FpmError("rows_quant8: %s is on %s, y on %s" % (name, t.device, y.device))
+    if rows and (y.data_ptr() | y8.data_ptr()) & 15:
+        raise _lib.FpmError("rows_quant8: y and y8 must be 16-byte aligned")
+    if not y.is_cuda:
+        q, sc = _quant8_host(y)
+        y8.copy_(q)
+        s8.copy_(sc)
+        return y8, s8
+    if rows:
+        _lib.call("fpm_rows_quant8", _p(y), rows, _p(y8), _p(s8), _stream(y))
+    return y8, s8
 
 
 def rank_key(scores, ids=None):
@@ -1109,15 +1189,17 @@ COARSE_KERNELS = tuple(_COARSE_KERNELS)
 
 def _coarse_call(kernel, pairs, y, args, B, n0max, ngmax):
     """Launch ``kernel``'s one-probe or pair-list (``pairs``) entry point for the index rows ``y`` (fp32, or
-    their bf16 copy: the _rows16 symbols) with ``args``, its workspace (sized from the launch's largest probe
+    their bf16 copy: the _rows16 symbols, or their fp8 form: the _rows8 symbols, whose ``args`` begin with
+    the rows and their scales) with ``args``, its workspace (sized from the launch's largest probe
     and largest entry, allocated here on the caller's stream) and the stream."""
     one, many, _, _, nws = _COARSE_KERNELS[kernel]
+    rows = {torch.float32: "", torch.bfloat16: "_rows16", torch.float8_e4m3fn: "_rows8"}[y.dtype]
     ws = ()
     if nws:
         wsb = int(getattr(_lib.load(), one + "_ws_bytes")(*(B, n0max, ngmax)[:nws]))
         buf = torch.empty(wsb, device=y.device, dtype=torch.uint8)
         ws = (_p(buf), wsb)
-    _lib.call((many if pairs else one) + ("_rows16" if y.dtype == torch.bfloat16 else ""), *args, *ws, _stream(y))
+    _lib.call((many if pairs else one) + rows, *args, *ws, _stream(y))
 
 
 # The checks that ``coarse_score*``, ``coarse_pairs`` and the ``rows_*`` wrappers make alike; ``op`` names the
@@ -1132,11 +1214,24 @@ def _check_index_tensors(op, named):
             raise _lib.FpmError("%s: %s must be a contiguous 1-d tensor" % (op, name))
 
 
-def _check_coarse_rows(op, y, named):
-    # y: the index's fp32 rows, or their bf16 copy (an index's y16: the rounding already done)
-    if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.bfloat16) or y.dim() != 2 \
-            or y.shape[1] != 768 or not y.is_contiguous():
-        raise _lib.FpmError("%s: y must be contiguous fp32 or bf16 rows of 768 channels" % op)
+def _check_coarse_rows(op, y, named, row_scale=None):
+    # y: the index's fp32 rows, their bf16 copy (an index's y16: the rounding already done) or their fp8 form
+    # with ``row_scale`` (an index's y8 and s8: ``rows_quant8``)
+    if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.bfloat16, torch.float8_e4m3fn) \
+            or y.dim() != 2 or y.shape[1] != 768 or not y.is_contiguous():
+        raise _lib.FpmError("%s: y must be contiguous fp32 or bf16 rows of 768 channels (or float8_e4m3fn rows with "
+                            "row_scale=)" % op)
+    if (y.dtype == torch.float8_e4m3fn) != (row_scale is not None):
+        raise _lib.FpmError("%s: float8_e4m3fn rows y go with their scales row_scale=, other rows without" % op)
+    if row_scale is not None:
+        if not isinstance(row_scale, torch.Tensor) or row_scale.dtype != torch.float32:
+            raise _lib.FpmError("%s: row_scale must be a float32 tensor (got %s)"
+                                % (op, getattr(row_scale, "dtype", type(row_scale).__name__)))
+        if row_scale.dim() != 1 or not row_scale.is_contiguous() or row_scale.numel() != y.shape[0]:
+            raise _lib.FpmError("%s: row_scale must be a contiguous 1-d tensor of one scale per row of y (%d)"
+                                % (op, y.shape[0]))
+        if row_scale.device != y.device:
+            raise _lib.FpmError("%s: row_scale is on %s, y on %s" % (op, row_scale.device, y.device))
     for name, t in named:
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
                 or not t.is_contiguous():
@@ -1172,6 +1267,11 @@ def _host_dtype(op, dtype):
     return dtype
 
 
+def _scale_arg(row_scale):
+    """The _rows8 entry points' second argument, after the rows."""
+    return () if row_scale is None else (_p(row_scale),)
+
+
 def _coarse_out(op, y, B, out, dtype, res=None):
     """The (B,) result: ``res`` (the host statement's, CPU tensors) copied to ``out`` if there is one; else
     ``out``, checked or allocated, for the kernel to fill."""
@@ -1190,14 +1290,15 @@ def _coarse_out(op, y, B, out, dtype, res=None):
     return out
 
 
-def _coarse_score_op(kernel, y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype):
+def _coarse_score_op(kernel, y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype,
+                     row_scale=None):
     """``coarse_score``, ``coarse_score_wide`` and ``coarse_score_stream``: the host-side checks, then
     ``kernel``'s one-probe entry point (``_COARSE_KERNELS``; its symbol without "fpm_" names the operation
     in every message)."""
     sym, _, bound, nmax, _ = _COARSE_KERNELS[kernel]
     op = sym[len("fpm_"):]
     _check_index_tensors(op, (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)))
-    _check_coarse_rows(op, y, (("yp", yp), ("coef", coef)))
+    _check_coarse_rows(op, y, (("yp", yp), ("coef", coef)), row_scale)
     _check_on_device_of(op, y, (("row_off", row_off), ("idx", idx), ("yp", yp), ("coef", coef), ("out", out)))
     G, B, n0 = int(row_off.numel()) - 1, int(idx.numel()), int(yp.shape[0])
     if G < 1:
@@ -1220,16 +1321,18 @@ def _coarse_score_op(kernel, y, row_off, idx, yp, coef, iters, tau, out, idx_hos
     iters, tau = _check_iters_tau(op, iters, tau)
     if not y.is_cuda:
         dtype = _host_dtype(op, dtype)
-        return _coarse_out(op, y, B, out, dtype, _coarse_score_host(y, oh, ih, yp, coef, iters, tau, dtype))
+        yh = y if row_scale is None else rows_dequant8(y, row_scale)
+        return _coarse_out(op, y, B, out, dtype, _coarse_score_host(yh, oh, ih, yp, coef, iters, tau, dtype))
     out = _coarse_out(op, y, B, out, dtype)
     if B:
-        _coarse_call(kernel, False, y, (_p(y), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef), iters, tau, _p(out)),
+        _coarse_call(kernel, False, y, (_p(y), *_scale_arg(row_scale), _p(row_off), _p(idx), G, B, _p(yp), n0, _p(coef),
+                                        iters, tau, _p(out)),
                      B, n0, int(ng.max()))
     return out
 
 
 def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
-                 dtype=None):
+                 dtype=None, row_scale=None):
     """Coarse 1:N score of one probe against gallery entries idx[b] of a ragged index
     (fpm_coarse_score) -> (B,) fp32:
 
@@ -1239,7 +1342,10 @@ def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_ho
     y (sum n_g, 768) fp32 with row_off int64 [G + 1] and idx int32 [B] as ``rows_gather_scale`` takes
     them, or the same rows as bf16 (``cast_bf16(y)``, an index's ``y16``: the kernel's bf16
     instantiation, fpm_coarse_score_rows16, copies the entry's tile as it is, the same operands and the
-    same bits; so for ``coarse_score_wide`` and ``coarse_score_stream``); yp (n0, 768) fp32, the
+    same bits; so for ``coarse_score_wide`` and ``coarse_score_stream``), or the rows as float8_e4m3fn
+    with ``row_scale`` (sum n_g,) fp32 (``rows_quant8``, an index's ``y8`` and ``s8``: the _rows8 entry points
+    dequantise the entry's tile on the way in, b = bf16(float(y8) * s8), exactly, so the score is the bits of
+    the bf16 call on ``rows_dequant8(y8, s8)``); yp (n0, 768) fp32, the
     probe's SplineConv rows; coef (B, 768) fp32 (``coef_tanh``).  Checked
     on the host before anything is launched: dtypes, contiguity and devices, every idx in [0, G),
     n0 and every selected n_g in [1, COARSE_NMAX = 128] (``idx_host`` / ``row_off_host``: host
@@ -1247,11 +1353,12 @@ def coarse_score(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_ho
 
     CPU tensors take the plain-torch statement of the definition, in ``dtype`` arithmetic
     (torch.float32, the default, or torch.float64) on the same bf16-rounded operands."""
-    return _coarse_score_op("fused", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
+    return _coarse_score_op("fused", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype,
+                            row_scale)
 
 
 def coarse_score_wide(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
-                      dtype=None):
+                      dtype=None, row_scale=None):
     """``coarse_score`` for boxes of up to COARSE_WIDE_NMAX = 256 keypoints (fpm_coarse_score_wide): the
     same definition, arguments and host-side checks, with n0 and every selected n_g in
     [1, COARSE_WIDE_NMAX].  The kernel keeps the block in registers and parks Kp in a scratch of
@@ -1259,11 +1366,12 @@ def coarse_score_wide(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, i
     Its sums run in another order than ``coarse_score``'s, so the two agree to rounding, not bit for
     bit, on boxes both take.  CPU tensors take the same plain-torch statement as ``coarse_score``
     (which has no size bound of its own)."""
-    return _coarse_score_op("wide", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
+    return _coarse_score_op("wide", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype,
+                            row_scale)
 
 
 def coarse_score_stream(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None, idx_host=None, row_off_host=None,
-                        dtype=None):
+                        dtype=None, row_scale=None):
     """``coarse_score`` for every box the matcher takes, up to COARSE_STREAM_NMAX = 600 keypoints
     (fpm_coarse_score_stream): the same definition, arguments and host-side checks, with n0 and every
     selected n_g in [1, COARSE_STREAM_NMAX].  The kernel writes Kp to a scratch of min(B, 256) slots of
@@ -1272,14 +1380,16 @@ def coarse_score_stream(y, row_off, idx, yp, coef, iters=10, tau=0.01, out=None,
     place, the others on potentials.  It agrees with ``coarse_score`` and ``coarse_score_wide`` to
     rounding, not bit for bit, on boxes they take.  CPU tensors take the same plain-torch statement
     (which has no size bound of its own)."""
-    return _coarse_score_op("stream", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype)
+    return _coarse_score_op("stream", y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype,
+                            row_scale)
 
 
 def coarse_pairs(y, row_off, gidx, yq, qrow_off, qidx, coef, kernel="fused", iters=10, tau=0.01, out=None,
-                 gidx_host=None, qidx_host=None, row_off_host=None, qrow_off_host=None, dtype=None):
+                 gidx_host=None, qidx_host=None, row_off_host=None, qrow_off_host=None, dtype=None, row_scale=None):
     """The coarse score over a pair list (fpm_coarse_pairs, _wide, _stream) -> (B,) fp32: pair b scores
     probe qidx[b] of the probe row store yq (sum n_q, 768) fp32 / qrow_off int64 [Q + 1] against entry
-    gidx[b] of the index rows y / row_off (fp32, or their bf16 copy: the _rows16 entry points) with
+    gidx[b] of the index rows y / row_off (fp32, their bf16 copy: the _rows16 entry points, or float8_e4m3fn
+    rows with their scales ``row_scale``: the _rows8 entry points) with
     coef[b], by the definition of ``coarse_score``.  ``kernel``: "fused" (boxes up to COARSE_NMAX),
     "wide" (COARSE_WIDE_NMAX) or "stream" (COARSE_STREAM_NMAX): the pair-list instantiation of that
     kernel, so score[b] is the same bits as ``coarse_score`` / ``_wide`` / ``_stream`` give for that
@@ -1295,7 +1405,7 @@ def coarse_pairs(y, row_off, gidx, yq, qrow_off, qidx, coef, kernel="fused", ite
     _, _, bound, nmax, _ = _COARSE_KERNELS[kernel]
     _check_index_tensors(op, (("gidx", gidx, torch.int32), ("qidx", qidx, torch.int32),
                               ("row_off", row_off, torch.int64), ("qrow_off", qrow_off, torch.int64)))
-    _check_coarse_rows(op, y, (("yq", yq), ("coef", coef)))
+    _check_coarse_rows(op, y, (("yq", yq), ("coef", coef)), row_scale)
     _check_on_device_of(op, y, (("row_off", row_off), ("gidx", gidx), ("yq", yq), ("qrow_off", qrow_off),
                                 ("qidx", qidx), ("coef", coef), ("out", out)))
     G, Q, B = int(row_off.numel()) - 1, int(qrow_off.numel()) - 1, int(gidx.numel())
@@ -1328,15 +1438,17 @@ def coarse_pairs(y, row_off, gidx, yq, qrow_off, qidx, coef, kernel="fused", ite
     if not y.is_cuda:
         dtype = _host_dtype(op, dtype)
         res = torch.empty(B, dtype=dtype)
+        yh = y if row_scale is None else rows_dequant8(y, row_scale)
         for b in range(B):
             q = int(qh[b])
-            res[b:b + 1] = _coarse_score_host(y, oh, gh[b:b + 1], yq[int(qoh[q]):int(qoh[q + 1])], coef[b:b + 1], iters,
+            res[b:b + 1] = _coarse_score_host(yh, oh, gh[b:b + 1], yq[int(qoh[q]):int(qoh[q + 1])], coef[b:b + 1], iters,
                                               tau, dtype)
         return _coarse_out(op, y, B, out, dtype, res)
     out = _coarse_out(op, y, B, out, dtype)
     if B:
         # the stream kernel's slots: the largest probe and the largest entry of the launch, from whichever pairs
-        _coarse_call(kernel, True, y, (_p(y), _p(row_off), _p(gidx), G, B, _p(yq), _p(qrow_off), _p(qidx), Q, _p(coef),
+        _coarse_call(kernel, True, y, (_p(y), *_scale_arg(row_scale), _p(row_off), _p(gidx), G, B, _p(yq), _p(qrow_off),
+                                       _p(qidx), Q, _p(coef),
                                        iters, tau, _p(out)), B, nqmax, ngmax)
     return out
 

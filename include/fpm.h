@@ -288,6 +288,18 @@ int fpm_rows_pack(const float* src, long src_rows, const int* n, int B, int nmax
  * destination).  cnt[k] = 0 copies nothing. */
 int fpm_rows_move(const float* src32, const void* src16, long src_rows, const long* src_off, const long* dst_off,
                   const long* cnt, int K, int band_rows, float* dst32, void* dst16, long dst_rows, void* stream);
+/* The same segment copy for the rows of an fp8 index: src8 -> dst8 (src_rows / dst_rows x 768 e4m3 bytes) together
+ * with the rows' scales srcs -> dsts (src_rows / dst_rows fp32), all four required, from the one offset table.
+ * Rows 16-byte aligned, scales 4-byte aligned; every other rule is fpm_rows_move's. */
+int fpm_rows_move8(const void* src8, const float* srcs, long src_rows, const long* src_off, const long* dst_off,
+                   const long* cnt, int K, int band_rows, void* dst8, float* dsts, long dst_rows, void* stream);
+/* Quantise index rows to fp8 with a power-of-two scale per row (the "fp8+host" layout of a gallery index).
+ * y: rows x 768 fp32 (device).  Per row: amax = max |y[r, k]|; e = 0 when amax == 0, else the smallest e with
+ * amax <= 448 * 2^e, held to [-110, 110]; s8[r] = 2^e (fp32); y8[r, k] = e4m3fn(clamp(y[r, k] * 2^-e, -448, 448)),
+ * round to nearest even (OCP e4m3fn, the encoding gfx950 converts natively).  float(y8) * s8 is then exactly
+ * representable in bf16: the coarse kernels' _rows8 entry points score with b = bf16(float(y8) * s8).  y and y8
+ * 16-byte aligned.  Non-finite rows are unspecified.  rows = 0 launches nothing. */
+int fpm_rows_quant8(const float* y, long rows, void* y8, float* s8, void* stream);
 /* vertex_attr_to_edge_attr (spline_conv.py:73-81): out[e] = x[src[e]] - x[dst[e]] */
 int fpm_edge_diff(const float* x, const int* src, const int* dst, long E, int D, float* out, void* stream);
 /* same, written into a padded per-pair layout and scaled: out[row[e]] = (x[src]-x[dst]) o c[pair[e]]
@@ -735,6 +747,28 @@ int fpm_coarse_pairs_wide_rows16(const void* y16, const long* row_off, const int
 int fpm_coarse_pairs_stream_rows16(const void* y16, const long* row_off, const int* idx, int G, int B,
                                    const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
                                    int iters, float tau, float* score, void* ws, long ws_bytes, void* stream);
+/* The six entry points for an fp8 index (fpm_rows_quant8): y8 (sum n_g x 768 e4m3 bytes) and s8 (sum n_g fp32, the
+ * rows' power-of-two scales) in the place of y16; every other argument, check and workspace is the _rows16
+ * sibling's.  The entry's tile is dequantised on the way into LDS, exactly, so score[b] is bit-identical to the
+ * _rows16 entry point's on y16 = bf16(float(y8) * s8[:, None]). */
+int fpm_coarse_score_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G, int B,
+                           const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                           void* stream);
+int fpm_coarse_score_wide_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G, int B,
+                                const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                                void* ws, long ws_bytes, void* stream);
+int fpm_coarse_score_stream_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G, int B,
+                                  const float* yp, int n0, const float* coef, int iters, float tau, float* score,
+                                  void* ws, long ws_bytes, void* stream);
+int fpm_coarse_pairs_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G, int B,
+                           const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef, int iters,
+                           float tau, float* score, void* stream);
+int fpm_coarse_pairs_wide_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G, int B,
+                                const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
+                                int iters, float tau, float* score, void* ws, long ws_bytes, void* stream);
+int fpm_coarse_pairs_stream_rows8(const void* y8, const float* s8, const long* row_off, const int* idx, int G, int B,
+                                  const float* yq, const long* qrow_off, const int* qidx, int Q, const float* coef,
+                                  int iters, float tau, float* score, void* ws, long ws_bytes, void* stream);
 
 /* ---- profiling hooks: HIP-event timing of the dominant kernel (edge-message GEMM) ------------ */
 int fpm_profile_enable(int on);

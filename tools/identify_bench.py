@@ -11,6 +11,8 @@
                                                                        (-> profiles/identify_shortlist_stream.json)
     python tools/identify_bench.py --shortlist 64 --layout f32,f32+bf16,bf16+host [--coarse auto --n 256] [--append]
                                                                        (-> profiles/identify_compact.json)
+    python tools/identify_bench.py --shortlist 64 --layout bf16+host,fp8+host [--coarse stream --n 512] [--append]
+                                                                       (-> profiles/identify_fp8.json)
     python tools/identify_bench.py --probes 16 --shortlist 64 [--coarse auto --n 256 --large 0] [--append]
                                                                        (-> profiles/identify_many.json)
     python tools/identify_bench.py --subjects 4 --shortlist 64 --probes 16 --gallery 16384 --large 0 --dtypes bf16
@@ -42,7 +44,9 @@ against wide in one process: the number that decides which kernel boxes of up to
 ``--layout a,b,..`` (with ``--shortlist``): the index layouts against each other.  The gallery is enrolled
 once per layout in one process; per layout the device and host bytes held, the coarse pass (which reads
 the bf16 rows where the layout has them), the fetch of the shortlist's fp32 rows from pinned host memory
-("bf16+host"), the M-pair forward and the whole shortlisted query; the first layout is the baseline of
+("bf16+host", "fp8+host"), the M-pair forward and the whole shortlisted query; an "fp8+host" layout also records
+how far its coarse scores lie from the baseline's and how much of the coarse top 10 they share, on this gallery
+and on the tests' planted-mate gallery; the first layout is the baseline of
 the A/B verdicts.
 
 Shape: config C4 (one probe, n = 128 keypoints, a gallery of 1024), both dtypes.  Per dtype, in a
@@ -278,7 +282,7 @@ def child_layouts(args):
     import torch
     import bench
     import fpm
-    from fpm import params, synth
+    from fpm import gallery as fgallery, params, synth
     dev = torch.device("cuda", 0)
     G, n, dtype, M, coarse = args.gallery, args.n, args.child, args.shortlist, args.coarse
     layouts = args.layout.split(",")
@@ -323,10 +327,21 @@ def child_layouts(args):
         r["identical_to_%s" % layouts[0]] = all(bool(torch.equal(short[k], ref[k])) for k in
                                                 ("ss", "ds_mat", "perm_mat", "k_prob", "cls_prob", "top_idx",
                                                  "top_score", "short_idx", "coarse_score", "coarse_all"))
+        if lay == fgallery.FP8_LAYOUT and ref is not short:
+            # the coarse scores are another operand's; the exact outputs of an entry are the same bits
+            r["coarse_vs_%s" % layouts[0]] = _coarse_shift(short["coarse_all"], ref["coarse_all"])
+            sel = net.identify(probe, index[layouts[0]], topk=10, select=sidx)
+            r["exact_identical_on_own_shortlist"] = all(bool(torch.equal(short[k], sel[k])) for k in
+                                                        ("ss", "ds_mat", "perm_mat", "k_prob", "cls_prob", "top_idx",
+                                                         "top_score"))
         r["coarse"] = series(lambda: net.coarse_scores(probe, ix, coarse=coarse))
         read = res["row_bytes"] // (1 if ix.y16 is None else 2)
+        if ix.y8 is not None:
+            read = int(ix.y8.shape[0]) * fgallery.ROW_BYTES_FP8
+        r["device_row_bytes_per_keypoint"] = {"f32": 3072, "f32+bf16": 4608, "bf16+host": 1536,
+                                              "fp8+host": fgallery.ROW_BYTES_FP8}[lay]
         r["coarse"].update(index_bytes_read=read, index_tb_per_s=round(read / r["coarse"]["median_ms"] / 1e9, 3))
-        if lay == "bf16+host":
+        if lay in fgallery.HOST_LAYOUTS:
             r["fetch"] = series(lambda: fresh(ix, lambda: ix.fetch(sidx)))
             fb = int(ix.n[sidx].sum()) * 3072
             r["fetch"].update(bytes=fb, gb_per_s=round(fb / r["fetch"]["median_ms"] / 1e6, 1),
@@ -347,7 +362,41 @@ def child_layouts(args):
                 slower_margin_ms=round(c["min_ms"] - (c["max_ms"] - c["min_ms"]) - o["median_ms"], 3))
             r["ab_%s" % part]["verdict"] = ("faster" if r["ab_%s" % part]["faster_margin_ms"] > 0 else
                                             "slower" if r["ab_%s" % part]["slower_margin_ms"] > 0 else "within spread")
+    if fgallery.FP8_LAYOUT in layouts[1:]:
+        res["planted"] = _planted_shift(layouts[0], dtype)
     print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
+
+
+def _coarse_shift(got, ref):
+    """One probe's coarse scores on two layouts -> the largest shift and how much of the top 10 is shared."""
+    import torch
+    k = min(10, int(ref.numel()))
+    a, b = set(torch.topk(got, k).indices.tolist()), set(torch.topk(ref, k).indices.tolist())
+    return dict(max_shift=float((got - ref).abs().max()), ref_min=float(ref.min()), ref_max=float(ref.max()),
+                top10_overlap=len(a & b))
+
+
+def _planted_shift(base, dtype):
+    """The tests' planted-mate gallery (40 entries, three probes, the "spread" weights) on the fp8 layout against
+    ``base``: per probe the coarse-score shift, the top-10 overlap and the mate's margin."""
+    import torch
+    import fpm
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_shortlist_cpu import state_dicts
+    from test_shortlist_gpu import MATES, planted
+    dev = torch.device("cuda", 0)
+    gal, probes = planted()
+    net = fpm.Net(regression=True, backbone=False, dtype=dtype)
+    net.load_state_dict(state_dicts()["spread"])
+    a, b = net.enroll(gal, dev, batch=16, layout="fp8+host"), net.enroll(gal, dev, batch=16, layout=base)
+    out = []
+    for p, probe in enumerate(probes):
+        got, ref = net.coarse_scores(probe, a)[0], net.coarse_scores(probe, b)[0]
+        mate = [e for e, q in MATES.items() if q == p][0]
+        rest = torch.cat([got[:mate], got[mate + 1:]])
+        out.append(dict(_coarse_shift(got, ref), mate_first=int(torch.argmax(got)) == mate, mate_score=float(got[mate]),
+                        best_other=float(rest.max())))
+    return dict(gallery=len(gal), baseline=base, weights="spread", probes=out)
 
 
 def _entry_major(p0, p1, Qs, Gs):
@@ -524,7 +573,7 @@ def main_shortlist(ap, args):
     name = {"fused": "identify_shortlist.json", "wide": "identify_shortlist_wide.json",
             "auto": "identify_shortlist_wide.json"}.get(args.coarse, "identify_shortlist_stream.json")
     if args.layout != "f32":
-        name = "identify_compact.json"
+        name = "identify_fp8.json" if "fp8+host" in args.layout.split(",") else "identify_compact.json"
     if args.probes:
         name = "identify_many.json"
     if args.subjects:
@@ -569,10 +618,11 @@ def main():
                     help="--shortlist: the coarse pass's kernel (wide / auto: profiles/identify_shortlist_wide.json; "
                          "stream / any: profiles/identify_shortlist_stream.json)")
     ap.add_argument("--layout", default="f32",
-                    help="--shortlist: the index layout(s), comma-separated (f32, f32+bf16, bf16+host).  Anything but "
+                    help="--shortlist: the index layout(s), comma-separated (f32, f32+bf16, bf16+host, fp8+host).  Anything but "
                          "the default 'f32' enrols the gallery once per layout in one process and records per layout "
                          "the bytes held, the coarse pass, the fetch, the M-pair forward and the whole shortlisted "
-                         "query, the first layout the A/B baseline (profiles/identify_compact.json)")
+                         "query, the first layout the A/B baseline (profiles/identify_compact.json; with fp8+host, "
+                         "which also records its coarse scores' shift against the baseline: profiles/identify_fp8.json)")
     ap.add_argument("--probes", type=int, default=0,
                     help="--shortlist: Q > 0 probes: the looped identify against identify_many "
                          "(profiles/identify_many.json)")
