@@ -48,6 +48,10 @@ SIGNATURES = {
     "fpm_rank_topk": (I, [P, L, I, I, I, P, P, P]),
     "fpm_rank_select_ws_bytes": (L, [I]),
     "fpm_rank_select": (I, [P, L, I, I, I, P, P, P, L, P]),
+    "fpm_rank_keep_ws_bytes": (L, [I, I]),
+    "fpm_rank_keep": (I, [P, L, I, I, I, P, P, L, P]),
+    "fpm_rows_pool": (I, [P, L, P, I, I, P, P]),
+    "fpm_desc_score": (I, [P, I, P, I, P, I, P, P]),
     "fpm_group_scores": (I, [P, L, I, I, P, L, P, L, I, I, P, P, P]),
     "fpm_group_topr": (I, [P, L, I, I, P, L, P, L, I, I, P, P, P]),
     "fpm_cohort_decide": (I, [P, I, I, I, I, I, F, I, I, F, P, P, P, P, P, P]),

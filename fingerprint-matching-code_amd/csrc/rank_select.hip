@@ -12,6 +12,10 @@
 //   2. Compaction: the keys >= T (exactly k, keys being unique) go to a k-slot list, slots handed
 //      out by an integer atomic (their order is arbitrary and does not matter:)
 //   3. one workgroup per row sorts the list in LDS (bitonic, 1024 slots) and writes indices and scores.
+//
+// fpm_rank_keep (the prescreen of a 1:N identification) takes step 1 as it is (rs_search) for any k <= G and
+// replaces steps 2 and 3 by an ordered compaction: the columns whose key is >= T, in ascending column order,
+// with no slot handed out by an atomic (below).
 #include "fpm_common.h"
 #include "fpm.h"
 
@@ -177,6 +181,109 @@ __global__ __launch_bounds__(RS_THREADS) void rank_select_sort_kernel(const floa
         top_score[(long)blockIdx.x * k + j] = ok ? row[i] : __uint_as_float(0x7FC00000u);
     }
 }
+
+// ---- rank_keep: the k best of a row as a set, in column order, for any k <= G ------------------------------
+// The row is cut into contiguous slices of RK_CHUNK-aligned length; slice s of row p is one workgroup in both
+// launches.  Launch 1: the slice's count of keys >= T.  Launch 2: the sum of the counts of the slices before it
+// (fixed order), then the slice's columns in ascending order, a chunk of 256 at a time: the place inside a chunk
+// is the wave's ballot prefix plus the counts of the waves before it.
+constexpr int RK_CHUNK = RS_THREADS;
+constexpr int RK_SLICE = RS_THREADS * RS_ITEMS;     // columns per slice, at least
+constexpr int RK_SLICES = 1024;                     // slices per row, at most
+
+struct RkPlan {
+    int nb;        // slices per row
+    long len;      // columns per slice (a multiple of RK_CHUNK)
+};
+inline RkPlan rk_plan(int G) {
+    long nb = ((long)G + RK_SLICE - 1) / RK_SLICE;
+    nb = nb < 1 ? 1 : (nb > RK_SLICES ? RK_SLICES : nb);
+    long len = ((long)G + nb - 1) / nb;
+    len = (len + RK_CHUNK - 1) / RK_CHUNK * RK_CHUNK;
+    nb = ((long)G + len - 1) / len;
+    return RkPlan{(int)(nb < 1 ? 1 : nb), len};
+}
+
+// the sum of v over the workgroup, in every thread (a fixed tree over LDS; sh: RS_THREADS words)
+__device__ unsigned rk_block_sum(unsigned v, unsigned* sh) {
+    const int tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+    for (int o = RS_THREADS / 2; o > 0; o >>= 1) {
+        if (tid < o) sh[tid] += sh[tid + o];
+        __syncthreads();
+    }
+    const unsigned r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void rank_keep_count_kernel(const float* __restrict__ scores, long ld, int G,
+                                                                     int k, long len, const RsRow* __restrict__ ws,
+                                                                     unsigned* __restrict__ cnt) {
+    __shared__ unsigned sh[RS_THREADS + 2];
+    const RsRow* w = ws + blockIdx.y;
+    const float* row = scores + (long)blockIdx.y * ld;
+    u64 T;
+    unsigned krem;
+    rs_derive(w, RS_PASSES, (unsigned)k, sh, T, krem);
+    const long c0 = (long)blockIdx.x * len, c1 = c0 + len < G ? c0 + len : G;
+    unsigned c = 0;
+    for (long i = c0 + threadIdx.x; i < c1; i += RS_THREADS) c += rs_key(row[i], (int)i) >= T ? 1u : 0u;
+    c = rk_block_sum(c, sh);
+    if (threadIdx.x == 0) cnt[(long)blockIdx.y * gridDim.x + blockIdx.x] = c;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void rank_keep_write_kernel(const float* __restrict__ scores, long ld, int G,
+                                                                     int k, long len, const RsRow* __restrict__ ws,
+                                                                     const unsigned* __restrict__ cnt,
+                                                                     int* __restrict__ keep) {
+    __shared__ unsigned sh[RS_THREADS + 2];
+    __shared__ unsigned wc[RS_THREADS / 64];
+    const RsRow* w = ws + blockIdx.y;
+    const float* row = scores + (long)blockIdx.y * ld;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    u64 T;
+    unsigned krem;
+    rs_derive(w, RS_PASSES, (unsigned)k, sh, T, krem);
+    // columns kept by the slices before this one
+    unsigned before = 0;
+    for (int s = tid; s < (int)blockIdx.x; s += RS_THREADS) before += cnt[(long)blockIdx.y * gridDim.x + s];
+    unsigned base = rk_block_sum(before, sh);
+    int* out = keep + (long)blockIdx.y * k;
+    const long c0 = (long)blockIdx.x * len, c1 = c0 + len < G ? c0 + len : G;
+    for (long b = c0; b < c1; b += RK_CHUNK) {               // the trip count is the workgroup's
+        const long i = b + tid;
+        const bool in = i < c1 && rs_key(row[i < c1 ? i : c0], (int)i) >= T;
+        const u64 m = __ballot(in);
+        if (lane == 0) wc[wv] = (unsigned)__popcll(m);
+        __syncthreads();
+        unsigned at = base, all = 0;
+#pragma unroll
+        for (int q = 0; q < RS_THREADS / 64; ++q) {
+            if (q < wv) at += wc[q];
+            all += wc[q];
+        }
+        at += (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+        if (in && at < (unsigned)k) out[at] = (int)i;        // exactly k columns pass; the guard bounds the write
+        base += all;
+        __syncthreads();
+    }
+}
+
+// the grid of the search's passes and of rank_select's compaction: several workgroups per row
+inline dim3 rs_grid(int P, int G) {
+    const long per = (long)RS_THREADS * RS_ITEMS;
+    long nb = (G + per - 1) / per;
+    nb = nb < 1 ? 1 : (nb > 256 ? 256 : nb);
+    return dim3((unsigned)nb, (unsigned)P);
+}
+
+// step 1 of both entry points: the six digit passes over a cleared workspace
+void rs_search(const float* scores, long ld, int P, int G, int k, RsRow* w, hipStream_t st) {
+    for (int d = 0; d < RS_PASSES; ++d)
+        hipLaunchKernelGGL(rank_select_hist_kernel, rs_grid(P, G), dim3(RS_THREADS), 0, st, scores, ld, G, k, d, w);
+}
 }  // namespace
 
 extern "C" long fpm_rank_select_ws_bytes(int P) { return P > 0 ? (long)P * (long)sizeof(RsRow) : 0; }
@@ -196,15 +303,43 @@ extern "C" int fpm_rank_select(const float* scores, long ld, int P, int G, int k
         fpm::set_error("rank_select: clearing the workspace failed");
         return 1;
     }
-    const long per = (long)RS_THREADS * RS_ITEMS;
-    long nb = (G + per - 1) / per;
-    nb = nb < 1 ? 1 : (nb > 256 ? 256 : nb);
     RsRow* w = (RsRow*)ws;
-    const dim3 grid((unsigned)nb, (unsigned)P);
-    for (int d = 0; d < RS_PASSES; ++d)
-        hipLaunchKernelGGL(rank_select_hist_kernel, grid, dim3(RS_THREADS), 0, st, scores, ld, G, k, d, w);
-    hipLaunchKernelGGL(rank_select_compact_kernel, grid, dim3(RS_THREADS), 0, st, scores, ld, G, k, w);
+    rs_search(scores, ld, P, G, k, w, st);
+    hipLaunchKernelGGL(rank_select_compact_kernel, rs_grid(P, G), dim3(RS_THREADS), 0, st, scores, ld, G, k, w);
     hipLaunchKernelGGL(rank_select_sort_kernel, dim3((unsigned)P), dim3(RS_THREADS), 0, st, scores, ld, G, k,
                        (const RsRow*)w, top_idx, top_score);
     return fpm::check_launch("fpm_rank_select");
+}
+
+extern "C" long fpm_rank_keep_ws_bytes(int P, int G) {
+    if (P <= 0 || G <= 0) return 0;
+    return (long)P * ((long)sizeof(RsRow) + (long)rk_plan(G).nb * (long)sizeof(unsigned));
+}
+
+extern "C" int fpm_rank_keep(const float* scores, long ld, int P, int G, int k, int* keep, void* ws, long ws_bytes,
+                             void* stream) {
+    FPM_CHECK_ARG(P >= 0 && G >= 1 && ld >= G, "rank_keep: bad sizes (P %d, G %d, ld %ld)", P, G, ld);
+    FPM_CHECK_ARG(k >= 1 && k <= G, "rank_keep: k = %d outside [1, G = %d]", k, G);
+    FPM_CHECK_ARG(scores && keep, "rank_keep: scores and keep are required");
+    FPM_CHECK_ARG(P <= 65535, "rank_keep: at most 65535 rows per call (P %d)", P);
+    if (P == 0) return 0;
+    const long need = fpm_rank_keep_ws_bytes(P, G);
+    FPM_CHECK_ARG(ws && ws_bytes >= need, "rank_keep: workspace of %ld bytes required (got %ld)", need, ws_bytes);
+    FPM_CHECK_ARG(((uintptr_t)ws & 7) == 0, "rank_keep: the workspace must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ws, 0, (size_t)need, st) != hipSuccess) {
+        (void)hipGetLastError();
+        fpm::set_error("rank_keep: clearing the workspace failed");
+        return 1;
+    }
+    RsRow* w = (RsRow*)ws;
+    unsigned* cnt = (unsigned*)(w + P);
+    const RkPlan pl = rk_plan(G);
+    rs_search(scores, ld, P, G, k, w, st);
+    const dim3 grid((unsigned)pl.nb, (unsigned)P);
+    hipLaunchKernelGGL(rank_keep_count_kernel, grid, dim3(RS_THREADS), 0, st, scores, ld, G, k, pl.len,
+                       (const RsRow*)w, cnt);
+    hipLaunchKernelGGL(rank_keep_write_kernel, grid, dim3(RS_THREADS), 0, st, scores, ld, G, k, pl.len,
+                       (const RsRow*)w, (const unsigned*)cnt, keep);
+    return fpm::check_launch("fpm_rank_keep");
 }

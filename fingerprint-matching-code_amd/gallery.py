@@ -69,6 +69,13 @@ over a sharded gallery branches to ``identify_sharded`` there, which runs the st
 shards' shortlists (``ops.topk_merge``); ``probe_batch(pad_to=...)`` lays a shard's part of a list out in the whole
 list's box, so that the parts' outputs are the one-index forward's.
 
+Prescreen (``identify`` / ``identify_many(shortlist=M, prescreen=K)``; opt-in, and without it nothing above changes):
+an index may hold one pooled bf16 descriptor per entry (``GalleryIndex.desc``: ``enroll*(descriptors=True)``,
+``add_descriptors``; ``ops.rows_pool``).  ``_prescreen`` scores the probes' descriptors against the selection's
+(``ops.desc_score``) and keeps each probe's K best entries in entry order (``ops.rank_keep``); the coarse pass then runs
+over each probe's own list (``_coarse_one``, or ``_coarse_many`` over the Q x K pair lists) and ``_shortlist`` maps its
+positions through that list.
+
 A mutable index (``GalleryIndex.reserve``, ``enroll*(capacity=...)``; ``Net.enroll_into`` and its keypoint and image
 forms; ``remove``, ``compact``): storage with capacity, of which the public fields are prefix views, re-made by the one
 ``_commit``; appends write past ``used`` and commit at the end; ``remove`` sets tombstones and every query then runs
@@ -93,6 +100,7 @@ FORMAT = 1                    # a saved "f32" index; the other layouts write FOR
 FORMAT_LAYOUTS = 2
 FORMAT_TOMBSTONES = 3         # any layout, with the table ``removed`` (an index saved with removed slots)
 FORMAT_FP8 = 4                # the "fp8+host" layout: ``y8`` and ``s8`` for ``y16``; ``removed`` with tombstones
+FORMAT_DESC = 5               # any layout (its own row fields), with ``desc``; ``removed`` with tombstones
 SCORES = ("cls_prob", "cls_logits", "k_prob")
 LAYOUTS = ("f32", "f32+bf16", "bf16+host", "fp8+host")
 HOST_LAYOUTS = ("bf16+host", "fp8+host")      # the fp32 rows in (pinned) host memory: ``fetch``
@@ -113,6 +121,7 @@ def _host_rows(shape, dev):
 
 # the rows of the device buffer ``GalleryIndex.compact`` stages blocks in whose destination meets their source
 COMPACT_STAGE_BYTES = 64 << 20
+DESC_STAGE_BYTES = 64 << 20   # the device buffer ``GalleryIndex.add_descriptors`` uploads host rows through
 COMPACT_HOST_ROWS = 4096      # rows per piece (12 MB) of a host-side move whose destination meets its source
 
 
@@ -134,7 +143,7 @@ def _check_capacity(what, capacity, G, R, E=0):
     return tuple(cap)
 
 
-def _make_store(cap, layout, dev, has_P, has_subject):
+def _make_store(cap, layout, dev, has_P, has_subject, has_desc=False):
     """The buffers of an index with capacity ``cap`` = (entries, rows, edges): the device arrays (in
     "bf16+host" and "fp8+host" the fp32 rows pinned on the host), and the host tables.  Rows and edges are uninitialised,
     the small tables zero.  The public fields of the index are prefix views of these."""
@@ -149,6 +158,7 @@ def _make_store(cap, layout, dev, has_P, has_subject):
                 P=new((rows, 2), torch.float32) if has_P else None,
                 src=new((edges,), torch.int32), dst=new((edges,), torch.int32), pseudo=new((edges, 2), torch.float32),
                 w=new((ents, C.GLOBAL_FEATURE_DIM), torch.float32),
+                desc=new((ents, C.NODE_FEATURE_DIM), torch.bfloat16) if has_desc else None,
                 row_off=torch.zeros(ents + 1, device=dev, dtype=torch.int64),
                 n=torch.zeros(ents, dtype=torch.int32), edge_off=torch.zeros(ents + 1, dtype=torch.int64),
                 row_off_host=torch.zeros(ents + 1, dtype=torch.int64),
@@ -186,6 +196,9 @@ class GalleryIndex:
       pseudo    (sum E, 2) fp32     their pseudo-coordinates (device)
       edge_off  (G + 1,) int64      edge offsets per graph (host)
       w         (G, 512) fp32       global features (device)
+      desc      (G, 768) bf16       device, or None: the prescreen descriptor of each entry, its rows sum-pooled
+                                    and L2-normalised (``ops.rows_pool``; ``add_descriptors``,
+                                    ``enroll*(descriptors=True)``): 1536 B per entry
       P         (sum n, 2) fp32     keypoints, or None when the graphs carry none (device)
       subject   (G,) int64 or None  the subject label (>= 0) of each entry (host; ``set_subjects``): the
                                     impressions of one finger share a label.  ``subject_groups`` makes a
@@ -196,7 +209,7 @@ class GalleryIndex:
     """
 
     def __init__(self, y, row_off, n, src, dst, pseudo, edge_off, w, P, sc_mode, pack_gen, weights_id, y16=None,
-                 layout="f32", subject=None, y8=None, s8=None):
+                 layout="f32", subject=None, y8=None, s8=None, desc=None):
         if sc_mode not in ("f32", "bf16"):
             raise FpmError("GalleryIndex: sc_mode must be 'f32' or 'bf16'")
         if layout not in LAYOUTS:
@@ -218,7 +231,13 @@ class GalleryIndex:
         if layout in HOST_LAYOUTS and (y.is_cuda or (row_off.is_cuda and not y.is_pinned())):
             raise FpmError("GalleryIndex: layout %r keeps y in host memory (pinned when the index is on a "
                            "GPU)" % layout)
+        if desc is not None and (not isinstance(desc, torch.Tensor) or desc.dtype != torch.bfloat16
+                                 or tuple(desc.shape) != (int(w.shape[0]), C.NODE_FEATURE_DIM)
+                                 or desc.device != row_off.device):
+            raise FpmError("GalleryIndex: inconsistent fields (desc must be bfloat16, one row of %d channels per entry, "
+                           "on the index device)" % C.NODE_FEATURE_DIM)
         self.y, self.src, self.dst, self.pseudo, self.w, self.P = y, src, dst, pseudo, w, P
+        self.desc = desc
         self.y16, self.y8, self.s8, self.layout = y16, y8, s8, layout
         self._stage = None          # fetch: (sel, staging buffer, row offsets device / host) of the last selection
         self.row_off = row_off
@@ -255,10 +274,12 @@ class GalleryIndex:
 
     def nbytes(self):
         """Device bytes held: the rows (3 KB per keypoint in the "f32" layout, 4.5 KB in "f32+bf16",
-        1.5 KB in "bf16+host", 772 B in "fp8+host"), plus edges and global features."""
+        1.5 KB in "bf16+host", 772 B in "fp8+host"), plus edges, global features and the descriptors (1536 B per
+        entry) when the index holds them."""
         f = self._store or dict(row_off=self.row_off, src=self.src, dst=self.dst, pseudo=self.pseudo, w=self.w,
-                                P=self.P, y=self.y, y16=self.y16, y8=self.y8, s8=self.s8)
+                                P=self.P, y=self.y, y16=self.y16, y8=self.y8, s8=self.s8, desc=self.desc)
         ts = [f[k] for k in ("row_off", "src", "dst", "pseudo", "w")] + ([] if f["P"] is None else [f["P"]])
+        ts += [] if f.get("desc") is None else [f["desc"]]
         ts += ([] if self.layout in HOST_LAYOUTS else [f["y"]]) + [f[k] for k in ("y16", "y8", "s8") if f[k] is not None]
         if self._groups is not None:
             ts += [self._groups[1][k] for k in ("labels_d", "off_d", "pos_d")]
@@ -275,6 +296,47 @@ class GalleryIndex:
         if self.y8 is not None:
             return self.y8, self.s8
         return (self.y if self.y16 is None else self.y16), None
+
+    def add_descriptors(self, chunk=None):
+        """Pool the prescreen descriptor of every slot of an existing index (``ops.rows_pool``) -> self, with
+        ``desc`` (G, 768) bf16 on the device (in an index with capacity: a table of ``capacity`` entries, of which
+        ``desc`` is the prefix view).  The "f32" layouts pool from ``y`` where it is; "bf16+host" and "fp8+host"
+        upload their pinned fp32 rows in chunks of whole entries of at most ``chunk`` rows (default
+        DESC_STAGE_BYTES worth, never less than the largest entry) into one reused device buffer.  The bits are
+        those ``enroll*(descriptors=True)`` gives.  Removed slots are pooled too (their rows are still there);
+        an index that holds descriptors already pools them afresh."""
+        G, R, _ = self.used
+        dev = self.device
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+            if self._store is not None and self._store.get("desc") is None:
+                self._store["desc"] = torch.empty(self._store["cap"][0], C.NODE_FEATURE_DIM, device=dev,
+                                                  dtype=torch.bfloat16)
+            desc = (torch.empty(G, C.NODE_FEATURE_DIM, device=dev, dtype=torch.bfloat16) if self._store is None
+                    else self._store["desc"][:G])
+            ro = self.row_off_host
+            if self.layout not in HOST_LAYOUTS:
+                ops.rows_pool(self.y, self.row_off, 0, G, out=desc, row_off_host=ro)
+            elif G:
+                big = int(self.n.max())
+                rows = max(DESC_STAGE_BYTES // ROW_BYTES if chunk is None else int(chunk), 1)
+                if rows < big:
+                    if chunk is not None:
+                        raise FpmError("GalleryIndex.add_descriptors: chunk = %d below the largest entry (%d rows)"
+                                       % (rows, big))
+                    rows = big
+                stage = torch.empty(min(rows, R), C.NODE_FEATURE_DIM, device=dev, dtype=torch.float32)
+                g0 = 0
+                while g0 < G:
+                    # the entries [g0, g1) whose rows fit the stage: at least one
+                    g1 = int(torch.searchsorted(ro, ro[g0] + rows, right=True)) - 1
+                    g1 = min(max(g1, g0 + 1), G)
+                    r0, r1 = int(ro[g0]), int(ro[g1])
+                    stage[:r1 - r0].copy_(self.y[r0:r1], non_blocking=True)
+                    off = ro[g0:g1 + 1] - r0
+                    ops.rows_pool(stage[:r1 - r0], off.to(dev), 0, g1 - g0, out=desc[g0:g1], row_off_host=off)
+                    g0 = g1
+        self.desc = desc
+        return self
 
     # ---- a mutable index: capacity, enrolment into it (Net.enroll_into), tombstones, compaction ----
     @property
@@ -335,6 +397,7 @@ class GalleryIndex:
         self.P = None if st["P"] is None else st["P"][:R]
         self.src, self.dst, self.pseudo = st["src"][:E], st["dst"][:E], st["pseudo"][:E]
         self.w, self.row_off = st["w"][:G], st["row_off"][:G + 1]
+        self.desc = None if st.get("desc") is None else st["desc"][:G]
         self.n, self.edge_off, self.row_off_host = st["n"][:G], st["edge_off"][:G + 1], st["row_off_host"][:G + 1]
         self.subject = None if st["subject"] is None else st["subject"][:G]
         self._touch()
@@ -349,7 +412,8 @@ class GalleryIndex:
                            None if st["P"] is None else st["P"][:R], sc_mode, pack_gen, weights_id,
                            y16=None if st["y16"] is None else st["y16"][:R], layout=layout,
                            subject=None if sub is None else sub[:G], y8=None if st["y8"] is None else st["y8"][:R],
-                           s8=None if st["s8"] is None else st["s8"][:R])
+                           s8=None if st["s8"] is None else st["s8"][:R],
+                           desc=None if st.get("desc") is None else st["desc"][:G])
         idx._store = st
         idx._commit(G, R, E, lo=G)
         idx.generation = 0
@@ -367,10 +431,13 @@ class GalleryIndex:
                               (entries, keypoints, edges), G, R, E)
         dev = self.device
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-            st = _make_store(cap, self.layout, dev, self.P is not None, self.subject is not None)
+            st = _make_store(cap, self.layout, dev, self.P is not None, self.subject is not None,
+                             self.desc is not None)
             for key in ("y", "y16", "y8", "s8", "P"):
                 if st[key] is not None:
                     st[key][:R].copy_(getattr(self, key))
+            if self.desc is not None:
+                st["desc"][:G].copy_(self.desc)
             for key in ("src", "dst", "pseudo"):
                 st[key][:E].copy_(getattr(self, key))
             st["w"][:G].copy_(self.w)
@@ -389,7 +456,7 @@ class GalleryIndex:
             self._store = dict(cap=self.used, y=self.y, y16=self.y16, y8=self.y8, s8=self.s8, P=self.P, src=self.src,
                                dst=self.dst,
                                pseudo=self.pseudo, w=self.w, row_off=self.row_off, n=self.n, edge_off=self.edge_off,
-                               row_off_host=self.row_off_host, subject=self.subject)
+                               row_off_host=self.row_off_host, subject=self.subject, desc=self.desc)
         return self._store
 
     def _need_capacity(self, what):
@@ -415,10 +482,11 @@ class GalleryIndex:
                            "used); reserve a bigger index (GalleryIndex.reserve)" % (what, Gn, Rn, G, cap[0], R, cap[1]))
         return G, R, E
 
-    def _finish_append(self, what, at, n, w, P, src, dst, pseudo, cnt, subjects):
+    def _finish_append(self, what, at, n, w, P, src, dst, pseudo, cnt, subjects, desc=None):
         """The end of an append whose rows are written (past ``used``, from ``at`` = ``_begin_append``'s):
         the new entries' small arrays go into the storage's tail -- n host int32, w (Gn, 512), P (Rn, 2) or
-        None, the edges with graph-local ids and their host counts per entry -- and the index is committed.
+        None, the edges with graph-local ids and their host counts per entry, ``desc`` (Gn, 768) the new entries'
+        descriptors on an index that holds them -- and the index is committed.
         Until the commit no field has changed: an error before it leaves the index as it was."""
         G, R, E = at
         st = self._store
@@ -428,7 +496,12 @@ class GalleryIndex:
         if int(cnt.numel()) != Gn or int(cnt.sum()) != En:
             raise FpmError("%s: %d edges, their counts per entry sum to %d" % (what, En, int(cnt.sum())))
         _edge_room(what, En, st["cap"][2] - E)
+        if (desc is None) != (st.get("desc") is None):
+            raise FpmError("%s: the index %s descriptors, the append %s" % (
+                what, "holds" if desc is None else "holds no", "brings none" if desc is None else "brings them"))
         st["w"][G:G + Gn].copy_(w)
+        if desc is not None:
+            st["desc"][G:G + Gn].copy_(desc)
         if P is not None:
             st["P"][R:R + Rn].copy_(P)
         for key, t in (("src", src), ("dst", dst), ("pseudo", pseudo)):
@@ -585,6 +658,8 @@ class GalleryIndex:
             for key in ("src", "dst", "pseudo"):
                 st[key][:En] = st[key][edges_d]
             st["w"][:L] = st["w"][live_d]
+            if st.get("desc") is not None:
+                st["desc"][:L] = st["desc"][live_d]          # a fixed-size per-entry table, as w
             st["n"][:L] = st["n"][live]
             if st["subject"] is not None:
                 st["subject"][:L] = st["subject"][live]
@@ -598,7 +673,9 @@ class GalleryIndex:
         writes format 1, as ever; the bf16 layouts write format 2, with ``layout`` and ``y16``.  Of an
         index with capacity the used part is written; one with removed slots writes format 3, which adds
         the table ``removed``.  "fp8+host" writes format 4: ``layout``, ``y8`` (as bytes: uint8) and ``s8`` in
-        ``y16``'s place, and ``removed`` when there are removed slots."""
+        ``y16``'s place, and ``removed`` when there are removed slots.  An index that holds descriptors writes
+        format 5: ``layout``, the layout's own row fields as above, ``desc``, and ``removed`` when there are removed
+        slots; without descriptors the formats 1 to 4 are written as before."""
         # a field of an index with storage is a view: a host view is copied, so that only its part is written
         host = (lambda t: t.cpu()) if self._store is None else (lambda t: t.cpu() if t.is_cuda else t.clone())
         d = dict(format=FORMAT, y=host(self.y), row_off=host(self.row_off_host), n=host(self.n), src=host(self.src),
@@ -614,6 +691,8 @@ class GalleryIndex:
             d.update(format=FORMAT_TOMBSTONES, layout=self.layout, removed=self.removed.clone())
         if self.layout == FP8_LAYOUT:
             d.update(format=FORMAT_FP8, layout=self.layout, y8=host(self.y8).view(torch.uint8), s8=host(self.s8))
+        if self.desc is not None:
+            d.update(format=FORMAT_DESC, layout=self.layout, desc=host(self.desc))
         torch.save(d, path)
 
     @staticmethod
@@ -621,12 +700,16 @@ class GalleryIndex:
         """The index ``save`` wrote, on ``device``.  ``capacity``: (entries, keypoints[, edges]) -- the index
         is restored into storage of that size (as ``reserve`` makes it), without a second copy of it."""
         d = torch.load(path, map_location="cpu", weights_only=True)
-        if d.get("format") not in (FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8) or (
+        if d.get("format") not in (FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8, FORMAT_DESC) or (
                 d["format"] == FORMAT_TOMBSTONES and not ("removed" in d and "layout" in d)) or (
                 d["format"] == FORMAT_FP8 and not (d.get("layout") == FP8_LAYOUT and "y8" in d and "s8" in d)) or (
-                d["format"] != FORMAT_FP8 and d.get("layout") == FP8_LAYOUT):
-            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d, %d, %d or %d"
-                           % (path, FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8))
+                d["format"] not in (FORMAT_FP8, FORMAT_DESC) and d.get("layout") == FP8_LAYOUT) or (
+                d["format"] == FORMAT_DESC and not (d.get("layout") in LAYOUTS and "desc" in d and (
+                    d["layout"] != FP8_LAYOUT or ("y8" in d and "s8" in d)) and (
+                    d["layout"] not in BF16_LAYOUTS or "y16" in d))) or (
+                d["format"] != FORMAT_DESC and "desc" in d):
+            raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d, %d, %d, %d or %d"
+                           % (path, FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8, FORMAT_DESC))
         layout = d["layout"] if d["format"] != FORMAT else "f32"
         if layout == FP8_LAYOUT:
             d["y8"] = d["y8"].view(torch.float8_e4m3fn)
@@ -640,15 +723,15 @@ class GalleryIndex:
                                mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"],
                                y16=mv("y16") if layout in BF16_LAYOUTS else None, layout=layout,
                                subject=d.get("subject"), y8=mv("y8") if layout == FP8_LAYOUT else None,
-                               s8=mv("s8") if layout == FP8_LAYOUT else None)
+                               s8=mv("s8") if layout == FP8_LAYOUT else None, desc=mv("desc") if "desc" in d else None)
         else:
             G, R, E = int(d["n"].numel()), int(d["y"].shape[0]), int(d["src"].numel())
             cap = _check_capacity("GalleryIndex.load", capacity, G, R, E)
             dev = torch.device(device)
             with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-                st = _make_store(cap, layout, dev, "P" in d, "subject" in d)
+                st = _make_store(cap, layout, dev, "P" in d, "subject" in d, "desc" in d)
                 for key, k in (("y", R), ("y16", R), ("y8", R), ("s8", R), ("P", R), ("src", E), ("dst", E),
-                               ("pseudo", E), ("w", G),
+                               ("pseudo", E), ("w", G), ("desc", G),
                                ("n", G), ("edge_off", G + 1), ("subject", G)):
                     if st[key] is not None:
                         st[key][:k].copy_(d[key])
@@ -742,7 +825,7 @@ class GalleryIndex:
     def slice(self, entries, device=None):
         """A new GalleryIndex holding the entries ``entries`` (host int64, ascending, no repeats) in that
         order, on ``device`` (default: this index's): the rows (``y``, ``y16``, ``y8``, ``s8``, ``P``) and edges (``src``,
-        ``dst``, ``pseudo``) of those entries copied by their row and edge ranges, ``n``, ``w`` and ``subject``
+        ``dst``, ``pseudo``) of those entries copied by their row and edge ranges, ``n``, ``w``, ``desc`` and ``subject``
         by entry, the offsets rebuilt; layout, ``sc_mode``, ``_pack_gen`` and ``weights_id`` kept.  A
         "bf16+host" or "fp8+host" slice gets pinned host rows of its own.  Every field of the slice holds the parent's
         bytes for those entries (``ShardedGallery.split`` cuts an index into shards with it)."""
@@ -769,7 +852,8 @@ class GalleryIndex:
                             self.weights_id, y16=None if self.y16 is None else take(self.y16, rows_d),
                             layout=self.layout, subject=None if self.subject is None else self.subject[ent],
                             y8=None if self.y8 is None else take(self.y8, rows_d),
-                            s8=None if self.s8 is None else take(self.s8, rows_d))
+                            s8=None if self.s8 is None else take(self.s8, rows_d),
+                            desc=None if self.desc is None else take(self.desc, ent_d))
 
     def _selection(self, select, pad_to=None):
         """Side 1 of a probe x gallery batch over the entries ``select`` (None: all), in that order,
@@ -916,11 +1000,35 @@ def _edge_room(what, seen, room):
                        "index (GalleryIndex.reserve(..., edges=...))" % (what, seen, room))
 
 
-def _enroll_dicts(net, what, graphs, dev, sc_mode, batch, rows, r0, room=None):
+def _pool_new(desc, g0, rows, off_host, dev):
+    """The descriptors of a sub-batch's entries, whose packed fp32 rows ``rows`` (device) have the host offsets
+    ``off_host``, into desc[g0 : g0 + entries] (nothing without ``desc``): where the enrolment loops round those
+    rows to bf16 or quantise them to fp8."""
+    if desc is not None:
+        Bs = int(off_host.numel()) - 1
+        ops.rows_pool(rows, off_host.to(dev), 0, Bs, out=desc[g0:g0 + Bs], row_off_host=off_host)
+
+
+def _new_desc(descriptors, G, dev):
+    """The table an enrolment with ``descriptors`` pools its G new entries into, or None."""
+    return torch.empty(G, C.NODE_FEATURE_DIM, device=dev, dtype=torch.bfloat16) if descriptors else None
+
+
+def _into_descriptors(what, index, descriptors):
+    """An append pools the new entries exactly when the index holds descriptors; ``descriptors=True`` on an index
+    without them is refused."""
+    if descriptors and index.desc is None:
+        raise FpmError("%s: descriptors=True, but the index holds no descriptors; pool the index first "
+                       "(GalleryIndex.add_descriptors), or enrol it with descriptors=True" % what)
+    return index.desc is not None
+
+
+def _enroll_dicts(net, what, graphs, dev, sc_mode, batch, rows, r0, room=None, desc=None):
     """The enrolment loop of ``enroll`` and ``enroll_into``: the two SplineConv layers over the graph dicts in
     sub-batches of ``batch``, each sub-batch's ragged rows written from row ``r0`` on into ``rows``
     (``_alloc_rows`` / ``_store_rows``) -> the edges (graph-local src, dst, pseudo on the device, host counts
-    per graph).  ``room``: the edges the index has room for (None: a new index)."""
+    per graph).  ``room``: the edges the index has room for (None: a new index).  ``desc``: (len(graphs), 768) bf16
+    or None: the table each sub-batch's descriptors are pooled into (``_pool_new``)."""
     y, y16, y_host, y8, s8 = rows
     wp = net.packed(dev)
     srcs, dsts, pss, cnts, seen = [], [], [], [], 0
@@ -941,6 +1049,7 @@ def _enroll_dicts(net, what, graphs, dev, sc_mode, batch, rows, r0, room=None):
             ops.cast_bf16(yr, out=y16[r0:r1])
         if y8 is not None:
             ops.rows_quant8(yr, y8[r0:r1], s8[r0:r1])
+        _pool_new(desc, g0, yr, torch.cat([torch.zeros(1, dtype=torch.int64), n.long().cumsum(0)]), dev)
         if y_host is not None:
             y_host[r0:r1].copy_(yr, non_blocking=True)
         else:
@@ -965,16 +1074,17 @@ def _dict_tables(graphs, dev):
     return n_all, w, P
 
 
-def _empty_index(net, what, capacity, G, R, layout, dev, sc_mode, has_P, has_subject):
+def _empty_index(net, what, capacity, G, R, layout, dev, sc_mode, has_P, has_subject, has_desc=False):
     """An index of no entries over storage of ``capacity`` (checked against the G entries and R rows to come):
     ``enroll*(capacity=...)`` is an enrolment into it."""
     cap = _check_capacity(what, capacity, G, R)
     with torch.cuda.device(dev):
-        st = _make_store(cap, layout, dev, has_P, has_subject)
+        st = _make_store(cap, layout, dev, has_P, has_subject, has_desc)
         return GalleryIndex._over(st, 0, 0, 0, sc_mode, net._pack_gen, spline_weights_id(net), layout)
 
 
-def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None, capacity=None):
+def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None, capacity=None,
+           descriptors=False):
     """``Net.enroll``: the two SplineConv layers over ``graphs`` (dicts as ``fpm.synth.make_graph``
     returns: n, x, w, edge_index, pseudo, optionally P) in sub-batches of ``batch`` graphs -> GalleryIndex.
     ``layout`` (LAYOUTS): where the rows are kept.  The bf16 copy is rounded per sub-batch on the device
@@ -983,7 +1093,9 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
     host tensor, so the device holds the bf16 or fp8 rows plus one sub-batch at most.
     ``subjects``: one integer label >= 0 per graph (``GalleryIndex.subject``), checked before any GPU work;
     every other field of the index is the same with or without it.  ``capacity``: (entries, keypoints[,
-    edges]), the storage to enrol into (``GalleryIndex.reserve``'s sizes), for an index that will grow."""
+    edges]), the storage to enrol into (``GalleryIndex.reserve``'s sizes), for an index that will grow.
+    ``descriptors``: also pool each entry's prescreen descriptor (``GalleryIndex.desc``; ``ops.rows_pool`` over each
+    sub-batch's fp32 rows, the bits ``GalleryIndex.add_descriptors`` gives)."""
     sc_mode = _check_enroll(net, "enroll", layout, sc_mode)
     dev = torch.device(device)
     graphs = list(graphs)
@@ -994,20 +1106,22 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
     total = sum(int(g["n"]) for g in graphs)
     if capacity is not None:
         index = _empty_index(net, "enroll", capacity, len(graphs), total, layout, dev, sc_mode,
-                             all("P" in g for g in graphs), subjects is not None)
+                             all("P" in g for g in graphs), subjects is not None, bool(descriptors))
         enroll_into(net, index, graphs, batch=batch, subjects=subjects, what="enroll")
         index.generation, index._pack_gen = 0, net._pack_gen    # a new index: as the constructor call below records it
         return index
     with torch.cuda.device(dev):
         y, y16, y_host, y8, s8 = rows = _alloc_rows(layout, dev, total)
-        src, dst, ps, cnt = _enroll_dicts(net, "enroll", graphs, dev, sc_mode, batch, rows, 0)
+        desc = _new_desc(descriptors, len(graphs), dev)
+        src, dst, ps, cnt = _enroll_dicts(net, "enroll", graphs, dev, sc_mode, batch, rows, 0, desc=desc)
     n_all, w, P = _dict_tables(graphs, dev)
     row_off = torch.cat([torch.zeros(1, dtype=torch.int64), n_all.long().cumsum(0)])
     edge_off = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
     if y_host is not None:
         torch.cuda.current_stream(dev).synchronize()       # the host rows are complete before they are read
     return GalleryIndex(y if y_host is None else y_host, row_off.to(dev), n_all, src, dst, ps, edge_off, w, P, sc_mode,
-                        net._pack_gen, spline_weights_id(net), y16=y16, layout=layout, subject=subjects, y8=y8, s8=s8)
+                        net._pack_gen, spline_weights_id(net), y16=y16, layout=layout, subject=subjects, y8=y8, s8=s8,
+                        desc=desc)
 
 
 def _check_into(net, index, what):
@@ -1018,9 +1132,10 @@ def _check_into(net, index, what):
     _check_query(net, index, what)
 
 
-def enroll_into(net, index, graphs, batch=256, subjects=None, what="enroll_into"):
+def enroll_into(net, index, graphs, batch=256, subjects=None, what="enroll_into", descriptors=None):
     """``Net.enroll_into``: see there."""
     _check_into(net, index, what)
+    descriptors = _into_descriptors(what, index, descriptors)
     graphs = list(graphs)
     if not graphs:
         raise FpmError("%s: no graphs" % what)
@@ -1030,9 +1145,10 @@ def enroll_into(net, index, graphs, batch=256, subjects=None, what="enroll_into"
     n_all, w, P = _dict_tables(graphs, dev)
     at = index._begin_append(what, len(graphs), int(n_all.sum()), subjects, P is not None)
     with torch.cuda.device(dev):
+        desc = _new_desc(descriptors, len(graphs), dev)     # its own table until the commit: a failed append
         edges = _enroll_dicts(net, what, graphs, dev, index.sc_mode, batch, _store_rows(index), at[1],
-                              index.capacity[2] - at[2])
-        return index._finish_append(what, at, n_all, w, P, *edges, subjects)
+                              index.capacity[2] - at[2], desc=desc)       # leaves the index's descriptors as they were
+        return index._finish_append(what, at, n_all, w, P, *edges, subjects, desc=desc)
 
 
 def _check_enroll(net, what, layout, sc_mode):
@@ -1088,7 +1204,7 @@ def _device_of(device, *ts):
 
 
 def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, subjects=None, capacity=None,
-                   into=None):
+                   into=None, descriptors=False):
     """The enrolment loop of ``enroll_keypoints`` / ``enroll_images`` and their ``_into`` forms -> a new
     GalleryIndex, or (``into``: an index with capacity, whose ``sc_mode`` and layout are taken) the new
     entries' numbers.  ``feats(g0, g1, m)``:
@@ -1105,9 +1221,11 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
     row_off_h = torch.cat([torch.zeros(1, dtype=torch.int64), n_h.cumsum(0)])
     total = int(row_off_h[-1])
     if into is None and capacity is not None:
-        into = _empty_index(net, what, capacity, G, total, layout, dev, sc_mode, True, subjects is not None)
+        into = _empty_index(net, what, capacity, G, total, layout, dev, sc_mode, True, subjects is not None,
+                            bool(descriptors))
     base, room = 0, None
     if into is not None:
+        descriptors = _into_descriptors(what, into, descriptors)
         at = into._begin_append(what, G, total, subjects, True)
         sc_mode, layout, base, room = into.sc_mode, into.layout, at[1], into.capacity[2] - at[2]
     wp = net.packed(dev)
@@ -1122,6 +1240,7 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
             stage = torch.empty(max(int(row_off_h[min(G, g0 + step)] - row_off_h[g0]) for g0 in range(0, G, step)), D,
                                 device=dev, dtype=torch.float32)
         w_all = torch.empty(G, C.GLOBAL_FEATURE_DIM, device=dev, dtype=torch.float32)
+        desc = _new_desc(descriptors, G, dev)
         for g0 in range(0, G, step):
             g1 = min(G, g0 + step)
             Bs, nsub, nv = g1 - g0, n_h[g0:g1], n_d[g0:g1]
@@ -1144,6 +1263,7 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
                           out_off_host=row_off_h[g0:g1 + 1] - r0)
             if y8 is not None:
                 ops.rows_quant8(stage[:r1 - r0], y8[base + r0:base + r1], s8[base + r0:base + r1])
+            _pool_new(desc, g0, stage[:r1 - r0] if y is None else y[base + r0:base + r1], row_off_h[g0:g1 + 1] - r0, dev)
             if y_host is not None:
                 y_host[base + r0:base + r1].copy_(stage[:r1 - r0], non_blocking=True)
             srcs.append(gb.src % m)                          # edges back to graph-local ids
@@ -1155,7 +1275,7 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
         Pr = Pk[keep].to(dev)
         if into is not None:
             new = into._finish_append(what, at, n_h.to(torch.int32), w_all, Pr, torch.cat(srcs), torch.cat(dsts),
-                                      torch.cat(pss), torch.cat(cnts), subjects)
+                                      torch.cat(pss), torch.cat(cnts), subjects, desc=desc)
             if capacity is None:
                 return new
             into.generation, into._pack_gen = 0, net._pack_gen   # a new index: as the constructor call below records it
@@ -1165,7 +1285,7 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
             torch.cuda.current_stream(dev).synchronize()   # the host rows are complete before they are read
         return GalleryIndex(y if y_host is None else y_host, row_off, n_h.to(torch.int32), torch.cat(srcs),
                             torch.cat(dsts), torch.cat(pss), edge_off, w_all, Pr, sc_mode, net._pack_gen,
-                            spline_weights_id(net), y16=y16, layout=layout, subject=subjects, y8=y8, s8=s8)
+                            spline_weights_id(net), y16=y16, layout=layout, subject=subjects, y8=y8, s8=s8, desc=desc)
 
 
 def _keypoint_feats(x, w, dev):
@@ -1184,7 +1304,7 @@ def _image_feats(net, images, P, n_h):
 
 
 def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri", subjects=None,
-                     capacity=None):
+                     capacity=None, descriptors=False):
     """``Net.enroll_keypoints``: see there."""
     what = "enroll_keypoints"
     sc_mode = _check_enroll(net, what, layout, sc_mode)
@@ -1194,10 +1314,10 @@ def enroll_keypoints(net, P, n, x, w, device=None, sc_mode=None, batch=256, layo
     x, w = _feature_args(what, x, w, int(P.shape[0]), int(P.shape[1]))
     dev = _device_of(device, P, x)
     return _enroll_device(net, what, P, n_h, _keypoint_feats(x, w, dev), dev, sc_mode, batch, layout, stg, subjects,
-                          capacity)
+                          capacity, descriptors=descriptors)
 
 
-def enroll_keypoints_into(net, index, P, n, x, w, batch=256, stg="tri", subjects=None):
+def enroll_keypoints_into(net, index, P, n, x, w, batch=256, stg="tri", subjects=None, descriptors=None):
     """``Net.enroll_keypoints_into``: see there."""
     what = "enroll_keypoints_into"
     _check_into(net, index, what)
@@ -1207,7 +1327,7 @@ def enroll_keypoints_into(net, index, P, n, x, w, batch=256, stg="tri", subjects
     x, w = _feature_args(what, x, w, int(P.shape[0]), int(P.shape[1]))
     dev = index.device
     return _enroll_device(net, what, P, n_h, _keypoint_feats(x, w, dev), dev, None, batch, None, stg, subjects,
-                          into=index)
+                          into=index, descriptors=descriptors)
 
 
 def _check_images(what, images, G):
@@ -1218,7 +1338,7 @@ def _check_images(what, images, G):
 
 
 def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri", subjects=None,
-                  capacity=None):
+                  capacity=None, descriptors=False):
     """``Net.enroll_images``: see there."""
     what = "enroll_images"
     net._need_backbone()
@@ -1229,10 +1349,10 @@ def enroll_images(net, images, P, n, device=None, sc_mode=None, batch=256, layou
     images = _check_images(what, images, int(P.shape[0]))
     dev = _device_of(device, P, images)
     return _enroll_device(net, what, P, n_h, _image_feats(net, images, P, n_h), dev, sc_mode, batch, layout, stg,
-                          subjects, capacity)
+                          subjects, capacity, descriptors=descriptors)
 
 
-def enroll_images_into(net, index, images, P, n, batch=256, stg="tri", subjects=None):
+def enroll_images_into(net, index, images, P, n, batch=256, stg="tri", subjects=None, descriptors=None):
     """``Net.enroll_images_into``: see there."""
     what = "enroll_images_into"
     net._need_backbone()
@@ -1242,7 +1362,7 @@ def enroll_images_into(net, index, images, P, n, batch=256, stg="tri", subjects=
     P, n_h = _keypoint_args(what, P, n)
     images = _check_images(what, images, int(P.shape[0]))
     return _enroll_device(net, what, P, n_h, _image_feats(net, images, P, n_h), index.device, None, batch, None, stg,
-                          subjects, into=index)
+                          subjects, into=index, descriptors=descriptors)
 
 
 def probe_graphs(net, P, n, x=None, w=None, images=None, device=None, stg="tri"):
@@ -1686,7 +1806,7 @@ def _attach(outs, keys):
 
 def _shortlist(call, sel, M, own=None, gt=None, impressions="all"):
     """The shortlist stage of every query form.  ``call`` (Q, Gs): the coarse scores of Q probes over the
-    selection ``sel`` (Gs,) host int64; ``M``: the shortlist asked for, clamped here to what there is;
+    selection ``sel`` (Gs,) host int64 -- or, after a prescreen, (Q, Gs): each probe's own list --; ``M``: the shortlist asked for, clamped here to what there is;
     ``own`` (Q, Gs) host bool or None: positions that count as -inf and are left out (the probe's own
     entry); ``gt``: the selection's group tables (``subject_groups``) for a shortlist of subjects -- the
     coarse scores fused per subject by max whatever the exact stage's fuse is (a subject stays in if any
@@ -1700,16 +1820,54 @@ def _shortlist(call, sel, M, own=None, gt=None, impressions="all"):
     dev = call.device
     ranked = call if own is None else call.masked_fill(own.to(dev), float("-inf"))
     if gt is None:
-        M = min(M, int(sel.numel()) - (own is not None))
+        M = min(M, int(sel.shape[-1]) - (own is not None))
     else:
         M = min(M, int(gt["labels"].numel()))
         ranked, cb = ops.group_scores(ranked, gt["off_d"], gt["pos_d"], "max", off_host=gt["off"], pos_host=gt["pos"])
     pos, csc = ops.rank_select(ranked, M)
     if gt is None:
-        names = sel.to(dev)[pos.long()]
+        names = sel.to(dev)[pos.long()] if sel.dim() == 1 else torch.gather(sel.to(dev), 1, pos.long())
         return list(names.cpu()), None, names, csc
     lists = _subject_entry_lists(gt, pos.cpu(), cb.cpu() if impressions == "best" else None, own)
     return [sel[p] for p, _ in lists], [so for _, so in lists], gt["labels_d"][pos.long()], csc
+
+
+def _check_prescreen(what, index, prescreen, shortlist, by):
+    """The refusals of ``prescreen=K`` (before any GPU work) -> K, or None without a prescreen."""
+    from .sharded_gallery import ShardedGallery
+    if prescreen is None:
+        return None
+    if isinstance(index, ShardedGallery):
+        raise FpmError("%s: prescreen is not supported over a ShardedGallery" % what)
+    if shortlist is None:
+        raise FpmError("%s: prescreen needs a shortlist (it narrows the coarse pass of shortlist=M)" % what)
+    if isinstance(prescreen, bool) or not isinstance(prescreen, int) or prescreen < int(shortlist):
+        raise FpmError("%s: prescreen = %r must be an integer >= shortlist = %d" % (what, prescreen, int(shortlist)))
+    if by is not None:
+        raise FpmError("%s: prescreen with by=%r is not supported (the group tables would differ from probe to probe)"
+                       % (what, by))
+    if isinstance(index, GalleryIndex) and index.desc is None:
+        raise FpmError("%s: prescreen needs descriptors on the index: GalleryIndex.add_descriptors(), or "
+                       "enroll*(descriptors=True)" % what)
+    return prescreen
+
+
+def _prescreen(dq, index, sel, K, own=None):
+    """The prescreen stage: ``ops.desc_score`` of the probes' descriptors ``dq`` (Q, 768) bf16 over the selection
+    ``sel`` (Gs,) host int64 of an index with descriptors, ``own`` (Q, Gs) host bool or None: positions that count
+    as -inf (the probe's own entry), ``ops.rank_keep`` to the K best, K clamped to the candidates there are
+    -> (lists (Q, K) host int64: each probe's entry numbers in the selection's order, the same as int32 on the
+    device, their descriptor scores (Q, K))."""
+    dev = index.device
+    sel32 = sel.to(torch.int32)
+    sel_d = sel32.to(dev)
+    sc = ops.desc_score(dq, index.desc, sel_d, idx_host=sel32)
+    if own is not None:
+        sc = sc.masked_fill(own.to(dev), float("-inf"))
+    K = max(1, min(int(K), int(sel.numel()) - (own is not None)))
+    keep = ops.rank_keep(sc, K).long()
+    pre_idx = sel_d[keep]
+    return pre_idx.long().cpu(), pre_idx, torch.gather(sc, 1, keep)
 
 
 def _check_eager(net, what):
@@ -1722,9 +1880,10 @@ def _check_eager(net, what):
 
 def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=None, shortlist=None,
              coarse="fused", by=None, fuse="max", impressions="all", top_r=None, normalize=None, cohort=32,
-             cohort_skip=1, sigma_floor=1e-6, threshold=None, coarse_all=True):
+             cohort_skip=1, sigma_floor=1e-6, threshold=None, coarse_all=True, prescreen=None):
     """``Net.identify``: see there."""
     from .sharded_gallery import ShardedGallery, identify_sharded
+    K = _check_prescreen("identify", index, prescreen, shortlist, by)
     if isinstance(index, ShardedGallery):
         return identify_sharded(net, probes, index, topk=topk, select=select, score=score, chunks=chunks,
                                 shortlist=shortlist, coarse=coarse, by=by, fuse=fuse, impressions=impressions,
@@ -1748,12 +1907,30 @@ def identify(net, probes, index, topk=10, select=None, score="cls_prob", chunks=
         gt = index.subject_groups(sel) if subj else None
         if not plist:
             return []
-        call = coarse_scores(net, plist, index, select=sel, coarse=coarse)
+        pre = {}
+        if K is not None:
+            # the probes' descriptors from their own rows, the K best entries of each by descriptor score, and the
+            # coarse pass over each probe's own K entries and no others
+            wp = net.packed(dev)
+            with torch.cuda.device(dev):
+                dq = torch.empty(len(plist), C.NODE_FEATURE_DIM, device=dev, dtype=torch.bfloat16)
+                for i, p in enumerate(plist):
+                    yp = net._probe_rows(wp, _ProbeSide(p, index))
+                    one = torch.tensor([0, int(yp.shape[0])], dtype=torch.int64)
+                    ops.rows_pool(yp, one.to(dev), 0, 1, out=dq[i:i + 1], row_off_host=one)
+                sel, pre_idx, pre_score = _prescreen(dq, index, sel, K)
+                call = torch.empty(len(plist), int(sel.shape[1]), device=dev, dtype=torch.float32)
+                for i, p in enumerate(plist):
+                    _coarse_one(net, wp, p, index, sel[i], pre_idx[i].contiguous(), call[i], COARSE_CHUNK, coarse)
+            pre = dict(pre_idx=pre_idx, pre_score=pre_score)
+        else:
+            call = coarse_scores(net, plist, index, select=sel, coarse=coarse)
         with torch.cuda.device(dev):
             ents, offs, names, csc = _shortlist(call, sel, M, gt=gt, impressions=impressions)
         # the exact stage, a probe at a time: the plain ``identify`` over its list alone, in that order
         outs = [identify(net, p, index, topk=topk, select=e, score=score, chunks=chunks) for p, e in zip(plist, ents)]
         keys = _shortlist_keys(subj, names, csc, call)
+        keys.update(pre)
         with torch.cuda.device(dev):
             if subj:
                 keys.update(_subject_ranking([o[score] for o in outs], ents, offs, names, fuse, topk, dev, top_r))
@@ -1888,11 +2065,17 @@ def coarse_scores_many(net, probes, index, probe_select=None, select=None, coars
     _check_many(net, probes, index, "coarse_scores_many")
     psel = _select_host(probes, probe_select, "coarse_scores_many (probe_select)")
     sel = _select_host(index, select, "coarse_scores_many")
-    nq, ng = probes.n[psel].long(), index.n[sel].long()
+    return _coarse_many(net, probes, index, psel, sel, coarse)
+
+
+def _coarse_many(net, probes, index, psel, sel, coarse):
+    """The pair-list coarse pass of the probes ``psel`` (Qs,) over the entries ``sel``: (Gs,) host int64, one
+    selection for all probes, or (Qs, Gs), each probe's own list (after a prescreen) -> (Qs, Gs) scores."""
+    nq, ng = probes.n[psel].long(), index.n[sel.reshape(-1)].long().view(sel.shape)
     _check_route_bounds(max(int(nq.max()), int(ng.max())), min(int(nq.min()), int(ng.min())), coarse)
     dev = index.device
     wp = net.packed(dev)
-    Qs, Gs = int(psel.numel()), int(sel.numel())
+    Qs, Gs = int(psel.numel()), int(sel.shape[-1])
     total = Qs * Gs
     out = torch.empty(Qs, Gs, device=dev, dtype=torch.float32)
     flat = out.view(-1)                      # pair (i, j) at i * Gs + j: a launch's pairs are one slice of it
@@ -1905,8 +2088,8 @@ def coarse_scores_many(net, probes, index, probe_select=None, select=None, coars
             p1 = min(total, p0 + step)
             qi, gi, where = _coarse_pairs_order(p0, p1, Qs, Gs)
             dst = flat[p0:p1] if where is None else torch.empty(p1 - p0, device=dev, dtype=torch.float32)
-            q, g = psel[qi], sel[gi]
-            rt = coarse_routes(nq[qi], ng[gi], coarse)
+            q, g = psel[qi], sel[gi] if sel.dim() == 1 else sel[qi, gi]
+            rt = coarse_routes(nq[qi], ng[gi] if sel.dim() == 1 else ng[qi, gi], coarse)
             cf = _coef_rows(wp, probes.w[q.to(dev)].contiguous(), index.w[g.to(dev)].contiguous(), coef)
             q32, g32 = q.to(torch.int32), g.to(torch.int32)
 
@@ -1992,13 +2175,14 @@ def _exact_many(net, probes, index, psel, ents, score, chunks, group_pairs):
 def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
                   coarse="fused", chunks=None, group_pairs=1024, exclude_self=False, by=None, fuse="max",
                   impressions="all", top_r=None, normalize=None, cohort=32, cohort_skip=1, sigma_floor=1e-6,
-                  threshold=None):
+                  threshold=None, prescreen=None):
     """``Net.identify_many``: see there.  Subject-level (``by="subject"``) the exact stage's pair lists are
     ragged (a subject has as many pairs as impressions) and the exact scores are fused over one structure
     per probe (``_subject_ranking``).  ``exclude_self`` is then leave-one-out: the probe's own entry counts
     as -inf in the coarse fuse and is left out of its pair list and of its group; its subject's other
     impressions stay, and a subject emptied that way ranks last (NaN)."""
     what = "identify_many"
+    K = _check_prescreen(what, index, prescreen, shortlist, by)
     _check_coarse(coarse, what)
     subj = _check_by(what, index, by, fuse, impressions, shortlist)
     opt = _check_open(what, subj, fuse, top_r, normalize, cohort, cohort_skip, sigma_floor, threshold)
@@ -2020,8 +2204,22 @@ def identify_many(net, probes, index, topk=10, shortlist=None, probe_select=None
     with torch.cuda.device(dev):
         if shortlist is not None:
             M = _check_shortlist(shortlist, what)
-            call = coarse_scores_many(net, probes, index, probe_select=psel, select=sel, coarse=coarse)
-            ents, offs, names, csc = _shortlist(call, sel, M, own, gt, impressions)
+            if K is not None:
+                # the probe set's descriptors if it holds them, else its selected probes' rows pooled here; own
+                # entries are out after the prescreen (K is clamped below the candidates), so none is in a list
+                if probes.desc is not None:
+                    dq = probes.desc[psel.to(dev)].contiguous()
+                else:
+                    lo, hi = int(psel.min()), int(psel.max()) + 1
+                    dq = ops.rows_pool(probes.y, probes.row_off, lo, hi, row_off_host=probes.row_off_host)
+                    dq = dq[(psel - lo).to(dev)].contiguous()
+                lists, pre_idx, pre_score = _prescreen(dq, index, sel, K, own)
+                call = _coarse_many(net, probes, index, psel, lists, coarse)
+                ents, offs, names, csc = _shortlist(call, lists, M)
+                keys.update(pre_idx=pre_idx, pre_score=pre_score)
+            else:
+                call = coarse_scores_many(net, probes, index, probe_select=psel, select=sel, coarse=coarse)
+                ents, offs, names, csc = _shortlist(call, sel, M, own, gt, impressions)
             keys.update(_shortlist_keys(subj, names, csc, call))
         else:
             if own is not None and not subj and not bool((own.sum(1) == 1).all()):

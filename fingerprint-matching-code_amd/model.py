@@ -1465,7 +1465,8 @@ class Net(nn.Module):
                                 chunk_timeline_ms=timeline)
         return res
 
-    def enroll(self, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None, capacity=None):
+    def enroll(self, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=None, capacity=None,
+               descriptors=False):
         """Enrol a gallery for 1:N identification (inference only): run the two SplineConv layers over
         ``graphs`` (dicts as ``fpm.synth.make_graph`` returns) once, in sub-batches of ``batch``, and
         keep their fp32 output rows -> ``fpm.gallery.GalleryIndex`` (3 KB per keypoint).  ``sc_mode``:
@@ -1494,12 +1495,18 @@ class Net(nn.Module):
 
         ``capacity``: (entries, keypoints[, edges]) -- enrol into storage of that size (the sizes of
         ``GalleryIndex.reserve``), so that ``enroll_into`` can add entries later and a large index need not
-        be copied once to become mutable.  Every field is the same with or without it."""
+        be copied once to become mutable.  Every field is the same with or without it.
+
+        ``descriptors=True``: also keep one prescreen descriptor per entry (``GalleryIndex.desc``, (G, 768) bf16 on
+        the device, 1536 B per entry): the entry's fp32 rows sum-pooled and L2-normalised (``ops.rows_pool``), pooled
+        per sub-batch where the rows are rounded to bf16 or quantised to fp8.  ``identify(prescreen=K)`` needs them;
+        ``GalleryIndex.add_descriptors`` pools an existing index to the same bits.  Every other field is the same
+        with or without it."""
         from . import gallery
         return gallery.enroll(self, graphs, device, sc_mode=sc_mode, batch=batch, layout=layout, subjects=subjects,
-                              capacity=capacity)
+                              capacity=capacity, descriptors=descriptors)
 
-    def enroll_into(self, index, graphs, batch=256, subjects=None):
+    def enroll_into(self, index, graphs, batch=256, subjects=None, descriptors=None):
         """Enrol ``graphs`` (dicts, as ``enroll`` takes them) into ``index``, an index with capacity
         (``GalleryIndex.reserve``, ``enroll*(capacity=...)``) -> the new entries' numbers (host int64).  The
         loop is ``enroll``'s, with the index's own layout and ``sc_mode``; the new rows are written into the
@@ -1510,24 +1517,31 @@ class Net(nn.Module):
         ``subjects`` missing on a labelled index or given on an unlabelled one, graphs with keypoints ``P``
         on an index without them and the reverse, entries or rows over capacity.  An overflow of the edge
         capacity, or any error, midway raises ``FpmError`` and leaves the index as it was.  To grow a
-        full index, ``reserve`` a bigger one."""
-        from . import gallery
-        return gallery.enroll_into(self, index, graphs, batch=batch, subjects=subjects)
+        full index, ``reserve`` a bigger one.
 
-    def enroll_keypoints_into(self, index, P, n, x, w, batch=256, stg="tri", subjects=None):
+        An index that holds descriptors (``GalleryIndex.desc``) always gets the new entries' descriptors, pooled
+        as ``enroll(descriptors=True)`` pools them and written at the commit; ``descriptors=True`` on an index
+        without them is refused (``GalleryIndex.add_descriptors`` pools an index first)."""
+        from . import gallery
+        return gallery.enroll_into(self, index, graphs, batch=batch, subjects=subjects, descriptors=descriptors)
+
+    def enroll_keypoints_into(self, index, P, n, x, w, batch=256, stg="tri", subjects=None, descriptors=None):
         """``enroll_into`` from keypoints and features on the device: the loop of ``enroll_keypoints`` (one
         ``ops.rows_pack`` per sub-batch, straight into the index's free rows).  The edge count of graphs
-        built on the device is known only per sub-batch, so the index is committed at the end."""
+        built on the device is known only per sub-batch, so the index is committed at the end.
+        ``descriptors``: as ``enroll_into``."""
         from . import gallery
-        return gallery.enroll_keypoints_into(self, index, P, n, x, w, batch=batch, stg=stg, subjects=subjects)
+        return gallery.enroll_keypoints_into(self, index, P, n, x, w, batch=batch, stg=stg, subjects=subjects,
+                                             descriptors=descriptors)
 
-    def enroll_images_into(self, index, images, P, n, batch=256, stg="tri", subjects=None):
+    def enroll_images_into(self, index, images, P, n, batch=256, stg="tri", subjects=None, descriptors=None):
         """``enroll_keypoints_into`` from images (needs ``Net(backbone=True)``)."""
         from . import gallery
-        return gallery.enroll_images_into(self, index, images, P, n, batch=batch, stg=stg, subjects=subjects)
+        return gallery.enroll_images_into(self, index, images, P, n, batch=batch, stg=stg, subjects=subjects,
+                                          descriptors=descriptors)
 
     def enroll_keypoints(self, P, n, x, w, device=None, sc_mode=None, batch=256, layout="f32", stg="tri",
-                         subjects=None, capacity=None):
+                         subjects=None, capacity=None, descriptors=False):
         """``enroll`` from keypoints and features, on the device: no host graph dicts.  P: (G, nmax, 2)
         fp32 padded keypoints, n: (G,) counts in [1, nmax], x: (G, nmax, 768) or (G * nmax, 768) fp32
         node features (padding rows are ignored), w: (G, 512) global features; tensors or arrays, host
@@ -1538,19 +1552,20 @@ class Net(nn.Module):
         writes the sub-batch's ragged rows -- fp32, bf16 or both, by ``layout`` -- into their place in
         the index, whose rows are allocated once: the device peak is the index plus one sub-batch.
         -> ``GalleryIndex``, every field equal to ``enroll`` on the same graphs as host dicts with the
-        same ``batch``.  ``sc_mode`` / ``layout`` / ``subjects`` / ``capacity``: as ``enroll``."""
+        same ``batch``.  ``sc_mode`` / ``layout`` / ``subjects`` / ``capacity`` / ``descriptors``: as ``enroll``
+        (the descriptors are pooled from each sub-batch's packed rows)."""
         from . import gallery
         return gallery.enroll_keypoints(self, P, n, x, w, device=device, sc_mode=sc_mode, batch=batch, layout=layout,
-                                        stg=stg, subjects=subjects, capacity=capacity)
+                                        stg=stg, subjects=subjects, capacity=capacity, descriptors=descriptors)
 
     def enroll_images(self, images, P, n, device=None, sc_mode=None, batch=256, layout="f32", stg="tri",
-                      subjects=None, capacity=None):
+                      subjects=None, capacity=None, descriptors=False):
         """``enroll_keypoints`` from images (needs ``Net(backbone=True)``): images (G, 3, H, W), P and n as
         there.  Per sub-batch ``image_features`` (backbone + feature_align, one side) makes x and w, so
         the backbone's memory is bounded by ``batch``."""
         from . import gallery
         return gallery.enroll_images(self, images, P, n, device=device, sc_mode=sc_mode, batch=batch, layout=layout,
-                                     stg=stg, subjects=subjects, capacity=capacity)
+                                     stg=stg, subjects=subjects, capacity=capacity, descriptors=descriptors)
 
     def probe_graphs(self, P, n, x=None, w=None, images=None, device=None, stg="tri"):
         """Probe graphs for ``identify`` / ``coarse_scores`` from keypoints, on the device -> a list of
@@ -1588,7 +1603,7 @@ class Net(nn.Module):
 
     def identify(self, probes, index, topk=10, select=None, shortlist=None, score="cls_prob", chunks=None,
                  coarse="fused", by=None, fuse="max", impressions="all", top_r=None, normalize=None, cohort=32,
-                 cohort_skip=1, sigma_floor=1e-6, threshold=None, coarse_all=True):
+                 cohort_skip=1, sigma_floor=1e-6, threshold=None, coarse_all=True, prescreen=None):
         """1:N identification against an enrolled gallery: for each probe graph (one dict, or a list)
         the shared-probe forward over the gallery entries ``select`` (an index list; default all),
         with side 1's operand rows gathered from ``index`` (no SplineConv for the gallery side) --
@@ -1608,6 +1623,18 @@ class Net(nn.Module):
         picks the coarse pass's kernel: the default takes boxes of at most 128 keypoints, "wide" and
         "auto" boxes of at most 256, "stream" and "any" boxes of at most 600 (every graph the matcher
         takes); without a shortlist it is only checked: the full query has no size bound.
+
+        ``shortlist=M, prescreen=K`` (K an integer >= M; an index with descriptors: ``enroll(descriptors=True)`` or
+        ``GalleryIndex.add_descriptors``; opt-in, and without it everything above is unchanged): an indexing stage
+        in front of the coarse pass, whose cost is linear in the gallery.  The probe's descriptor is its own
+        SplineConv rows sum-pooled and L2-normalised (``ops.rows_pool``), scored against the descriptors of
+        ``select`` at memory bandwidth (``ops.desc_score``); the K best entries by that score (``ops.rank_keep``; K
+        clamped to the selection) go on, in entry order, and the coarse pass, the shortlist and the exact forward
+        run over those alone: every output equals ``identify(probe, index, shortlist=M, select=pre_idx)`` bit for
+        bit.  The dict then also carries ``pre_idx`` (K, int32 entry numbers, ascending) and ``pre_score`` (K), and
+        ``coarse_all`` is (K,), aligned with ``pre_idx``.  What the descriptor costs in recall on trained weights is
+        not measured here.  Refused before any GPU work: ``prescreen`` without ``shortlist``, a K that is not an
+        integer >= M, an index without descriptors, ``by="subject"`` and a ``ShardedGallery``.
 
         On a "bf16+host" index (``enroll(layout=...)``) the coarse pass reads the bf16 rows on the
         device and the forward runs over the selected entries' fp32 rows, copied from pinned host
@@ -1679,7 +1706,8 @@ class Net(nn.Module):
         return gallery.identify(self, probes, index, topk=topk, select=select, score=score, chunks=chunks,
                                 shortlist=shortlist, coarse=coarse, by=by, fuse=fuse, impressions=impressions,
                                 top_r=top_r, normalize=normalize, cohort=cohort, cohort_skip=cohort_skip,
-                                sigma_floor=sigma_floor, threshold=threshold, coarse_all=coarse_all)
+                                sigma_floor=sigma_floor, threshold=threshold, coarse_all=coarse_all,
+                                prescreen=prescreen)
 
     # Probe sets: a *probe set* is a GalleryIndex enrolled from the probe graphs (``enroll``), with its
     # fp32 rows on the device (layout "f32" or "f32+bf16"), on the gallery's device, enrolled with the
@@ -1710,7 +1738,7 @@ class Net(nn.Module):
     def identify_many(self, probes, index, topk=10, shortlist=None, probe_select=None, select=None, score="cls_prob",
                       coarse="fused", chunks=None, group_pairs=1024, exclude_self=False, by=None, fuse="max",
                       impressions="all", top_r=None, normalize=None, cohort=32, cohort_skip=1, sigma_floor=1e-6,
-                      threshold=None):
+                      threshold=None, prescreen=None):
         """1:N identification of a whole probe set -> a list of dicts, one per probe of ``probe_select``
         (default all), in that order.  ``coarse_scores_many``, ``ops.rank_select`` to the ``shortlist``
         best entries per probe, one host copy of all shortlists, then the exact forward in *groups* of
@@ -1730,6 +1758,15 @@ class Net(nn.Module):
         ``exclude_self`` (only with ``probes is index``: de-duplicating a gallery): the pair (q, entry
         q) is left out: its coarse score counts as -inf in the ranking (``coarse_all`` keeps it) and
         the shortlist is clamped to len(select) - 1.
+
+        ``shortlist=M, prescreen=K``: the prescreen of ``identify`` for the whole probe set.  The probes' descriptors
+        are the probe set's own (``desc``) when it holds them, else its selected probes' rows pooled per call; one
+        ``ops.desc_score`` over the selection, ``ops.rank_keep`` to each probe's K best entries (under
+        ``exclude_self`` the probe's own position counts as -inf and K is clamped to len(select) - 1), the coarse
+        pass over pair lists of those Q x K pairs and no others, and the shortlist over each probe's own list.
+        Adds ``pre_idx`` (K, int32, ascending) and ``pre_score`` (K) per probe; ``coarse_all`` is (K,), aligned with
+        ``pre_idx``.  Probe by probe the query keys equal ``identify_many(probe_select=[q], select=pre_idx)``.
+        Refused as in ``identify``.
 
         ``by="subject"`` / ``fuse`` / ``impressions``: as ``identify``, with ``subjects`` the subjects of
         ``subject_score`` (the M shortlisted ones, or all S).  A probe's pair list is ragged under
@@ -1752,7 +1789,8 @@ class Net(nn.Module):
                                      select=select, score=score, coarse=coarse, chunks=chunks,
                                      group_pairs=group_pairs, exclude_self=exclude_self, by=by, fuse=fuse,
                                      impressions=impressions, top_r=top_r, normalize=normalize, cohort=cohort,
-                                     cohort_skip=cohort_skip, sigma_floor=sigma_floor, threshold=threshold)
+                                     cohort_skip=cohort_skip, sigma_floor=sigma_floor, threshold=threshold,
+                                     prescreen=prescreen)
 
     def _need_backbone(self):
         if not hasattr(self, "node_layers"):

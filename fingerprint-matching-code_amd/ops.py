@@ -2,7 +2,8 @@
 
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
-no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``topk_merge``,
+no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``rank_keep``,
+``rows_pool``, ``desc_score``, ``topk_merge``,
 ``group_scores``, ``group_topr``, ``cohort_decide``, ``coarse_score`` / ``coarse_pairs``, ``rows_fetch``,
 ``rows_pack``, ``rows_move`` and ``rows_quant8`` alone keep a plain-torch host path for CPU tensors: the statements
 of the ordering and of the merge of
@@ -754,6 +755,184 @@ def rank_select(scores, k, top_idx=None, top_score=None):
     ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
     _lib.call("fpm_rank_select", _p(scores), ld, P, G, k, _p(top_idx), _p(top_score), _p(ws), wsb, _stream(scores))
     return top_idx, top_score
+
+
+def rank_keep(scores, k, keep=None):
+    """The k best columns of every row as a set, in ascending column order, for any 1 <= k <= G (fpm_rank_keep;
+    the prescreen of a 1:N identification): scores (P, G) fp32 (any row stride) -> keep (P, k) int32.  The
+    ranking is ``rank_select``'s (``rank_key``: score descending, ties to the lower column, NaN after every
+    number), so for k <= 1024 ``keep`` holds ``rank_select``'s indices, sorted.  Device tensors run the kernel
+    (``rank_select``'s radix search for the k-th key, then an ordered compaction: counts per slice, their
+    prefix, ballots; no atomics hand out a slot); CPU tensors take the statement: a stable descending sort on the
+    key, the first k, sorted by column.  Keys are unique, so the two agree bit for bit."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
+        raise _lib.FpmError("rank_keep: scores must be a (P, G) fp32 tensor")
+    P, G = int(scores.shape[0]), int(scores.shape[1])
+    k = int(k)
+    if not 1 <= k <= G:
+        raise _lib.FpmError("rank_keep: k = %d outside [1, G = %d]" % (k, G))
+    if P > 65535:
+        raise _lib.FpmError("rank_keep: at most 65535 rows per call")
+    if keep is not None:
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.int32 or not keep.is_contiguous() \
+                or keep.device != scores.device:
+            raise _lib.FpmError("rank_keep: keep must be contiguous int32 on the scores' device")
+        _shape(keep, (P, k), "rank_keep keep")
+    if not scores.is_cuda:
+        order = torch.argsort(rank_key(scores), dim=1, descending=True, stable=True)[:, :k]
+        res = torch.sort(order, dim=1).values.to(torch.int32)
+        return res if keep is None else keep.copy_(res)
+    if G > 1 and scores.stride(1) != 1:
+        scores = scores.contiguous()
+    ld = int(scores.stride(0)) if P > 1 else G
+    if ld < G:
+        scores, ld = scores.contiguous(), G
+    if keep is None:
+        keep = torch.empty(P, k, device=scores.device, dtype=torch.int32)
+    if P == 0:
+        return keep
+    # scratch of this call alone, allocated on the caller's stream (histograms, prefix states, the slices' counts)
+    wsb = int(_lib.load().fpm_rank_keep_ws_bytes(P, G))
+    ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
+    _lib.call("fpm_rank_keep", _p(scores), ld, P, G, k, _p(keep), _p(ws), wsb, _stream(scores))
+    return keep
+
+
+DESC_DIM = 768
+POOL_THREADS = 192             # rows_pool: a thread per four channels
+POOL_TREE = 256                # rows_pool: the norm's tree runs over this many partial sums
+
+
+def _rows_pool_host(y, off):
+    """The definition of a template's descriptor in plain torch: y (R, 768) fp32, off (E + 1,) host int64 -> (E, 768)
+    bf16; see ``rows_pool``."""
+    E = int(off.numel()) - 1
+    n = off[1:] - off[:-1]
+    m = torch.zeros(E, DESC_DIM, dtype=torch.float32)
+    zero = torch.zeros((), dtype=torch.float32)
+    for i in range(int(n.max()) if E else 0):
+        on = i < n                                               # a sum that started at +0.0 is never -0.0: + 0.0 is exact
+        m = m + torch.where(on[:, None], y[torch.where(on, off[:-1] + i, torch.zeros_like(n))], zero)
+    md = m.to(torch.float64)
+    q = (md * md).view(E, POOL_THREADS, 4)
+    p = torch.zeros(E, POOL_TREE, dtype=torch.float64)
+    p[:, :POOL_THREADS] = ((q[:, :, 0] + q[:, :, 1]) + q[:, :, 2]) + q[:, :, 3]
+    o = POOL_TREE // 2
+    while o:
+        p = p[:, :o] + p[:, o:2 * o]
+        o //= 2
+    ss = p[:, 0]
+    ok = (ss > 0) & torch.isfinite(ss)
+    r = torch.sqrt(torch.where(ok, ss, torch.ones_like(ss)))
+    d = (md / r[:, None]).to(torch.float32).to(torch.bfloat16)
+    return torch.where(ok[:, None], d, torch.zeros_like(d))
+
+
+def rows_pool(y, row_off, lo=0, hi=None, out=None, row_off_host=None):
+    """The prescreen descriptors of the entries [lo, hi) of a ragged row store (fpm_rows_pool) -> (hi - lo, 768)
+    bf16: y (R, 768) fp32 and row_off (G + 1,) int64 on one device (entry g = rows row_off[g] .. row_off[g + 1]);
+    ``hi`` None: G.  Per entry of n rows:
+
+        m[c] = the fp32 sum of y[i, c] over i ascending, one running sum per channel from +0.0;
+        ss   = the fp64 sum of double(m[c])^2 in a fixed order: p[t] = ((m[4t]^2 + m[4t+1]^2) + m[4t+2]^2) +
+               m[4t+3]^2 for t < POOL_THREADS = 192, p[192 .. 256) = 0, then for o = 128, 64, .. 1:
+               p[t] += p[t + o] for t < o; ss = p[0];
+        r    = sqrt(ss) in fp64;  d[c] = bf16_rne(float(double(m[c]) / r)).
+
+    ss == 0 or not finite gives an all-zero descriptor.  Every step is one correctly rounded IEEE operation, so
+    the kernel (device tensors) and the statement above in torch (CPU tensors) give the same bits.  Checked on
+    the host before anything is launched: dtypes, contiguity, devices, 0 <= lo <= hi <= G and offsets that rise
+    from 0 to R (``row_off_host``: a host copy, so the check needs no device synchronisation)."""
+    op = "rows_pool"
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != DESC_DIM \
+            or not y.is_contiguous():
+        raise _lib.FpmError("%s: y must be contiguous fp32 rows of 768 channels" % op)
+    _check_index_tensors(op, (("row_off", row_off, torch.int64),))
+    _check_on_device_of(op, y, (("row_off", row_off), ("out", out)))
+    G = int(row_off.numel()) - 1
+    if G < 0:
+        raise _lib.FpmError("%s: row_off must hold G + 1 >= 1 offsets" % op)
+    hi = G if hi is None else int(hi)
+    lo = int(lo)
+    if not 0 <= lo <= hi <= G:
+        raise _lib.FpmError("%s: entries [%d, %d) outside the index's [0, %d]" % (op, lo, hi, G))
+    oh = _host_copy(row_off_host, row_off)
+    if oh.numel() != G + 1 or not _offsets_rise(oh, y):
+        raise _lib.FpmError("%s: row_off must rise from 0 to the %d rows of y" % (op, y.shape[0]))
+    if out is None:
+        out = torch.empty(hi - lo, DESC_DIM, device=y.device, dtype=torch.bfloat16)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise _lib.FpmError("%s: out must be a contiguous bfloat16 tensor" % op)
+    _shape(out, (hi - lo, DESC_DIM), "%s out" % op)
+    if hi == lo:
+        return out
+    if y.data_ptr() & 15 or out.data_ptr() & 7:
+        raise _lib.FpmError("%s: y must be 16-byte aligned, out 8-byte aligned" % op)
+    if not y.is_cuda:
+        return out.copy_(_rows_pool_host(y, oh[lo:hi + 1]))
+    _lib.call("fpm_rows_pool", _p(y), int(y.shape[0]), _p(row_off), lo, hi, _p(out), _stream(y))
+    return out
+
+
+def _desc_score_host(dq, dg, dtype):
+    """score[q, b] = sum_c dq[q, c] dg[b, c] in ``dtype`` arithmetic, c ascending, one product and one add per
+    channel (a product of two bf16 values is exact in fp32)."""
+    a, b = dq.to(dtype), dg.to(dtype)
+    acc = torch.zeros(a.shape[0], b.shape[0], dtype=dtype)
+    for c in range(DESC_DIM):
+        acc = acc + a[:, c, None] * b[None, :, c]
+    return acc
+
+
+def desc_score(dq, dg, idx=None, out=None, idx_host=None, dtype=None):
+    """Descriptor scores, probes x entries (fpm_desc_score) -> (Q, B) fp32: score[q, b] = sum_c dq[q, c] *
+    dg[idx[b], c] for descriptors dq (Q, 768) and dg (G, 768) bf16 (``rows_pool``); ``idx`` (B,) int32 selects
+    entries, None means all G in order.  The kernel accumulates in fp32 on v_mfma_f32_16x16x32_bf16, the 24 K steps
+    ascending, probes in tiles of 16: a score's bits depend on its (probe, entry) pair alone, not on the other
+    probes, the other entries or the pair's place in ``idx``.  Checked on the host before anything is launched:
+    dtypes, contiguity, devices, 16-byte alignment, and every idx in [0, G) when ``idx_host`` (a host copy) is given
+    or the tensors are on the host; the kernel itself reads nothing for an idx outside [0, G) and writes NaN.
+
+    CPU tensors take the statement: the sum over ascending c in ``dtype`` arithmetic (torch.float32, the default,
+    or torch.float64), to which the kernel agrees within rounding (the MFMA's order inside a K step is its own)."""
+    op = "desc_score"
+    for name, t in (("dq", dq), ("dg", dg)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[1] != DESC_DIM \
+                or not t.is_contiguous():
+            raise _lib.FpmError("%s: %s must be contiguous bfloat16 descriptors of 768 channels" % (op, name))
+    if idx is not None:
+        _check_index_tensors(op, (("idx", idx, torch.int32),))
+    _check_on_device_of(op, dq, (("dg", dg), ("idx", idx), ("out", out)))
+    Q, G = int(dq.shape[0]), int(dg.shape[0])
+    B = G if idx is None else int(idx.numel())
+    if Q > 16 * 65535:
+        raise _lib.FpmError("%s: at most %d probes per call" % (op, 16 * 65535))
+    if idx is not None and (idx_host is not None or not dq.is_cuda):
+        ih = _host_copy(idx_host, idx)
+        if ih.numel() != B:
+            raise _lib.FpmError("%s: the host copy of idx does not match the device tensor" % op)
+        if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
+            raise _lib.FpmError("%s: idx value outside [0, %d)" % (op, G))
+    if not dq.is_cuda:
+        dtype = _host_dtype(op, dtype)
+        res = _desc_score_host(dq, dg if idx is None else dg[idx.long()], dtype)
+        if out is None:
+            return res
+        _shape(out, (Q, B), "%s out" % op)
+        return out.copy_(res)
+    if dtype is not None:
+        raise _lib.FpmError("%s: dtype selects the host statement's arithmetic; the kernel is fp32" % op)
+    if out is None:
+        out = torch.empty(Q, B, device=dq.device, dtype=torch.float32)
+    _shape(out, (Q, B), "%s out" % op)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.FpmError("%s: out must be contiguous fp32" % op)
+    if Q == 0 or B == 0:
+        return out
+    if (dq.data_ptr() | dg.data_ptr()) & 15:
+        raise _lib.FpmError("%s: dq and dg must be 16-byte aligned" % op)
+    _lib.call("fpm_desc_score", _p(dq), Q, _p(dg), G, _p(idx), B, _p(out), _stream(dq))
+    return out
 
 
 TOPK_MERGE_SMAX = 16

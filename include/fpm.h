@@ -576,6 +576,41 @@ int fpm_rank_topk(const float* scores, long ld, int P, int G, int k, int* top_id
 long fpm_rank_select_ws_bytes(int P);
 int fpm_rank_select(const float* scores, long ld, int P, int G, int k, int* top_idx, float* top_score, void* ws,
                     long ws_bytes, void* stream);
+/* The k best of every row for any 1 <= k <= G, as a set in entry order (the prescreen of a 1:N identification):
+ * keep[p][0..k) (int32, contiguous, P x k) holds the columns whose key is at or above the row's k-th largest key,
+ * in ascending column order.  The key and the search for the k-th key T are fpm_rank_select's own (score bits
+ * descending, ties to the lower column, NaN after every number; keys are unique, so exactly k columns pass).
+ * Then an ordered compaction over contiguous slices of the row: one launch writes every slice's count of keys
+ * >= T, the next takes the prefix of those counts and writes the slice's columns behind it, a wave ballot giving
+ * the place inside a chunk of 256 columns.  No slot is handed out by an atomic, no workgroup waits for another
+ * inside a launch: the output is one answer whatever the schedule.  ws: fpm_rank_keep_ws_bytes(P, G) bytes of
+ * device scratch, owned by the call until the stream has run it (the entry point clears it on the stream).
+ * P <= 65535. */
+long fpm_rank_keep_ws_bytes(int P, int G);
+int fpm_rank_keep(const float* scores, long ld, int P, int G, int k, int* keep, void* ws, long ws_bytes,
+                  void* stream);
+/* ---- prescreen descriptors (1:N identification) ---------------------------------------------------
+ * The descriptor of a template: its index rows sum-pooled, L2-normalised, in bf16.  y: rows x 768 fp32 (device,
+ * 16-byte aligned); row_off: the index's offsets (device, int64), entry g the rows [row_off[g], row_off[g + 1]);
+ * entries lo <= g < hi are pooled into desc ((hi - lo) x 768 bf16, 8-byte aligned).  Per entry of n rows:
+ *   m[c] = the fp32 sum of y[i][c] over i ascending, one running sum per channel from +0.0;
+ *   ss   = the fp64 sum of double(m[c])^2 in this order: thread t < 192 owns channels 4t .. 4t + 3 and holds
+ *          p[t] = ((m0^2 + m1^2) + m2^2) + m3^2; p[192 .. 256) = +0.0; for o = 128, 64, .. 1: p[t] += p[t + o]
+ *          for every t < o; ss = p[0] (a square of an fp32 value is exact in fp64; every sum is one rounded add);
+ *   r    = sqrt(ss) in fp64;  desc[c] = bf16_rne(float(double(m[c]) / r)), each step correctly rounded.
+ * ss == 0, or ss not finite, gives an all-zero descriptor; so does an entry whose offsets fall or leave
+ * [0, rows] (the kernel reads nothing for it).  One workgroup of 192 threads per entry, a float4 of channels per
+ * thread (row reads fully coalesced), 2 KB of LDS for the norm, no atomics, no scratch: an entry's descriptor
+ * depends on its own rows alone. */
+int fpm_rows_pool(const float* y, long rows, const long* row_off, int lo, int hi, void* desc, void* stream);
+/* Descriptor scores, probes x entries: score[q][b] = sum_c dq[q][c] * dg[e_b][c], e_b = idx[b] (int32, device)
+ * or b when idx is NULL (then B must equal G).  dq: Q x 768 bf16, dg: G x 768 bf16, both 16-byte aligned; score:
+ * Q x B fp32, contiguous.  v_mfma_f32_16x16x32_bf16, one fp32 accumulator per pair over the 24 K steps in
+ * ascending order; probes in tiles of 16 (rows past Q are zeros), the tile's operand in registers for the whole
+ * launch; a wave takes 16 entries at a time, each entry's 1536 bytes read once per probe tile, straight from
+ * global memory into the B operand.  A score's bits depend on its (probe, entry) pair alone.  An e_b outside
+ * [0, G) reads nothing and gives NaN (0x7FC00000).  No LDS, no atomics, no scratch. */
+int fpm_desc_score(const void* dq, int Q, const void* dg, int G, const int* idx, int B, float* score, void* stream);
 /* Per-group fusion of a score matrix (subject-level identification: a group is the impressions of one
  * subject).  Row p's groups are CSR tables: group s holds the positions grp_pos[grp_off[s] .. grp_off[s + 1])
  * (int32, positions into row p of scores, each in [0, G); they need not cover the row), read at

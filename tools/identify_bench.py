@@ -17,6 +17,16 @@
                                                                        (-> profiles/identify_many.json)
     python tools/identify_bench.py --subjects 4 --shortlist 64 --probes 16 --gallery 16384 --large 0 --dtypes bf16
                                                                        (-> profiles/identify_subjects.json)
+    python tools/identify_bench.py --shortlist 64 --prescreen 1024 --layout fp8+host --dtypes bf16
+    python tools/identify_bench.py --shortlist 64 --prescreen 1024 --layout fp8+host --dtypes bf16 --coarse stream
+                                   --n 512 --large 4096 --append       (-> profiles/identify_prescreen.json)
+
+``--prescreen K`` (with ``--shortlist M``; one ``--layout``, the ``--large`` gallery alone): the index enrolled with
+descriptors; ``identify(shortlist=M, prescreen=K)`` against ``identify(shortlist=M)`` (the path without the
+prescreen: its kernels are untouched) in one process, with the A/B verdict; the prescreen's three kernels each alone
+and together as the query runs them, the coarse pass over the K kept entries against the pass over the whole
+gallery, and ``add_descriptors`` once.  Also the descriptor scores of mate and runner-up on the tests' planted-mate
+gallery.  Recall on trained weights is not measured: the weights are ``params.init_params``.
 
 ``--subjects R`` (with ``--shortlist M``): the gallery labelled with R consecutive entries per subject.
 ``ops.group_scores`` (max and mean) and ``ops.rank_select`` timed on the same ``--probes`` x gallery coarse
@@ -549,6 +559,179 @@ def child_subjects(args):
     print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
 
 
+def _ab(o, c):
+    """The project's A/B rule: the candidate's median against the baseline's best run less its spread."""
+    faster = o["min_ms"] - (o["max_ms"] - o["min_ms"]) - c["median_ms"]
+    slower = c["min_ms"] - (c["max_ms"] - c["min_ms"]) - o["median_ms"]
+    return dict(speedup_median=round(o["median_ms"] / c["median_ms"], 3), faster_margin_ms=round(faster, 3),
+                slower_margin_ms=round(slower, 3),
+                verdict="faster" if faster > 0 else "slower" if slower > 0 else "within spread")
+
+
+def child_prescreen(args):
+    """``--shortlist M --prescreen K``: the prescreened query against the shortlisted query without it, in this one
+    process; the prescreen's kernels alone; the coarse pass over K entries against the pass over the gallery."""
+    import torch
+    import bench
+    import fpm
+    from fpm import gallery as fgallery, ops, params, synth
+    dev = torch.device("cuda", 0)
+    G, n, dtype, M, K, coarse = args.gallery, args.n, args.child, args.shortlist, args.prescreen, args.coarse
+    layout = args.layout
+    probe = synth.make_graph(args.seed, 0, 0, n)
+    base = bench.make_gallery(args.seed, 1, min(G, args.distinct), n, args.gen_workers)
+    gal = [base[i % len(base)] for i in range(G)]          # past --distinct graphs the gallery repeats them
+    net = fpm.Net(regression=True, backbone=False, dtype=dtype)
+    net.load_state_dict(params.init_params(args.seed))
+    index = net.enroll(gal, dev, layout=layout, descriptors=True)
+    torch.cuda.synchronize()
+    del gal, base
+    res = dict(dtype=dtype, gallery=G, distinct_graphs=min(G, args.distinct), n=n, shortlist=M, prescreen=K,
+               layout=layout, coarse=coarse, sc_mode=index.sc_mode, reps=args.reps, nbytes=index.nbytes(),
+               desc_bytes=int(index.desc.numel()) * 2)
+
+    def series(fn):
+        fn()
+        torch.cuda.synchronize()
+        return _ev(_timed(fn, args.reps))
+
+    def fresh(fn):
+        index._sel = index._stage = None                   # a new probe's lists: nothing staged is kept
+        return fn()
+    pre = net.identify(probe, index, topk=10, shortlist=M, prescreen=K, coarse=coarse)
+    plain = net.identify(probe, index, topk=10, shortlist=M, coarse=coarse)
+    torch.cuda.synchronize()
+    pre_idx = pre["pre_idx"].cpu().long()
+    res["prescreen_kept"] = int(pre_idx.numel())
+    res["plain_shortlist_in_prescreen"] = len(set(plain["short_idx"].tolist()) & set(pre_idx.tolist()))
+    res["same_top1"] = int(plain["top_idx"][0]) == int(pre["top_idx"][0])
+    wp = net.packed(dev)
+    yp = net._probe_rows(wp, fgallery._ProbeSide(probe, index))
+    one = torch.tensor([0, int(yp.shape[0])], dtype=torch.int64)
+    one_d = one.to(dev)
+    dq = ops.rows_pool(yp, one_d, row_off_host=one)
+    sel = index.live
+    sel32 = sel.to(torch.int32)
+    sel_d = sel32.to(dev)
+    sc = ops.desc_score(dq, index.desc, sel_d, idx_host=sel32)
+    res["pool"] = series(lambda: ops.rows_pool(yp, one_d, out=dq, row_off_host=one))
+    res["score"] = series(lambda: ops.desc_score(dq, index.desc, sel_d, out=sc, idx_host=sel32))
+    res["score"]["desc_gb_per_s"] = round(res["desc_bytes"] / res["score"]["median_ms"] / 1e6, 1)
+    res["keep"] = series(lambda: ops.rank_keep(sc, min(K, G)))
+    res["prescreen_pass"] = series(lambda: (ops.rows_pool(yp, one_d, out=dq, row_off_host=one),
+                                            fgallery._prescreen(dq, index, sel, K)))
+    res["add_descriptors"] = series(lambda: index.add_descriptors())
+    res["coarse_over_G"] = series(lambda: net.coarse_scores(probe, index, coarse=coarse))
+    res["coarse_over_K"] = series(lambda: net.coarse_scores(probe, index, select=pre_idx, coarse=coarse))
+    res["coarse_K_over_G"] = round(res["coarse_over_K"]["median_ms"] / res["coarse_over_G"]["median_ms"], 4)
+    res["K_over_G"] = round(int(pre_idx.numel()) / G, 4)
+    res["query"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, shortlist=M, coarse=coarse)))
+    res["query_prescreen"] = series(lambda: fresh(lambda: net.identify(probe, index, topk=10, shortlist=M, prescreen=K,
+                                                                       coarse=coarse)))
+    res["ab_coarse"] = _ab(res["coarse_over_G"], res["coarse_over_K"])
+    res["ab_query"] = _ab(res["query"], res["query_prescreen"])
+    res["planted"] = _planted_prescreen(dtype, layout)
+    del index
+    res["kernels_at_scale"] = _prescreen_kernels(series)
+    print("IDENTIFY_BENCH " + json.dumps(res), flush=True)
+
+
+def _prescreen_kernels(series):
+    """The prescreen's kernels where the launch is not the cost: ``desc_score`` over 2^20 random unit descriptors
+    (1.6 GB) for 1, 16 and 17 probes, ``rank_keep`` and ``rank_select`` over one row of 2^20 scores, ``rows_pool``
+    over 8192 entries of 128 rows (3.2 GB)."""
+    import torch
+    from fpm import ops
+    dev = torch.device("cuda", 0)
+    out, G = {}, 1 << 20
+    dg = torch.nn.functional.normalize(torch.randn(G, 768, device=dev), dim=1).to(torch.bfloat16)
+    for Q in (1, 16, 17):
+        dq, sc = dg[:Q].clone(), torch.empty(Q, G, device=dev)
+        r = series(lambda: ops.desc_score(dq, dg, out=sc))
+        r.update(probes=Q, entries=G, desc_tb_per_s=round(G * 1536 * ((Q + 15) // 16) / r["median_ms"] / 1e9, 3))
+        out["score_Q%d" % Q] = r
+    row = sc[:1].contiguous()
+    for k in (1024, 65536):
+        out["keep_k%d" % k] = dict(series(lambda: ops.rank_keep(row, k)), entries=G)
+    out["select_k1024"] = dict(series(lambda: ops.rank_select(row, 1024)), entries=G)
+    del dg, sc, row
+    E, n = 8192, 128
+    y = torch.randn(E * n, 768, device=dev)
+    off = torch.arange(E + 1, dtype=torch.int64) * n
+    off_d, d = off.to(dev), torch.empty(E, 768, device=dev, dtype=torch.bfloat16)
+    r = series(lambda: ops.rows_pool(y, off_d, out=d, row_off_host=off))
+    r.update(entries=E, rows_per_entry=n, rows_tb_per_s=round(int(y.numel()) * 4 / r["median_ms"] / 1e9, 3))
+    out["pool"] = r
+    return out
+
+
+def _planted_prescreen(dtype, layout):
+    """The tests' planted-mate gallery (40 entries, three probes, the "spread" weights): per probe the descriptor
+    score of the mate and of the best other entry, and whether prescreen=8 keeps the mate."""
+    import torch
+    import fpm
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_shortlist_cpu import state_dicts
+    from test_shortlist_gpu import MATES, planted
+    dev = torch.device("cuda", 0)
+    gal, probes = planted()
+    net = fpm.Net(regression=True, backbone=False, dtype=dtype)
+    net.load_state_dict(state_dicts()["spread"])
+    index = net.enroll(gal, dev, batch=16, layout=layout, descriptors=True)
+    out = []
+    for p, r in enumerate(net.identify(probes, index, shortlist=4, prescreen=len(gal))):
+        mate = [e for e, q in MATES.items() if q == p][0]
+        sc = r["pre_score"].cpu()
+        rest = torch.cat([sc[:mate], sc[mate + 1:]])
+        kept = net.identify(probes[p], index, shortlist=4, prescreen=8)
+        out.append(dict(mate_score=float(sc[mate]), best_other=float(rest.max()),
+                        mate_kept_at_8=mate in kept["pre_idx"].tolist(), mate_first=int(kept["short_idx"][0]) == mate))
+    return dict(gallery=len(gal), weights="spread", layout=layout, probes=out)
+
+
+def main_prescreen(ap, args):
+    """``--shortlist M --prescreen K``: one child per dtype over the ``--large`` gallery (``--gallery`` when 0)."""
+    if "," in args.layout:
+        ap.error("--prescreen takes one --layout")
+    G, lines = args.large or args.gallery, []
+    for dtype in args.dtypes.split(","):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", dtype, "--gallery", str(G), "--n", str(args.n),
+               "--reps", str(args.reps), "--seed", str(args.seed), "--gen-workers", str(args.gen_workers),
+               "--shortlist", str(args.shortlist), "--prescreen", str(args.prescreen), "--distinct", str(args.distinct),
+               "--coarse", args.coarse, "--layout", args.layout]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
+        except subprocess.TimeoutExpired:
+            sys.exit("identify_bench: the %s x %d step ran over its %d s limit; stopping" % (dtype, G, args.step_timeout))
+        got = [l for l in r.stdout.splitlines() if l.startswith("IDENTIFY_BENCH ")]
+        if r.returncode != 0 or not got:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            sys.exit("identify_bench: the %s x %d step failed (exit %d); stopping" % (dtype, G, r.returncode))
+        lines.append(json.loads(got[-1][len("IDENTIFY_BENCH "):]))
+        print(json.dumps(lines[-1]), flush=True)
+    out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", "identify_prescreen.json")
+    doc = dict(tool="tools/identify_bench.py --shortlist %d --prescreen %d --layout %s --coarse %s --n %d"
+                    % (args.shortlist, args.prescreen, args.layout, args.coarse, args.n),
+               config="1 probe x gallery, n keypoints per graph, an index with descriptors; query = identify(shortlist=M) "
+                      "(no prescreen: the parent side), query_prescreen = identify(shortlist=M, prescreen=K); pool, score "
+                      "and keep: the prescreen's kernels alone, prescreen_pass: the three as the query runs them; "
+                      "coarse_over_G / coarse_over_K: the coarse pass over the gallery and over the K kept entries; "
+                      "weights are init_params: recall on trained weights is not measured",
+               method="1 warm-up, `reps` queries each, HIP events around each query, median and min-max; both sides "
+                      "in one process; a fresh process per shape",
+               results=lines)
+    if args.append and os.path.exists(out):
+        with open(out) as f:
+            old = json.load(f)
+        doc["tool"] = old["tool"] + "; " + doc["tool"]
+        doc["results"] = old["results"] + lines
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print("wrote %s" % out)
+
+
 def main_shortlist(ap, args):
     lines = []
     shapes = [(args.gallery, dt) for dt in args.dtypes.split(",")]
@@ -630,6 +813,9 @@ def main():
                     help="--shortlist: R > 0 labels the gallery with R consecutive entries per subject and times "
                          "group_scores against rank_select on the --probes (default 16) x gallery coarse matrix, and the "
                          "subject-level shortlisted query against the entry-level one (profiles/identify_subjects.json)")
+    ap.add_argument("--prescreen", type=int, default=0,
+                    help="--shortlist: K > 0 times identify(shortlist=M, prescreen=K) against identify(shortlist=M) over "
+                         "the --large gallery on one --layout (profiles/identify_prescreen.json)")
     ap.add_argument("--group-pairs", type=int, default=1024, help="--probes: identify_many's group_pairs")
     ap.add_argument("--append", action="store_true",
                     help="--shortlist: add the results to those the output file already holds (another --n)")
@@ -648,9 +834,13 @@ def main():
     args = ap.parse_args()
     if args.reps < 5:
         ap.error("--reps must be at least 5")
-    if (args.probes or args.subjects) and not args.shortlist > 0:
-        ap.error("--probes and --subjects go with --shortlist M")
+    if (args.probes or args.subjects or args.prescreen) and not args.shortlist > 0:
+        ap.error("--probes, --subjects and --prescreen go with --shortlist M")
+    if args.prescreen and (args.prescreen < args.shortlist or args.probes or args.subjects):
+        ap.error("--prescreen K needs K >= --shortlist, without --probes and --subjects")
     if args.child:
+        if args.prescreen:
+            return child_prescreen(args)
         if args.subjects:
             return child_subjects(args)
         if args.probes:
@@ -658,6 +848,8 @@ def main():
         if args.shortlist > 0 and args.layout != "f32":
             return child_layouts(args)
         return child_shortlist(args) if args.shortlist > 0 else child(args)
+    if args.prescreen:
+        return main_prescreen(ap, args)
     if args.shortlist > 0:
         return main_shortlist(ap, args)
     lines = []
