@@ -86,6 +86,7 @@ rows that it writes.
 """
 import contextlib
 import hashlib
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -96,12 +97,13 @@ from ._lib import FpmError
 from .batch import DeviceBatch, ORDER_MIN_NMAX, ORDER_ON, hilbert_order
 from .model import _CachedSide
 
+SCORES = ("cls_prob", "cls_logits", "k_prob")
 FORMAT = 1                    # a saved "f32" index; the other layouts write FORMAT_LAYOUTS
 FORMAT_LAYOUTS = 2
 FORMAT_TOMBSTONES = 3         # any layout, with the table ``removed`` (an index saved with removed slots)
 FORMAT_FP8 = 4                # the "fp8+host" layout: ``y8`` and ``s8`` for ``y16``; ``removed`` with tombstones
 FORMAT_DESC = 5               # any layout (its own row fields), with ``desc``; ``removed`` with tombstones
-SCORES = ("cls_prob", "cls_logits", "k_prob")
+FORMATS = (FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8, FORMAT_DESC)
 LAYOUTS = ("f32", "f32+bf16", "bf16+host", "fp8+host")
 HOST_LAYOUTS = ("bf16+host", "fp8+host")      # the fp32 rows in (pinned) host memory: ``fetch``
 BF16_LAYOUTS = ("f32+bf16", "bf16+host")      # a bf16 copy of the rows on the device: ``y16``
@@ -111,6 +113,53 @@ ROW_BYTES = 4 * C.NODE_FEATURE_DIM
 # the fp32 rows one ``GalleryIndex.fetch`` stages on the device at most: those of the largest shortlist
 # the API allows (1.89 GB)
 FETCH_MAX_BYTES = ops.RANK_SELECT_KMAX * ops.COARSE_STREAM_NMAX * ROW_BYTES
+# the rows of the device buffer ``GalleryIndex.compact`` stages blocks in whose destination meets their source
+COMPACT_STAGE_BYTES = 64 << 20
+DESC_STAGE_BYTES = 64 << 20   # the device buffer ``GalleryIndex.add_descriptors`` uploads host rows through
+COMPACT_HOST_ROWS = 4096      # rows per piece (12 MB) of a host-side move whose destination meets its source
+
+
+# The stored fields, one row per array, in the order ``save`` writes them (``row_off_host`` as ``row_off``; not the last).
+# axis: what the first dimension counts, "rows" (keypoints), "edges", "entries" or "entries+1" (offsets); place: "device",
+# "host", or "rows32" (the device, or pinned host memory in HOST_LAYOUTS); when: None (every index), the layouts that hold
+# it, or "optional" (may be None).  Everything that enumerates the arrays loops over this table: a new field is a new row.
+Field = namedtuple("Field", "name axis tail dtype place when")
+_D = C.NODE_FEATURE_DIM
+FIELDS = (
+    Field("y", "rows", (_D,), torch.float32, "rows32", None),
+    Field("row_off_host", "entries+1", (), torch.int64, "host", None),
+    Field("n", "entries", (), torch.int32, "host", None),
+    Field("src", "edges", (), torch.int32, "device", None),
+    Field("dst", "edges", (), torch.int32, "device", None),
+    Field("pseudo", "edges", (2,), torch.float32, "device", None),
+    Field("edge_off", "entries+1", (), torch.int64, "host", None),
+    Field("w", "entries", (C.GLOBAL_FEATURE_DIM,), torch.float32, "device", None),
+    Field("P", "rows", (2,), torch.float32, "device", "optional"),
+    Field("y16", "rows", (_D,), torch.bfloat16, "device", BF16_LAYOUTS),
+    Field("subject", "entries", (), torch.int64, "host", "optional"),
+    Field("y8", "rows", (_D,), torch.float8_e4m3fn, "device", (FP8_LAYOUT,)),
+    Field("s8", "rows", (), torch.float32, "device", (FP8_LAYOUT,)),
+    Field("desc", "entries", (_D,), torch.bfloat16, "device", "optional"),
+    Field("row_off", "entries+1", (), torch.int64, "device", None),
+)
+FIELD = {f.name: f for f in FIELDS}
+# the row stores of the layouts: what the enrolment loops write and ``ops.rows_move`` compacts
+ROW_STORES = tuple(f for f in FIELDS if f.axis == "rows" and f.when != "optional")
+# what the constructor says of a field that is not as its row of the table has it
+_MUST = {"y16": "y16 must be bfloat16 of y's shape on the index device",
+         "y8": "y8 must be float8_e4m3fn of y's shape and s8 float32, one scale per row, both on the index device",
+         "desc": "desc must be bfloat16, one row of %d channels per entry, on the index device" % _D}
+_MUST["s8"] = _MUST["y8"]
+
+
+def _fields(layout, optional=()):
+    """The rows of FIELDS an index of ``layout`` holds; of the optional ones those named in ``optional``."""
+    return [f for f in FIELDS if f.when is None or (f.name in optional if f.when == "optional" else layout in f.when)]
+
+
+def _count(axis, G, R, E):
+    """The length of ``axis`` in an index (or a prefix) of G entries, R rows and E edges."""
+    return {"rows": R, "edges": E, "entries": G, "entries+1": G + 1}[axis]
 
 
 def _host_rows(shape, dev):
@@ -119,10 +168,55 @@ def _host_rows(shape, dev):
     return torch.empty(shape, dtype=torch.float32, pin_memory=torch.device(dev).type == "cuda")
 
 
-# the rows of the device buffer ``GalleryIndex.compact`` stages blocks in whose destination meets their source
-COMPACT_STAGE_BYTES = 64 << 20
-DESC_STAGE_BYTES = 64 << 20   # the device buffer ``GalleryIndex.add_descriptors`` uploads host rows through
-COMPACT_HOST_ROWS = 4096      # rows per piece (12 MB) of a host-side move whose destination meets its source
+def _new_field(f, sizes, layout, dev):
+    """Field ``f`` for ``sizes`` = (entries, rows, edges), allocated where it lives in an index of ``layout`` on
+    ``dev``: the host tables and the offsets zero, everything else uninitialised."""
+    shape = (_count(f.axis, *sizes),) + f.tail
+    if f.place == "rows32" and layout in HOST_LAYOUTS:
+        return _host_rows(shape, dev)
+    make = torch.zeros if f.place == "host" or f.axis == "entries+1" else torch.empty
+    return make(shape, dtype=f.dtype, device="cpu" if f.place == "host" else dev)
+
+
+def _placed(f, t, layout, dev, at=None):
+    """``t`` (``at``: its rows ``at``, an index where ``t`` is) where field ``f`` of an index of ``layout`` on ``dev``
+    lives: a host table as it is, the fp32 rows of a host layout in host rows of their own, the rest on the device."""
+    if f.place == "rows32" and layout in HOST_LAYOUTS:
+        out = _host_rows((t.shape[0] if at is None else at.numel(),) + tuple(t.shape[1:]), dev)
+        return out.copy_(t) if at is None else torch.index_select(t, 0, at, out=out)
+    t = t if at is None else t[at]
+    return t if f.place == "host" else t.to(dev)
+
+
+def _make_store(cap, layout, dev, optional=()):
+    """The buffers of an index with capacity ``cap`` = (entries, rows, edges): ``cap`` and every field by name, None
+    for one the index does not hold (``_fields``).  The public fields of the index are prefix views of these."""
+    have = _fields(layout, optional)
+    return dict(cap=tuple(cap), **{f.name: _new_field(f, cap, layout, dev) if f in have else None for f in FIELDS})
+
+
+def _fill(st, src, G, R, E):
+    """``src(name)`` over the prefix of every field the storage ``st`` holds, but the device offsets (``_commit``'s)."""
+    for f in FIELDS:
+        if st[f.name] is not None and f.name != "row_off":
+            st[f.name][:_count(f.axis, G, R, E)].copy_(src(f.name))
+
+
+def _row_buffers(layout, get):
+    """The row stores ``get(field)`` gives, by name; the fp32 rows as "y" on the device, "y_host" on the host."""
+    b = {f.name: get(f) for f in ROW_STORES}
+    b["y"], b["y_host"] = (None, b["y"]) if layout in HOST_LAYOUTS else (b["y"], None)
+    return b
+
+
+def _alloc_rows(layout, dev, rows):
+    """The row buffers (``_row_buffers``) of a new index of exactly ``rows`` rows."""
+    return _row_buffers(layout, lambda f: _new_field(f, (0, rows, 0), layout, dev) if f in _fields(layout) else None)
+
+
+def _store_rows(index):
+    """The same of an index with capacity: its storage, which the loops write past ``used``."""
+    return _row_buffers(index.layout, lambda f: index._store[f.name])
 
 
 def _check_capacity(what, capacity, G, R, E=0):
@@ -143,26 +237,11 @@ def _check_capacity(what, capacity, G, R, E=0):
     return tuple(cap)
 
 
-def _make_store(cap, layout, dev, has_P, has_subject, has_desc=False):
-    """The buffers of an index with capacity ``cap`` = (entries, rows, edges): the device arrays (in
-    "bf16+host" and "fp8+host" the fp32 rows pinned on the host), and the host tables.  Rows and edges are uninitialised,
-    the small tables zero.  The public fields of the index are prefix views of these."""
-    ents, rows, edges = cap
-    D = C.NODE_FEATURE_DIM
-    new = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)
-    return dict(cap=tuple(cap),
-                y=_host_rows((rows, D), dev) if layout in HOST_LAYOUTS else new((rows, D), torch.float32),
-                y16=new((rows, D), torch.bfloat16) if layout in BF16_LAYOUTS else None,
-                y8=new((rows, D), torch.float8_e4m3fn) if layout == FP8_LAYOUT else None,
-                s8=new((rows,), torch.float32) if layout == FP8_LAYOUT else None,
-                P=new((rows, 2), torch.float32) if has_P else None,
-                src=new((edges,), torch.int32), dst=new((edges,), torch.int32), pseudo=new((edges, 2), torch.float32),
-                w=new((ents, C.GLOBAL_FEATURE_DIM), torch.float32),
-                desc=new((ents, C.NODE_FEATURE_DIM), torch.bfloat16) if has_desc else None,
-                row_off=torch.zeros(ents + 1, device=dev, dtype=torch.int64),
-                n=torch.zeros(ents, dtype=torch.int32), edge_off=torch.zeros(ents + 1, dtype=torch.int64),
-                row_off_host=torch.zeros(ents + 1, dtype=torch.int64),
-                subject=torch.zeros(ents, dtype=torch.int64) if has_subject else None)
+def _edge_room(what, seen, room):
+    """Refuse an enrolment into an index whose edges (``seen`` so far) pass the ``room`` left (None: no bound)."""
+    if room is not None and seen > room:
+        raise FpmError("%s: the graphs' edges pass the index's capacity (%d so far, room for %d); reserve a bigger "
+                       "index (GalleryIndex.reserve(..., edges=...))" % (what, seen, room))
 
 
 def _entry_ranges(off, ent):
@@ -172,6 +251,31 @@ def _entry_ranges(off, ent):
     new = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
     at = torch.arange(int(new[-1]), dtype=torch.int64)
     return at + torch.repeat_interleave(off[ent] - new[:-1], cnt), new
+
+
+def _check_subjects(what, labels, G):
+    """Subject labels as given -> host int64 (G,), a copy: one integer >= 0 per entry."""
+    t = torch.as_tensor(labels)
+    if t.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+        raise FpmError("%s: subject labels must be integers (got %s)" % (what, t.dtype))
+    if t.dim() != 1 or int(t.numel()) != int(G):
+        raise FpmError("%s: %s subject labels for %d entries (one label per entry)" % (what, tuple(t.shape), G))
+    t = t.detach().cpu().to(torch.int64).clone()
+    if int(G) and int(t.min()) < 0:
+        raise FpmError("%s: a negative subject label (%d)" % (what, int(t.min())))
+    return t
+
+
+def _select_host(index, select, what):
+    """The entries a query runs over (host int64): ``select`` as given, or all entries: the live ones of an
+    index with removed slots (the one place that defines "all entries"); a removed entry is refused."""
+    if select is None:
+        return index.live
+    sel = torch.as_tensor(select, dtype=torch.int64).view(-1).cpu()
+    if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= index.G:
+        raise FpmError("%s: select must name entries in [0, %d)" % (what, index.G))
+    index._check_live(sel, what)
+    return sel
 
 
 class GalleryIndex:
@@ -210,59 +314,58 @@ class GalleryIndex:
 
     def __init__(self, y, row_off, n, src, dst, pseudo, edge_off, w, P, sc_mode, pack_gen, weights_id, y16=None,
                  layout="f32", subject=None, y8=None, s8=None, desc=None):
+        self._init_state(sc_mode, pack_gen, weights_id, layout)
+        given = dict(y=y, y16=y16, y8=y8, s8=s8, P=P, src=src, dst=dst, pseudo=pseudo, w=w, desc=desc, row_off=row_off)
+        for when in dict.fromkeys(f.when for f in FIELDS if isinstance(f.when, tuple)):
+            names = [f.name for f in FIELDS if f.when == when]
+            has = [given[k] is not None for k in names]
+            if not all(has) if layout in when else any(has):
+                raise FpmError("GalleryIndex: layout %r %s" % (layout, "needs " + " and ".join(names) if layout in when
+                                                               else "has no " + " and no ".join(names)))
+        sizes = (int(w.shape[0]), int(y.shape[0]), int(src.numel()))
+        for k, t in given.items():
+            if k in _MUST and t is not None and (
+                    not isinstance(t, torch.Tensor) or t.dtype != FIELD[k].dtype or t.device != row_off.device
+                    or tuple(t.shape) != (_count(FIELD[k].axis, *sizes),) + FIELD[k].tail):
+                raise FpmError("GalleryIndex: inconsistent fields (%s)" % _MUST[k])
+        if layout in HOST_LAYOUTS and (y.is_cuda or (row_off.is_cuda and not y.is_pinned())):
+            raise FpmError("GalleryIndex: layout %r keeps y in host memory (pinned when the index is on a GPU)" % layout)
+        vars(self).update(given)
+        self.row_off_host = row_off.cpu()
+        self.n = torch.as_tensor(n, dtype=torch.int32).cpu()
+        self.edge_off = torch.as_tensor(edge_off, dtype=torch.int64).cpu()
+        self.subject = None         # (G,) int64 host subject labels (set_subjects), or None
+        self._check_tables()
+        if subject is not None:
+            self.set_subjects(subject)
+
+    def _init_state(self, sc_mode, pack_gen, weights_id, layout):
+        """Everything of a new index but its arrays."""
         if sc_mode not in ("f32", "bf16"):
             raise FpmError("GalleryIndex: sc_mode must be 'f32' or 'bf16'")
         if layout not in LAYOUTS:
             raise FpmError("GalleryIndex: layout must be one of %s" % (LAYOUTS,))
-        if (y16 is None) != (layout not in BF16_LAYOUTS):
-            raise FpmError("GalleryIndex: layout %r %s" % (layout, "needs y16" if y16 is None else "has no y16"))
-        if (y8 is None) != (layout != FP8_LAYOUT) or (s8 is None) != (layout != FP8_LAYOUT):
-            raise FpmError("GalleryIndex: layout %r %s" % (layout, "needs y8 and s8" if layout == FP8_LAYOUT else
-                                                           "has no y8 and no s8"))
-        if y8 is not None and (not isinstance(y8, torch.Tensor) or not isinstance(s8, torch.Tensor)
-                               or tuple(y8.shape) != tuple(y.shape) or y8.dtype != torch.float8_e4m3fn
-                               or tuple(s8.shape) != (y.shape[0],) or s8.dtype != torch.float32
-                               or y8.device != row_off.device or s8.device != row_off.device):
-            raise FpmError("GalleryIndex: inconsistent fields (y8 must be float8_e4m3fn of y's shape and s8 float32, one "
-                           "scale per row, both on the index device)")
-        if y16 is not None and (not isinstance(y16, torch.Tensor) or tuple(y16.shape) != tuple(y.shape)
-                                or y16.dtype != torch.bfloat16 or y16.device != row_off.device):
-            raise FpmError("GalleryIndex: inconsistent fields (y16 must be bfloat16 of y's shape on the index device)")
-        if layout in HOST_LAYOUTS and (y.is_cuda or (row_off.is_cuda and not y.is_pinned())):
-            raise FpmError("GalleryIndex: layout %r keeps y in host memory (pinned when the index is on a "
-                           "GPU)" % layout)
-        if desc is not None and (not isinstance(desc, torch.Tensor) or desc.dtype != torch.bfloat16
-                                 or tuple(desc.shape) != (int(w.shape[0]), C.NODE_FEATURE_DIM)
-                                 or desc.device != row_off.device):
-            raise FpmError("GalleryIndex: inconsistent fields (desc must be bfloat16, one row of %d channels per entry, "
-                           "on the index device)" % C.NODE_FEATURE_DIM)
-        self.y, self.src, self.dst, self.pseudo, self.w, self.P = y, src, dst, pseudo, w, P
-        self.desc = desc
-        self.y16, self.y8, self.s8, self.layout = y16, y8, s8, layout
-        self._stage = None          # fetch: (sel, staging buffer, row offsets device / host) of the last selection
-        self.row_off = row_off
-        self.row_off_host = row_off.cpu()
-        self.n = torch.as_tensor(n, dtype=torch.int32).cpu()
-        self.edge_off = torch.as_tensor(edge_off, dtype=torch.int64).cpu()
-        self.sc_mode = sc_mode
+        self.layout, self.sc_mode = layout, sc_mode
         self._pack_gen = int(pack_gen)
         self.weights_id = str(weights_id)
+        self._stage = None          # fetch: (sel, staging buffer, row offsets device / host) of the last selection
         self._sel = None            # the last selection's side-1 batch data (_selection)
-        self.subject = None         # (G,) int64 host subject labels (set_subjects), or None
         self._groups = None         # the last selection's group tables (subject_groups)
         self._store = None          # the buffers at capacity the fields are prefix views of (reserve), or None
         self._removed = None        # host bool table over the slots (remove); None: nothing was ever removed
         self._live = None           # the live slots, while the table above is unchanged
         self.generation = 0         # bumped by every mutation (enroll_into, remove, compact)
         self.last_compact = None    # the last compaction's launches by route (compact)
+
+    def _check_tables(self):
+        """The offsets, counts and sizes of the arrays agree (and no label of a storage's table is negative)."""
         G = self.G
-        if (row_off.dtype != torch.int64 or self.row_off_host.numel() != G + 1 or self.edge_off.numel() != G + 1
-                or int(self.row_off_host[-1]) != y.shape[0] or int(self.edge_off[-1]) != src.numel()
+        if (self.row_off.dtype != torch.int64 or self.row_off_host.numel() != G + 1 or self.edge_off.numel() != G + 1
+                or int(self.row_off_host[-1]) != self.y.shape[0] or int(self.edge_off[-1]) != self.src.numel()
                 or not torch.equal(self.row_off_host[1:] - self.row_off_host[:-1], self.n.long())
-                or tuple(w.shape) != (G, C.GLOBAL_FEATURE_DIM) or y.dtype != torch.float32):
+                or tuple(self.w.shape) != (G, C.GLOBAL_FEATURE_DIM) or self.y.dtype != torch.float32
+                or (self.subject is not None and G and int(self.subject.min()) < 0)):
             raise FpmError("GalleryIndex: inconsistent fields")
-        if subject is not None:
-            self.set_subjects(subject)
 
     @property
     def G(self):
@@ -272,23 +375,23 @@ class GalleryIndex:
     def device(self):
         return self.row_off.device
 
+    def _bytes(self, on_host):
+        """The bytes of the arrays (the storage's, if any) on the device, or of those a host layout keeps on the host."""
+        at = self._store or vars(self)
+        ts = [at[f.name] for f in FIELDS
+              if f.place != "host" and (f.place == "rows32" and self.layout in HOST_LAYOUTS) == on_host]
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
     def nbytes(self):
         """Device bytes held: the rows (3 KB per keypoint in the "f32" layout, 4.5 KB in "f32+bf16",
         1.5 KB in "bf16+host", 772 B in "fp8+host"), plus edges, global features and the descriptors (1536 B per
         entry) when the index holds them."""
-        f = self._store or dict(row_off=self.row_off, src=self.src, dst=self.dst, pseudo=self.pseudo, w=self.w,
-                                P=self.P, y=self.y, y16=self.y16, y8=self.y8, s8=self.s8, desc=self.desc)
-        ts = [f[k] for k in ("row_off", "src", "dst", "pseudo", "w")] + ([] if f["P"] is None else [f["P"]])
-        ts += [] if f.get("desc") is None else [f["desc"]]
-        ts += ([] if self.layout in HOST_LAYOUTS else [f["y"]]) + [f[k] for k in ("y16", "y8", "s8") if f[k] is not None]
-        if self._groups is not None:
-            ts += [self._groups[1][k] for k in ("labels_d", "off_d", "pos_d")]
-        return sum(t.numel() * t.element_size() for t in ts)
+        groups = [] if self._groups is None else [self._groups[1][k] for k in ("labels_d", "off_d", "pos_d")]
+        return self._bytes(False) + sum(t.numel() * t.element_size() for t in groups)
 
     def host_nbytes(self):
         """Host bytes held: the fp32 rows of the "bf16+host" and "fp8+host" layouts (3 KB per keypoint), else 0."""
-        y = self.y if self._store is None else self._store["y"]
-        return y.numel() * y.element_size() if self.layout in HOST_LAYOUTS else 0
+        return self._bytes(True)
 
     def coarse_rows(self):
         """What the coarse kernels read -> (rows, row_scale): the bf16 copy when the index keeps one, the e4m3
@@ -308,11 +411,8 @@ class GalleryIndex:
         G, R, _ = self.used
         dev = self.device
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-            if self._store is not None and self._store.get("desc") is None:
-                self._store["desc"] = torch.empty(self._store["cap"][0], C.NODE_FEATURE_DIM, device=dev,
-                                                  dtype=torch.bfloat16)
-            desc = (torch.empty(G, C.NODE_FEATURE_DIM, device=dev, dtype=torch.bfloat16) if self._store is None
-                    else self._store["desc"][:G])
+            desc = (_new_field(FIELD["desc"], self.used, self.layout, dev) if self._store is None
+                    else self._gain("desc")[:G])
             ro = self.row_off_host
             if self.layout not in HOST_LAYOUTS:
                 ops.rows_pool(self.y, self.row_off, 0, G, out=desc, row_off_host=ro)
@@ -392,32 +492,28 @@ class GalleryIndex:
         ``lo`` on are uploaded from the host table, and the caches are dropped (``_touch``)."""
         st = self._store
         st["row_off"][lo:G + 1].copy_(st["row_off_host"][lo:G + 1])
-        self.y, self.y16 = st["y"][:R], None if st["y16"] is None else st["y16"][:R]
-        self.y8, self.s8 = (None, None) if st["y8"] is None else (st["y8"][:R], st["s8"][:R])
-        self.P = None if st["P"] is None else st["P"][:R]
-        self.src, self.dst, self.pseudo = st["src"][:E], st["dst"][:E], st["pseudo"][:E]
-        self.w, self.row_off = st["w"][:G], st["row_off"][:G + 1]
-        self.desc = None if st.get("desc") is None else st["desc"][:G]
-        self.n, self.edge_off, self.row_off_host = st["n"][:G], st["edge_off"][:G + 1], st["row_off_host"][:G + 1]
-        self.subject = None if st["subject"] is None else st["subject"][:G]
+        for f in FIELDS:
+            t = st[f.name]
+            setattr(self, f.name, None if t is None else t[:_count(f.axis, G, R, E)])
         self._touch()
 
     @staticmethod
     def _over(st, G, R, E, sc_mode, pack_gen, weights_id, layout):
-        """The index over the first G entries, R rows and E edges of the storage ``st`` (``_make_store``)."""
-        st["row_off"][:G + 1].copy_(st["row_off_host"][:G + 1])
-        sub = st["subject"]
-        idx = GalleryIndex(st["y"][:R], st["row_off"][:G + 1], st["n"][:G], st["src"][:E], st["dst"][:E],
-                           st["pseudo"][:E], st["edge_off"][:G + 1], st["w"][:G],
-                           None if st["P"] is None else st["P"][:R], sc_mode, pack_gen, weights_id,
-                           y16=None if st["y16"] is None else st["y16"][:R], layout=layout,
-                           subject=None if sub is None else sub[:G], y8=None if st["y8"] is None else st["y8"][:R],
-                           s8=None if st["s8"] is None else st["s8"][:R],
-                           desc=None if st.get("desc") is None else st["desc"][:G])
+        """The index over the first G entries, R rows and E edges of the storage ``st``, its tables checked."""
+        idx = object.__new__(GalleryIndex)
+        idx._init_state(sc_mode, pack_gen, weights_id, layout)
         idx._store = st
-        idx._commit(G, R, E, lo=G)
+        idx._commit(G, R, E)
+        idx._check_tables()
         idx.generation = 0
         return idx
+
+    def _gain(self, name):
+        """The storage's optional field ``name``, allocated at capacity if the storage does not hold it yet."""
+        st = self._store
+        if st[name] is None:
+            st[name] = _new_field(FIELD[name], st["cap"], self.layout, self.device)
+        return st[name]
 
     def reserve(self, entries, keypoints, edges=None):
         """A new index holding this index's entries (and tombstones) in storage sized for ``entries`` slots,
@@ -431,19 +527,8 @@ class GalleryIndex:
                               (entries, keypoints, edges), G, R, E)
         dev = self.device
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-            st = _make_store(cap, self.layout, dev, self.P is not None, self.subject is not None,
-                             self.desc is not None)
-            for key in ("y", "y16", "y8", "s8", "P"):
-                if st[key] is not None:
-                    st[key][:R].copy_(getattr(self, key))
-            if self.desc is not None:
-                st["desc"][:G].copy_(self.desc)
-            for key in ("src", "dst", "pseudo"):
-                st[key][:E].copy_(getattr(self, key))
-            st["w"][:G].copy_(self.w)
-            st["n"][:G], st["edge_off"][:G + 1], st["row_off_host"][:G + 1] = self.n, self.edge_off, self.row_off_host
-            if self.subject is not None:
-                st["subject"][:G] = self.subject
+            st = _make_store(cap, self.layout, dev, [k for k in FIELD if getattr(self, k) is not None])
+            _fill(st, lambda k: getattr(self, k), G, R, E)
             idx = GalleryIndex._over(st, G, R, E, self.sc_mode, self._pack_gen, self.weights_id, self.layout)
         if self._removed is not None:
             idx._removed = torch.zeros(cap[0], dtype=torch.bool)
@@ -453,10 +538,7 @@ class GalleryIndex:
     def _adopt(self):
         """The storage of an index that has none: its own tensors, full (capacity = used)."""
         if self._store is None:
-            self._store = dict(cap=self.used, y=self.y, y16=self.y16, y8=self.y8, s8=self.s8, P=self.P, src=self.src,
-                               dst=self.dst,
-                               pseudo=self.pseudo, w=self.w, row_off=self.row_off, n=self.n, edge_off=self.edge_off,
-                               row_off_host=self.row_off_host, subject=self.subject, desc=self.desc)
+            self._store = dict(cap=self.used, **{f.name: getattr(self, f.name) for f in FIELDS})
         return self._store
 
     def _need_capacity(self, what):
@@ -496,23 +578,16 @@ class GalleryIndex:
         if int(cnt.numel()) != Gn or int(cnt.sum()) != En:
             raise FpmError("%s: %d edges, their counts per entry sum to %d" % (what, En, int(cnt.sum())))
         _edge_room(what, En, st["cap"][2] - E)
-        if (desc is None) != (st.get("desc") is None):
+        if (desc is None) != (st["desc"] is None):
             raise FpmError("%s: the index %s descriptors, the append %s" % (
                 what, "holds" if desc is None else "holds no", "brings none" if desc is None else "brings them"))
-        st["w"][G:G + Gn].copy_(w)
-        if desc is not None:
-            st["desc"][G:G + Gn].copy_(desc)
-        if P is not None:
-            st["P"][R:R + Rn].copy_(P)
-        for key, t in (("src", src), ("dst", dst), ("pseudo", pseudo)):
-            st[key][E:E + En].copy_(t)
-        if self.layout in HOST_LAYOUTS and self.device.type == "cuda":
-            torch.cuda.current_stream(self.device).synchronize()   # the host rows are complete before they are read
-        st["n"][G:G + Gn] = n
-        st["row_off_host"][G + 1:G + Gn + 1] = R + n.long().cumsum(0)
-        st["edge_off"][G + 1:G + Gn + 1] = E + cnt.cumsum(0)
-        if subjects is not None:
-            st["subject"][G:G + Gn] = subjects
+        new = dict(w=w, desc=desc, P=P, src=src, dst=dst, pseudo=pseudo, n=n, row_off_host=R + n.long().cumsum(0),
+                   edge_off=E + cnt.cumsum(0), subject=subjects)
+        for k, t in new.items():        # each into the tail of its field: from its axis' used count to the new one
+            if k == "n" and self.layout in HOST_LAYOUTS and self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()   # the host rows are complete before they are read
+            if t is not None:
+                st[k][_count(FIELD[k].axis, G, R, E):_count(FIELD[k].axis, G + Gn, R + Rn, E + En)].copy_(t)
         self._commit(G + Gn, R + Rn, E + En, lo=G)
         return torch.arange(G, G + Gn, dtype=torch.int64)
 
@@ -644,25 +719,20 @@ class GalleryIndex:
                 at = (torch.nonzero(head).view(-1) + first).tolist() + [L]
                 for i, j in zip(at[:-1], at[1:]):
                     s, d, k = int(src[i]), int(dst[i]), int(new_ro[j] - new_ro[i])
-                    step = max(s - d, COMPACT_HOST_ROWS)     # a piece no longer than the shift lands on rows already read
+                    step = max(s - d, COMPACT_HOST_ROWS)          # a piece no longer than the shift lands on rows already read
                     for o in range(0, k, step):
                         part = y[s + o:s + min(k, o + step)]
                         y[d + o:d + min(k, o + step)].copy_(part.clone() if step > s - d else part)
-            # the small arrays: gathered out of place (the right sides are whole before anything is written)
+            # the small arrays: gathered out of place by their axis (the right sides are whole before anything is written)
             rows_at, _ = _entry_ranges(ro, live)
             edges_at, new_eo = _entry_ranges(eo, live)
             Rn, En = int(new_ro[-1]), int(new_eo[-1])
-            rows_d, edges_d, live_d = rows_at.to(dev), edges_at.to(dev), live.to(dev)
-            if st["P"] is not None:
-                st["P"][:Rn] = st["P"][rows_d]
-            for key in ("src", "dst", "pseudo"):
-                st[key][:En] = st[key][edges_d]
-            st["w"][:L] = st["w"][live_d]
-            if st.get("desc") is not None:
-                st["desc"][:L] = st["desc"][live_d]          # a fixed-size per-entry table, as w
-            st["n"][:L] = st["n"][live]
-            if st["subject"] is not None:
-                st["subject"][:L] = st["subject"][live]
+            at = dict(rows=rows_at, edges=edges_at, entries=live)
+            at_d = {k: v.to(dev) for k, v in at.items()}
+            for f in FIELDS:
+                if f.axis in at and f not in ROW_STORES and st[f.name] is not None:
+                    pick = (at if f.place == "host" else at_d)[f.axis]
+                    st[f.name][:pick.numel()] = st[f.name][pick]
             st["row_off_host"][:L + 1], st["edge_off"][:L + 1] = new_ro, new_eo
             self._removed[:] = False
             self._commit(L, Rn, En)
@@ -678,21 +748,22 @@ class GalleryIndex:
         slots; without descriptors the formats 1 to 4 are written as before."""
         # a field of an index with storage is a view: a host view is copied, so that only its part is written
         host = (lambda t: t.cpu()) if self._store is None else (lambda t: t.cpu() if t.is_cuda else t.clone())
-        d = dict(format=FORMAT, y=host(self.y), row_off=host(self.row_off_host), n=host(self.n), src=host(self.src),
-                 dst=host(self.dst), pseudo=host(self.pseudo), edge_off=host(self.edge_off), w=host(self.w),
-                 sc_mode=self.sc_mode, pack_gen=self._pack_gen, weights_id=self.weights_id)
-        if self.P is not None:
-            d["P"] = host(self.P)
-        if self.layout in BF16_LAYOUTS:
-            d.update(format=FORMAT_LAYOUTS, layout=self.layout, y16=host(self.y16))
-        if self.subject is not None:
-            d["subject"] = host(self.subject)
-        if self.tombstones:
-            d.update(format=FORMAT_TOMBSTONES, layout=self.layout, removed=self.removed.clone())
-        if self.layout == FP8_LAYOUT:
-            d.update(format=FORMAT_FP8, layout=self.layout, y8=host(self.y8).view(torch.uint8), s8=host(self.s8))
-        if self.desc is not None:
-            d.update(format=FORMAT_DESC, layout=self.layout, desc=host(self.desc))
+        fmt = (FORMAT_DESC if self.desc is not None else FORMAT_FP8 if self.layout == FP8_LAYOUT else
+               FORMAT_TOMBSTONES if self.tombstones else FORMAT_LAYOUTS if self.layout in BF16_LAYOUTS else FORMAT)
+        d = dict(format=fmt)
+        for f in FIELDS:                    # in file order, with the scalars, ``layout`` and ``removed`` at their places
+            t = getattr(self, f.name)
+            if f.name == "y16" and t is not None:
+                d["layout"] = self.layout   # where format 2 put it; the later formats after ``subject``
+            if t is not None and f.name != "row_off":
+                t = host(t)
+                d["row_off" if f.name == "row_off_host" else f.name] = t.view(torch.uint8) if t.element_size() == 1 else t
+            if f.name == "w":
+                d.update(sc_mode=self.sc_mode, pack_gen=self._pack_gen, weights_id=self.weights_id)
+            if f.name == "subject" and fmt != FORMAT:
+                d.setdefault("layout", self.layout)
+            if f.name == "subject" and self.tombstones:
+                d["removed"] = self.removed.clone()
         torch.save(d, path)
 
     @staticmethod
@@ -700,43 +771,30 @@ class GalleryIndex:
         """The index ``save`` wrote, on ``device``.  ``capacity``: (entries, keypoints[, edges]) -- the index
         is restored into storage of that size (as ``reserve`` makes it), without a second copy of it."""
         d = torch.load(path, map_location="cpu", weights_only=True)
-        if d.get("format") not in (FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8, FORMAT_DESC) or (
-                d["format"] == FORMAT_TOMBSTONES and not ("removed" in d and "layout" in d)) or (
-                d["format"] == FORMAT_FP8 and not (d.get("layout") == FP8_LAYOUT and "y8" in d and "s8" in d)) or (
-                d["format"] not in (FORMAT_FP8, FORMAT_DESC) and d.get("layout") == FP8_LAYOUT) or (
-                d["format"] == FORMAT_DESC and not (d.get("layout") in LAYOUTS and "desc" in d and (
-                    d["layout"] != FP8_LAYOUT or ("y8" in d and "s8" in d)) and (
-                    d["layout"] not in BF16_LAYOUTS or "y16" in d))) or (
-                d["format"] != FORMAT_DESC and "desc" in d):
+        fmt, named = d.get("format"), d.get("layout")
+        layout = "f32" if fmt == FORMAT else named
+        # the fp8 layout came with format 4, which is that layout's alone; format 5 is every layout's, and alone has desc
+        if not (fmt in FORMATS and layout in LAYOUTS and ((named == FP8_LAYOUT) == (fmt == FORMAT_FP8) or fmt == FORMAT_DESC)
+                and ("desc" in d) == (fmt == FORMAT_DESC) and ("removed" in d or fmt != FORMAT_TOMBSTONES)
+                and all(f.name in d for f in FIELDS if isinstance(f.when, tuple) and layout in f.when)):
             raise FpmError("GalleryIndex.load: %s is not a gallery index of format %d, %d, %d, %d or %d"
-                           % (path, FORMAT, FORMAT_LAYOUTS, FORMAT_TOMBSTONES, FORMAT_FP8, FORMAT_DESC))
-        layout = d["layout"] if d["format"] != FORMAT else "f32"
+                           % ((path,) + FORMATS))
         if layout == FP8_LAYOUT:
             d["y8"] = d["y8"].view(torch.float8_e4m3fn)
+        scalars = dict(sc_mode=d["sc_mode"], pack_gen=d["pack_gen"], weights_id=d["weights_id"], layout=layout)
         if capacity is None:
-            mv = lambda k: d[k].to(device)
-            if layout in HOST_LAYOUTS:
-                y = _host_rows(d["y"].shape, device).copy_(d["y"])
-            else:
-                y = mv("y")
-            idx = GalleryIndex(y, mv("row_off"), d["n"], mv("src"), mv("dst"), mv("pseudo"), d["edge_off"], mv("w"),
-                               mv("P") if "P" in d else None, d["sc_mode"], d["pack_gen"], d["weights_id"],
-                               y16=mv("y16") if layout in BF16_LAYOUTS else None, layout=layout,
-                               subject=d.get("subject"), y8=mv("y8") if layout == FP8_LAYOUT else None,
-                               s8=mv("s8") if layout == FP8_LAYOUT else None, desc=mv("desc") if "desc" in d else None)
+            fields = {f.name: _placed(f, d[f.name], layout, device)
+                      for f in _fields(layout, set(d)) if f.name != "row_off_host"}
+            fields.setdefault("P", None)                 # the one optional field the constructor has no default for
+            idx = GalleryIndex(**scalars, **fields)
         else:
             G, R, E = int(d["n"].numel()), int(d["y"].shape[0]), int(d["src"].numel())
             cap = _check_capacity("GalleryIndex.load", capacity, G, R, E)
             dev = torch.device(device)
             with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-                st = _make_store(cap, layout, dev, "P" in d, "subject" in d, "desc" in d)
-                for key, k in (("y", R), ("y16", R), ("y8", R), ("s8", R), ("P", R), ("src", E), ("dst", E),
-                               ("pseudo", E), ("w", G), ("desc", G),
-                               ("n", G), ("edge_off", G + 1), ("subject", G)):
-                    if st[key] is not None:
-                        st[key][:k].copy_(d[key])
-                st["row_off_host"][:G + 1] = d["row_off"]
-                idx = GalleryIndex._over(st, G, R, E, d["sc_mode"], d["pack_gen"], d["weights_id"], layout)
+                st = _make_store(cap, layout, dev, set(d))
+                _fill(st, lambda k: d["row_off" if k == "row_off_host" else k], G, R, E)
+                idx = GalleryIndex._over(st, G, R, E, **scalars)
         if "removed" in d:
             idx._removed = torch.zeros(idx.G if capacity is None else idx.capacity[0], dtype=torch.bool)
             idx._removed[:idx.G] = d["removed"]
@@ -748,14 +806,11 @@ class GalleryIndex:
         tensor (``subject``); the cached group tables are dropped.  None removes the labels."""
         lab = None if labels is None else _check_subjects("set_subjects", labels, self.G)
         if self._store is not None:
-            st = self._store
             if lab is None:
-                st["subject"] = None
+                self._store["subject"] = None
             else:
-                if st["subject"] is None:
-                    st["subject"] = torch.zeros(st["cap"][0], dtype=torch.int64)
-                st["subject"][:self.G] = lab
-                lab = st["subject"][:self.G]
+                self._gain("subject")[:self.G] = lab
+                lab = self._store["subject"][:self.G]
         self.subject = lab
         self._groups = None
 
@@ -824,11 +879,11 @@ class GalleryIndex:
 
     def slice(self, entries, device=None):
         """A new GalleryIndex holding the entries ``entries`` (host int64, ascending, no repeats) in that
-        order, on ``device`` (default: this index's): the rows (``y``, ``y16``, ``y8``, ``s8``, ``P``) and edges (``src``,
-        ``dst``, ``pseudo``) of those entries copied by their row and edge ranges, ``n``, ``w``, ``desc`` and ``subject``
-        by entry, the offsets rebuilt; layout, ``sc_mode``, ``_pack_gen`` and ``weights_id`` kept.  A
-        "bf16+host" or "fp8+host" slice gets pinned host rows of its own.  Every field of the slice holds the parent's
-        bytes for those entries (``ShardedGallery.split`` cuts an index into shards with it)."""
+        order, on ``device`` (default: this index's): every field taken by its axis (``FIELDS``) -- the rows and
+        edges of those entries by their row and edge ranges, the per-entry fields by entry -- and the offsets rebuilt;
+        layout, ``sc_mode``, ``_pack_gen`` and ``weights_id`` kept.  A "bf16+host" or "fp8+host" slice gets pinned
+        host rows of its own.  Every field of the slice holds the parent's bytes for those entries
+        (``ShardedGallery.split`` cuts an index into shards with it)."""
         ent = torch.as_tensor(entries)
         if ent.dtype != torch.int64 or ent.is_cuda or ent.dim() != 1 or ent.numel() == 0:
             raise FpmError("GalleryIndex.slice: entries must be a non-empty 1-D host int64 tensor")
@@ -836,24 +891,17 @@ class GalleryIndex:
             raise FpmError("GalleryIndex.slice: entries must ascend without repeats inside [0, %d)" % self.G)
         self._check_live(ent, "GalleryIndex.slice")
         dev = self.device if device is None else torch.device(device)
-        src_dev = self.device
         rows, row_off = _entry_ranges(self.row_off_host, ent)
         edges, edge_off = _entry_ranges(self.edge_off, ent)
-        rows_d, edges_d, ent_d = rows.to(src_dev), edges.to(src_dev), ent.to(src_dev)
-        take = lambda t, at: t[at].to(dev)
-        if self.layout in HOST_LAYOUTS:
-            y = _host_rows((int(rows.numel()), self.y.shape[1]), dev)
-            torch.index_select(self.y, 0, rows, out=y)
-        else:
-            y = take(self.y, rows_d)
-        return GalleryIndex(y, row_off.to(dev), self.n[ent], take(self.src, edges_d), take(self.dst, edges_d),
-                            take(self.pseudo, edges_d), edge_off, take(self.w, ent_d),
-                            None if self.P is None else take(self.P, rows_d), self.sc_mode, self._pack_gen,
-                            self.weights_id, y16=None if self.y16 is None else take(self.y16, rows_d),
-                            layout=self.layout, subject=None if self.subject is None else self.subject[ent],
-                            y8=None if self.y8 is None else take(self.y8, rows_d),
-                            s8=None if self.s8 is None else take(self.s8, rows_d),
-                            desc=None if self.desc is None else take(self.desc, ent_d))
+        at = dict(rows=rows, edges=edges, entries=ent)
+        at_d = {k: v.to(self.device) for k, v in at.items()}
+        fields = dict(row_off=row_off.to(dev), edge_off=edge_off, P=None)
+        for f in FIELDS:
+            t = getattr(self, f.name)
+            if t is not None and f.axis in at:
+                fields[f.name] = _placed(f, t, self.layout, dev, (at_d if t.is_cuda else at)[f.axis])
+        return GalleryIndex(sc_mode=self.sc_mode, pack_gen=self._pack_gen, weights_id=self.weights_id,
+                            layout=self.layout, **fields)
 
     def _selection(self, select, pad_to=None):
         """Side 1 of a probe x gallery batch over the entries ``select`` (None: all), in that order,
@@ -902,19 +950,6 @@ class GalleryIndex:
             P2[rows, loc] = self.P[loc + self.row_off[sel_d][rows]]
             f["ord2"] = hilbert_order(P2, n2, nmax)
         return f
-
-
-def _check_subjects(what, labels, G):
-    """Subject labels as given -> host int64 (G,), a copy: one integer >= 0 per entry."""
-    t = torch.as_tensor(labels)
-    if t.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
-        raise FpmError("%s: subject labels must be integers (got %s)" % (what, t.dtype))
-    if t.dim() != 1 or int(t.numel()) != int(G):
-        raise FpmError("%s: %s subject labels for %d entries (one label per entry)" % (what, tuple(t.shape), G))
-    t = t.detach().cpu().to(torch.int64).clone()
-    if int(G) and int(t.min()) < 0:
-        raise FpmError("%s: a negative subject label (%d)" % (what, int(t.min())))
-    return t
 
 
 class _CachedBatch(DeviceBatch):
@@ -974,32 +1009,6 @@ def spline_weights_id(net):
     return net._sc_weights_id[1]
 
 
-def _alloc_rows(layout, dev, rows):
-    """The row buffers of a new index of exactly ``rows`` rows -> (y fp32 device or None, y16 or None, the
-    pinned host fp32 rows of "bf16+host" / "fp8+host" or None, y8 or None, s8 or None): what the enrolment loops
-    write into."""
-    D = C.NODE_FEATURE_DIM
-    fp8 = layout == FP8_LAYOUT
-    return (None if layout in HOST_LAYOUTS else torch.empty(rows, D, device=dev, dtype=torch.float32),
-            torch.empty(rows, D, device=dev, dtype=torch.bfloat16) if layout in BF16_LAYOUTS else None,
-            _host_rows((rows, D), dev) if layout in HOST_LAYOUTS else None,
-            torch.empty(rows, D, device=dev, dtype=torch.float8_e4m3fn) if fp8 else None,
-            torch.empty(rows, device=dev, dtype=torch.float32) if fp8 else None)
-
-
-def _store_rows(index):
-    """The same five of an index with capacity: its storage, which the loops write past ``used``."""
-    st, host = index._store, index.layout in HOST_LAYOUTS
-    return None if host else st["y"], st["y16"], st["y"] if host else None, st["y8"], st["s8"]
-
-
-def _edge_room(what, seen, room):
-    """Refuse an enrolment into an index whose edges (``seen`` so far) pass the ``room`` left (None: no bound)."""
-    if room is not None and seen > room:
-        raise FpmError("%s: the graphs' edges pass the index's capacity (%d so far, room for %d); reserve a bigger "
-                       "index (GalleryIndex.reserve(..., edges=...))" % (what, seen, room))
-
-
 def _pool_new(desc, g0, rows, off_host, dev):
     """The descriptors of a sub-batch's entries, whose packed fp32 rows ``rows`` (device) have the host offsets
     ``off_host``, into desc[g0 : g0 + entries] (nothing without ``desc``): where the enrolment loops round those
@@ -1029,7 +1038,6 @@ def _enroll_dicts(net, what, graphs, dev, sc_mode, batch, rows, r0, room=None, d
     (``_alloc_rows`` / ``_store_rows``) -> the edges (graph-local src, dst, pseudo on the device, host counts
     per graph).  ``room``: the edges the index has room for (None: a new index).  ``desc``: (len(graphs), 768) bf16
     or None: the table each sub-batch's descriptors are pooled into (``_pool_new``)."""
-    y, y16, y_host, y8, s8 = rows
     wp = net.packed(dev)
     srcs, dsts, pss, cnts, seen = [], [], [], [], 0
     for g0 in range(0, len(graphs), max(1, int(batch))):
@@ -1045,15 +1053,15 @@ def _enroll_dicts(net, what, graphs, dev, sc_mode, batch, rows, r0, room=None, d
         keep = (torch.arange(nmax, device=dev)[None, :] < nv.view(-1, 1)).reshape(-1)
         yr = yb[keep]
         r1 = r0 + int(yr.shape[0])
-        if y16 is not None:
-            ops.cast_bf16(yr, out=y16[r0:r1])
-        if y8 is not None:
-            ops.rows_quant8(yr, y8[r0:r1], s8[r0:r1])
+        if rows["y16"] is not None:
+            ops.cast_bf16(yr, out=rows["y16"][r0:r1])
+        if rows["y8"] is not None:
+            ops.rows_quant8(yr, rows["y8"][r0:r1], rows["s8"][r0:r1])
         _pool_new(desc, g0, yr, torch.cat([torch.zeros(1, dtype=torch.int64), n.long().cumsum(0)]), dev)
-        if y_host is not None:
-            y_host[r0:r1].copy_(yr, non_blocking=True)
+        if rows["y_host"] is not None:
+            rows["y_host"][r0:r1].copy_(yr, non_blocking=True)
         else:
-            y[r0:r1].copy_(yr)
+            rows["y"][r0:r1].copy_(yr)
         r0 = r1
         shift = torch.repeat_interleave(torch.arange(Bs, device=dev) * nmax, torch.from_numpy(cnt).to(dev),
                                         output_size=E).to(torch.int32)
@@ -1079,7 +1087,7 @@ def _empty_index(net, what, capacity, G, R, layout, dev, sc_mode, has_P, has_sub
     ``enroll*(capacity=...)`` is an enrolment into it."""
     cap = _check_capacity(what, capacity, G, R)
     with torch.cuda.device(dev):
-        st = _make_store(cap, layout, dev, has_P, has_subject, has_desc)
+        st = _make_store(cap, layout, dev, ("P",) * has_P + ("subject",) * has_subject + ("desc",) * has_desc)
         return GalleryIndex._over(st, 0, 0, 0, sc_mode, net._pack_gen, spline_weights_id(net), layout)
 
 
@@ -1111,17 +1119,18 @@ def enroll(net, graphs, device, sc_mode=None, batch=256, layout="f32", subjects=
         index.generation, index._pack_gen = 0, net._pack_gen    # a new index: as the constructor call below records it
         return index
     with torch.cuda.device(dev):
-        y, y16, y_host, y8, s8 = rows = _alloc_rows(layout, dev, total)
+        rows = _alloc_rows(layout, dev, total)
         desc = _new_desc(descriptors, len(graphs), dev)
         src, dst, ps, cnt = _enroll_dicts(net, "enroll", graphs, dev, sc_mode, batch, rows, 0, desc=desc)
     n_all, w, P = _dict_tables(graphs, dev)
     row_off = torch.cat([torch.zeros(1, dtype=torch.int64), n_all.long().cumsum(0)])
     edge_off = torch.cat([torch.zeros(1, dtype=torch.int64), cnt.cumsum(0)])
+    y_host = rows.pop("y_host")
     if y_host is not None:
         torch.cuda.current_stream(dev).synchronize()       # the host rows are complete before they are read
-    return GalleryIndex(y if y_host is None else y_host, row_off.to(dev), n_all, src, dst, ps, edge_off, w, P, sc_mode,
-                        net._pack_gen, spline_weights_id(net), y16=y16, layout=layout, subject=subjects, y8=y8, s8=s8,
-                        desc=desc)
+        rows["y"] = y_host
+    return GalleryIndex(rows.pop("y"), row_off.to(dev), n_all, src, dst, ps, edge_off, w, P, sc_mode, net._pack_gen,
+                        spline_weights_id(net), layout=layout, subject=subjects, desc=desc, **rows)
 
 
 def _check_into(net, index, what):
@@ -1233,7 +1242,8 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
     with torch.cuda.device(dev):
         row_off = row_off_h.to(dev)
         n_d = n_h.to(torch.int32).to(dev)
-        y, y16, y_host, y8, s8 = _alloc_rows(layout, dev, total) if into is None else _store_rows(into)
+        rows = _alloc_rows(layout, dev, total) if into is None else _store_rows(into)
+        y, y_host, y16 = rows.pop("y"), rows.pop("y_host"), rows["y16"]     # the rest goes to the constructor by name
         stage = None
         if y_host is not None:
             # one sub-batch of fp32 rows on the device, reused: the copies to the host are ordered on the stream
@@ -1261,8 +1271,8 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
             ops.rows_pack(yb, nv, m, row_off[g0:g1 + 1] - r0, out32=stage if y is None else y[base + r0:base + r1],
                           out16=None if y16 is None else y16[base + r0:base + r1], n_host=nsub,
                           out_off_host=row_off_h[g0:g1 + 1] - r0)
-            if y8 is not None:
-                ops.rows_quant8(stage[:r1 - r0], y8[base + r0:base + r1], s8[base + r0:base + r1])
+            if rows["y8"] is not None:
+                ops.rows_quant8(stage[:r1 - r0], rows["y8"][base + r0:base + r1], rows["s8"][base + r0:base + r1])
             _pool_new(desc, g0, stage[:r1 - r0] if y is None else y[base + r0:base + r1], row_off_h[g0:g1 + 1] - r0, dev)
             if y_host is not None:
                 y_host[base + r0:base + r1].copy_(stage[:r1 - r0], non_blocking=True)
@@ -1285,7 +1295,7 @@ def _enroll_device(net, what, P, n_h, feats, dev, sc_mode, batch, layout, stg, s
             torch.cuda.current_stream(dev).synchronize()   # the host rows are complete before they are read
         return GalleryIndex(y if y_host is None else y_host, row_off, n_h.to(torch.int32), torch.cat(srcs),
                             torch.cat(dsts), torch.cat(pss), edge_off, w_all, Pr, sc_mode, net._pack_gen,
-                            spline_weights_id(net), y16=y16, layout=layout, subject=subjects, y8=y8, s8=s8, desc=desc)
+                            spline_weights_id(net), layout=layout, subject=subjects, desc=desc, **rows)
 
 
 def _keypoint_feats(x, w, dev):
@@ -1471,18 +1481,6 @@ class _ProbeSide:
         self.edge_off = [torch.tensor([0, int(ei.shape[1])], dtype=torch.int64)]
         self.n = [torch.tensor([n0], dtype=torch.int32, device=dev)]
         self.w0 = w0.reshape(1, -1)
-
-
-def _select_host(index, select, what):
-    """The entries a query runs over (host int64): ``select`` as given, or all entries: the live ones of an
-    index with removed slots (the one place that defines "all entries"); a removed entry is refused."""
-    if select is None:
-        return index.live
-    sel = torch.as_tensor(select, dtype=torch.int64).view(-1).cpu()
-    if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= index.G:
-        raise FpmError("%s: select must name entries in [0, %d)" % (what, index.G))
-    index._check_live(sel, what)
-    return sel
 
 
 COARSE_ROUTES = ("fused", "wide", "auto", "stream", "any")

@@ -334,8 +334,9 @@ def append8(index, add):
     quantisation written past ``used``, then the small arrays and the commit."""
     R = int(add.y.shape[0])
     at = index._begin_append("append", add.G, R, add.subject, add.P is not None)
-    y, y16, y_host, y8, s8 = gallery._store_rows(index)
-    assert y is None and y16 is None and y_host is index._store["y"] and y8 is index._store["y8"]
+    rows = gallery._store_rows(index)
+    y_host, y8, s8 = rows["y_host"], rows["y8"], rows["s8"]
+    assert rows["y"] is None and rows["y16"] is None and y_host is index._store["y"] and y8 is index._store["y8"]
     y_host[at[1]:at[1] + R].copy_(add.y)
     ops.rows_quant8(add.y, y8[at[1]:at[1] + R], s8[at[1]:at[1] + R])
     return index._finish_append("append", at, add.n, add.w, add.P, add.src, add.dst, add.pseudo,
