@@ -107,6 +107,19 @@ __global__ __launch_bounds__(1024) void instnorm_bwd_kernel(const float* __restr
     const int b = blockIdx.x, cl = threadIdx.x & 63, c = blockIdx.y * 64 + cl, g = threadIdx.x >> 6;
     const bool cv = c < Cn;
     const int nb = onehot_bias ? nvalid[b] : 0;
+    // the values relative to the channel's first position x0, as instnorm_kernel keeps them (afau.hip):
+    // the mean of x - x0 rounds at the scale of the channel's spread, not of its offset, and a channel
+    // without spread (every column-block channel c >= n2) gets xhat = 0 exactly, so dw = 0, instead
+    // of rstd = 316 times the rounding error of its fp32 mean
+    float x0 = 0.f;
+    if (cv && P > 0) {
+        if (onehot_bias) {
+            x0 = ((c == 0 && nb > 0) ? 1.f : 0.f) + onehot_bias[c];
+        } else {
+            const long o = (long)b * P * Cn + c;
+            x0 = in2 ? in1[o] + in2[o] : in1[o];
+        }
+    }
     float v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -119,10 +132,11 @@ __global__ __launch_bounds__(1024) void instnorm_bwd_kernel(const float* __restr
                 const long o = ((long)b * P + p) * Cn + c;
                 x = in2 ? in1[o] + in2[o] : in1[o];
             }
+            x -= x0;
         }
         v[k] = x;
     }
-    // statistics exactly as the forward computes them (same order, same values)
+    // statistics as the forward computes them: the same shifted values, summed in the same order
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) s += v[k];
@@ -232,8 +246,12 @@ __global__ __launch_bounds__(1024) void instnorm_bwd_kernel(const float* __restr
 
 // ---- row-block attention backward: one workgroup per (pair, head), thread t owns the columns
 // j = t + 256 u (u < TJ); rows i are walked in order.  Per (i, j):
-//   score = f_h(cost_ij) (16-term sum), att = exp(score - M_i) / S_i (forward statistics),
-//   dA = datt_h(i) . v_h(j),  dscore = att (dA - datt_h(i) . out_h(i)),
+//   score = f_h(cost_ij) (16-term sum), e = exp(score - M_i) (M_i: the forward's row max),
+//   att = e / sum_j e -- the sum is taken here over the same e, not from the forward's statistics:
+//   the forward sums exp2-approximated terms, and against them sum_j att = 1 holds only to ~1e-6,
+//   which the cancelling sum sum_j dscore = 0 turns into an error of dW2 / dW1 (measured 30-65
+//   times the fp32 CPU reference's with the init weights, whose pre-activations are ~ b1 ~ 10) --,
+//   dA = datt_h(i) . v_h(j),  dscore = att (dA - sum_j att dA),
 //   dWv[h*16 + d][j] += att datt_h(i)[d]  (j < n2b; v = 0 beyond),
 //   mixed-score grads through the active hidden units (pre = w1 c + b1 > 0).
 // Outputs per pair: dwv_part[b][h*16 + d][j] (j < n2max) and mix_part[b][h][49] =
@@ -285,16 +303,15 @@ __global__ __launch_bounds__(256) void afau_attn_bwd_kernel(const float* __restr
     }
     int ntot = 0;
     const float* Cb = cost + (long)b * c_sb;
-    __shared__ float dred[2][4];
+    __shared__ float dred[2][4], sred[2][4];
     for (int i = 0; i < n1max; ++i) {
         const long row = (long)b * n1max + i;
         float da[16];
 #pragma unroll
         for (int d = 0; d < 16; ++d) da[d] = datt[row * 256 + h * 16 + d];
-        const float2 st = stats[row * 16 + h];
-        const float invS = 1.f / st.y;
-        float cj[TJ], att[TJ], dA[TJ];
-        float part = 0.f;
+        const float M = stats[row * 16 + h].x;
+        float cj[TJ], att[TJ], dA[TJ];                      // att: e until the row sum is known
+        float part = 0.f, esum = 0.f;
 #pragma unroll
         for (int u = 0; u < TJ; ++u) {
             const int j = tid + 256 * u;
@@ -308,26 +325,35 @@ __global__ __launch_bounds__(256) void afau_attn_bwd_kernel(const float* __restr
             for (int m = 0; m < 16; ++m) sc += fmaxf(c * w1[m] + b1[m], 0.f) * w2[m];
             sc += b2;
             cj[u] = c;
-            att[u] = expf(sc - st.x) * invS;
+            att[u] = expf(sc - M);
             float a = 0.f;
 #pragma unroll
             for (int d = 0; d < 16; ++d) a = fmaf(da[d], vj[u][d], a);
             dA[u] = a;
             part = fmaf(att[u], a, part);
+            esum += att[u];
         }
-        // the softmax backward's row term sum_j att dA, reduced exactly over the row (not taken
-        // as datt . out from the forward: the bias-like parameters' true gradient is a sum with
-        // heavy cancellation, which a 1-ulp mismatch between the two would bias)
+        // the row sums sum_j e and sum_j e dA, reduced exactly over the row (neither the forward's
+        // sum nor datt . out from the forward: the bias-like parameters' true gradient is a sum
+        // with heavy cancellation, which a 1-ulp mismatch between the two would bias)
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-        if (lane == 0) dred[i & 1][wv] = part;
+        for (int o = 32; o > 0; o >>= 1) {
+            part += __shfl_xor(part, o);
+            esum += __shfl_xor(esum, o);
+        }
+        if (lane == 0) {
+            dred[i & 1][wv] = part;
+            sred[i & 1][wv] = esum;
+        }
         __syncthreads();
-        const float dot = ((dred[i & 1][0] + dred[i & 1][1]) + dred[i & 1][2]) + dred[i & 1][3];
+        const float invS = 1.f / (((sred[i & 1][0] + sred[i & 1][1]) + sred[i & 1][2]) + sred[i & 1][3]);
+        const float dot = (((dred[i & 1][0] + dred[i & 1][1]) + dred[i & 1][2]) + dred[i & 1][3]) * invS;
 #pragma unroll
         for (int u = 0; u < TJ; ++u) {
             const int j = tid + 256 * u;
             if (j >= n2max) continue;
             const float c = cj[u];
+            att[u] *= invS;
 #pragma unroll
             for (int d = 0; d < 16; ++d) dwv[u][d] = fmaf(att[u], da[d], dwv[u][d]);
             const float ds = att[u] * (dA[u] - dot);

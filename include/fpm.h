@@ -405,8 +405,9 @@ int fpm_soft_topk_fwd_f64(const double* ss, long s_sb, long s_ld, const int* n1,
  *   block's one-hot + bias; seed dy (dense) or gseed (max-pool gradient routed to the argmax);
  *   dx (optional, accumulate) and per-pair dw / db partials (B x Cn).
  * fpm_afau_attn_bwd: the row block's cross-set attention (afau.py:231-300 with R0 = 0) given the
- *   forward's output and softmax stats: per-pair dWv partials (B x 256 x n2max) and mixed-score
- *   partials (B x 16 x 49 = [dW2 | dW1 row 1 | db1 | db2]).
+ *   forward's softmax stats (only the row max is read; the row sum is formed again over the
+ *   backward's own terms): per-pair dWv partials (B x 256 x n2max) and mixed-score partials
+ *   (B x 16 x 49 = [dW2 | dW1 row 1 | db1 | db2]).
  * fpm_rows_sum: out[u][k] (+)= sum_b in[b][k] in order over the b with key[b] == u, or (key NULL)
  *   over the u-th of nkeys contiguous row chunks (deterministic).
  * fpm_transpose: out[c][r] = in[r][c], rows [R, ldo) of out zero.
