@@ -56,6 +56,11 @@ SIGNATURES = {
     "fpm_group_topr": (I, [P, L, I, I, P, L, P, L, I, I, P, P, P]),
     "fpm_cohort_decide": (I, [P, I, I, I, I, I, F, I, I, F, P, P, P, P, P, P]),
     "fpm_topk_merge": (I, [P, P, L, I, ctypes.POINTER(I), I, I, P, P, P, P]),
+    "fpm_mate_rank_ws_bytes": (L, [I]),
+    "fpm_mate_rank": (I, [P, L, I, I, P, P, L, P, P, P, P, P, L, P]),
+    "fpm_score_census": (I, [P, L, I, I, P, P, L, P, P, I, P, P, P, P]),
+    "fpm_score_select_ws_bytes": (L, []),
+    "fpm_score_select": (I, [P, L, I, I, P, P, L, P, I, L, ctypes.POINTER(F), ctypes.POINTER(L), P, L, P]),
     "fpm_coarse_score_wide_ws_bytes": (L, [I]),
     "fpm_coarse_score_stream_ws_bytes": (L, [I, I, I]),
     "fpm_rows_fetch": (I, [P, L, P, P, I, I, I, P, L, P, P]),

@@ -1792,6 +1792,17 @@ class Net(nn.Module):
                                      cohort_skip=cohort_skip, sigma_floor=sigma_floor, threshold=threshold,
                                      prescreen=prescreen)
 
+    def evaluate_search(self, probes, index, ks=(1, 5, 10), **query):
+        """``identify_many(probes, index, **query)`` on labelled sets, and where each probe's mate went: see
+        ``evaluate.search_report``."""
+        from . import evaluate
+        return evaluate.search_report(self, probes, index, ks=ks, **query)
+
+    def stage_ranks(self, probes, index, **kw):
+        """The rank of every probe's mate at each stage of the search: see ``evaluate.stage_ranks``."""
+        from . import evaluate
+        return evaluate.stage_ranks(self, probes, index, **kw)
+
     def _need_backbone(self):
         if not hasattr(self, "node_layers"):
             raise NotImplementedError("image input needs the backbone: this Net was built with backbone=False "

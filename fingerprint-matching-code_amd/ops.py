@@ -3,7 +3,7 @@
 Every op takes device tensors, checks shapes/dtypes on the host, and launches on the current
 torch stream.  Outputs are caller-allocated (``torch.empty`` on the tensor's device).  There is
 no CPU fallback: a CPU tensor or a missing library raises (``rank_topk``, ``rank_select``, ``rank_keep``,
-``rows_pool``, ``desc_score``, ``topk_merge``,
+``mate_rank``, ``score_census``, ``score_select``, ``rows_pool``, ``desc_score``, ``topk_merge``,
 ``group_scores``, ``group_topr``, ``cohort_decide``, ``coarse_score`` / ``coarse_pairs``, ``rows_fetch``,
 ``rows_pack``, ``rows_move`` and ``rows_quant8`` alone keep a plain-torch host path for CPU tensors: the statements
 of the ordering and of the merge of
@@ -796,6 +796,167 @@ def rank_keep(scores, k, keep=None):
     ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
     _lib.call("fpm_rank_keep", _p(scores), ld, P, G, k, _p(keep), _p(ws), wsb, _stream(scores))
     return keep
+
+
+# ---- evaluation of a search from its score matrices (``fpm.evaluate``) -----------------------------
+CENSUS_TMAX = 4095
+SCORE_CLASSES = ("genuine", "impostor")
+
+
+def _eval_args(op, scores, row_lab, col_lab, own):
+    """The common inputs of ``mate_rank``, ``score_census`` and ``score_select``, checked on the host before
+    anything is launched -> (scores with dense columns, its row stride, P, G, the labels' leading dimension)."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
+        raise _lib.FpmError("%s: scores must be a (P, G) fp32 tensor" % op)
+    P, G = int(scores.shape[0]), int(scores.shape[1])
+    if G < 1:
+        raise _lib.FpmError("%s: scores must have at least one column" % op)
+    for name, t in (("row_lab", row_lab), ("col_lab", col_lab), ("own", own)):
+        if t is None and name == "own":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise _lib.FpmError("%s: %s must be a contiguous int32 tensor (got %s)"
+                                % (op, name, getattr(t, "dtype", type(t).__name__)))
+        if t.device != scores.device:
+            raise _lib.FpmError("%s: %s is on %s, scores on %s" % (op, name, t.device, scores.device))
+    _shape(row_lab, (P,), "%s row_lab" % op)
+    _shape(own, (P,), "%s own" % op)
+    if tuple(col_lab.shape) not in ((G,), (P, G)):
+        raise _lib.FpmError("%s: col_lab of shape %s where (G,) = %s or (P, G) = %s is required"
+                            % (op, tuple(col_lab.shape), (G,), (P, G)))
+    lab_ld = G if col_lab.dim() == 2 else 0
+    if G > 1 and scores.stride(1) != 1:
+        scores = scores.contiguous()
+    ld = int(scores.stride(0)) if P > 1 else G
+    if ld < G:
+        scores, ld = scores.contiguous(), G
+    return scores, ld, P, G, lab_ld
+
+
+def score_classes(scores, row_lab, col_lab, own=None):
+    """The classes of a score matrix, in plain torch -> (genuine, impostor) bool masks (P, G); a score in neither
+    is ignored: a column with ``col_lab < 0``, and the column ``own[p]`` of row p.  Otherwise genuine where
+    ``col_lab == row_lab[p]``, else impostor."""
+    P, G = int(scores.shape[0]), int(scores.shape[1])
+    cl = col_lab if col_lab.dim() == 2 else col_lab.view(1, G).expand(P, G)
+    ign = cl < 0
+    if own is not None:
+        ign = ign | (torch.arange(G, device=scores.device, dtype=torch.int32).view(1, G) == own.view(P, 1))
+    gen = ~ign & (cl == row_lab.view(P, 1))
+    return gen, ~ign & ~gen
+
+
+def mate_rank(scores, row_lab, col_lab, own=None):
+    """Where every row's mate ranks among the impostors (fpm_mate_rank): scores (P, G) fp32 (any row stride),
+    row_lab (P,) int32, col_lab (G,) or (P, G) int32, own (P,) int32 or None (``score_classes``) ->
+
+        mate_col   (P,) int32  the genuine column with the greatest ``rank_key``, -1 if the row has none;
+        mate_score (P,) fp32   that column's bits, NaN 0x7FC00000 if none;
+        mate_rank  (P,) int32  the number of impostor columns whose key is above the mate's, -1 if none.
+
+    The mate survives a cut to the K best exactly when ``mate_rank < K`` if the row has one genuine column; with
+    several, the rank is the best one's and the other genuine columns also take places in the cut (each further
+    impression needs the rank plus the genuine columns above it below K).  Device tensors
+    run the kernels (a 64-bit integer atomic max, then integer adds); CPU tensors take the statement below.  Keys
+    are unique and integer sums have one value, so the two agree bit for bit."""
+    op = "mate_rank"
+    scores, ld, P, G, lab_ld = _eval_args(op, scores, row_lab, col_lab, own)
+    if not scores.is_cuda:
+        gen, imp = score_classes(scores, row_lab, col_lab, own)
+        key = rank_key(scores)
+        low = torch.iinfo(torch.int64).min
+        best = torch.where(gen, key, torch.full_like(key, low)).max(1).values if P else key.new_empty(0)
+        has = gen.any(1)
+        col = torch.where(has, 0xFFFFFFFF - (best & 0xFFFFFFFF), torch.full_like(best, -1))
+        rank = (imp & (key > best.view(P, 1))).sum(1)
+        qnan = torch.full((P,), 0x7FC00000, dtype=torch.int32).view(torch.float32)
+        sc = torch.where(has, torch.gather(scores, 1, col.clamp(min=0).view(P, 1)).view(P).view(torch.int32),
+                         qnan.view(torch.int32)).view(torch.float32)
+        return col.to(torch.int32), sc, torch.where(has, rank, torch.full_like(rank, -1)).to(torch.int32)
+    dev = scores.device
+    mcol = torch.empty(P, device=dev, dtype=torch.int32)
+    msc = torch.empty(P, device=dev, dtype=torch.float32)
+    mrank = torch.empty(P, device=dev, dtype=torch.int32)
+    if P == 0:
+        return mcol, msc, mrank
+    wsb = int(_lib.load().fpm_mate_rank_ws_bytes(P))
+    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+    _lib.call("fpm_mate_rank", _p(scores), ld, P, G, _p(row_lab), _p(col_lab), lab_ld, _p(own), _p(mcol), _p(msc),
+              _p(mrank), _p(ws), wsb, _stream(scores))
+    return mcol, msc, mrank
+
+
+def _check_edges(op, edges, scores):
+    if not isinstance(edges, torch.Tensor) or edges.dtype != torch.float32 or edges.dim() != 1 \
+            or not edges.is_contiguous():
+        raise _lib.FpmError("%s: edges must be a contiguous 1-d fp32 tensor" % op)
+    if edges.device != scores.device:
+        raise _lib.FpmError("%s: edges is on %s, scores on %s" % (op, edges.device, scores.device))
+    T = int(edges.numel())
+    if not 1 <= T <= CENSUS_TMAX:
+        raise _lib.FpmError("%s: T = %d edges outside [1, %d]" % (op, T, CENSUS_TMAX))
+    eh = edges.cpu()
+    if not bool(torch.isfinite(eh).all()):
+        raise _lib.FpmError("%s: edges must be finite" % op)
+    if T > 1 and not bool((eh[1:] > eh[:-1]).all()):
+        raise _lib.FpmError("%s: edges must be strictly ascending" % op)
+    return T
+
+
+def score_census(scores, row_lab, col_lab, edges, own=None):
+    """The histograms of the genuine and the impostor scores of a whole matrix (fpm_score_census): the common
+    inputs of ``mate_rank``, and ``edges`` (T,) fp32, finite, strictly ascending, 1 <= T <= 4095 ->
+    (gen (T + 1,) int64, imp (T + 1,) int64, skipped (3,) int64: NaN genuine, NaN impostor, ignored).
+    bin(s) = the number of edges <= s (``torch.bucketize(s, edges, right=True)``): a score equal to an edge falls
+    in the upper bin, -inf in bin 0, +inf in bin T.  gen.sum() + imp.sum() + skipped.sum() == P * G.  Device
+    tensors run the kernel (32-bit histograms in LDS, 64-bit integer atomic adds), CPU tensors the statement;
+    integer counts have one value, so the two agree exactly."""
+    op = "score_census"
+    scores, ld, P, G, lab_ld = _eval_args(op, scores, row_lab, col_lab, own)
+    T = _check_edges(op, edges, scores)
+    if not scores.is_cuda:
+        gen, imp = score_classes(scores, row_lab, col_lab, own)
+        nan = torch.isnan(scores)
+        b = torch.bucketize(scores, edges, right=True)
+        hist = lambda m: torch.bincount(b[m & ~nan].view(-1), minlength=T + 1)
+        skipped = torch.stack([(gen & nan).sum(), (imp & nan).sum(), (~gen & ~imp).sum()])
+        return hist(gen), hist(imp), skipped
+    dev = scores.device
+    out = torch.empty(2 * (T + 1) + 3, device=dev, dtype=torch.int64)
+    gen, imp, skipped = out[:T + 1], out[T + 1:2 * T + 2], out[2 * T + 2:]
+    _lib.call("fpm_score_census", _p(scores), ld, P, G, _p(row_lab), _p(col_lab), lab_ld, _p(own), _p(edges), T,
+              _p(gen), _p(imp), _p(skipped), _stream(scores))
+    return gen, imp, skipped
+
+
+def score_select(scores, row_lab, col_lab, cls, k, own=None):
+    """The k-th largest (1-based) non-NaN score of one class over a whole matrix (fpm_score_select): the common
+    inputs of ``mate_rank``, ``cls`` "genuine" or "impostor", k >= 1 -> (value: a 0-d fp32 host tensor, the exact
+    bits of that score -- -0 ranks below +0 --, NaN 0x7FC00000 when k exceeds the count; count: the class's number
+    of non-NaN scores, an int).  Device tensors run three radix passes over the order-preserving score bits (11, 11
+    and 10 bits), each histogram read back on the host (the call synchronises the stream: an offline tool); CPU
+    tensors take a sort."""
+    op = "score_select"
+    scores, ld, P, G, lab_ld = _eval_args(op, scores, row_lab, col_lab, own)
+    if cls not in SCORE_CLASSES:
+        raise _lib.FpmError("%s: cls must be one of %s (got %r)" % (op, SCORE_CLASSES, cls))
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise _lib.FpmError("%s: k = %r must be an integer >= 1" % (op, k))
+    if not scores.is_cuda:
+        m = score_classes(scores, row_lab, col_lab, own)[SCORE_CLASSES.index(cls)] & ~torch.isnan(scores)
+        n = int(m.sum())
+        if k > n:
+            return torch.full((), 0x7FC00000, dtype=torch.int32).view(torch.float32), n
+        key = rank_key(scores[m].view(1, -1), ids=torch.zeros(1, n, dtype=torch.int64))[0]
+        at = torch.argsort(key, descending=True, stable=True)[k - 1]
+        return scores[m][at].clone(), n
+    value, count = ctypes.c_float(), ctypes.c_long()
+    wsb = int(_lib.load().fpm_score_select_ws_bytes())
+    ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
+    _lib.call("fpm_score_select", _p(scores), ld, P, G, _p(row_lab), _p(col_lab), lab_ld, _p(own),
+              1 + SCORE_CLASSES.index(cls), k, ctypes.byref(value), ctypes.byref(count), _p(ws), wsb, _stream(scores))
+    bits = ctypes.c_int32.from_buffer_copy(value).value
+    return torch.full((), bits, dtype=torch.int32).view(torch.float32), int(count.value)
 
 
 DESC_DIM = 768

@@ -681,6 +681,42 @@ int fpm_cohort_decide(const float* top, int P, int K, int k, int skip, int cohor
 int fpm_topk_merge(const float* score, const int* id, long ld, int P, const int* list_off, int S, int k, int* top_id,
                    float* top_score, int* top_col, void* stream);
 
+/* ---- evaluation of a search from its score matrices ----------------------------------------------
+ * Common inputs: scores P x G fp32, row p at scores + p * ld (ld >= G, columns dense); row_lab (P) int32;
+ * col_lab int32, read at col_lab + p * lab_ld: lab_ld 0 for one row of G labels shared by all rows, or
+ * lab_ld >= G for one row of labels per row; own (P) int32 or NULL: a column that row p ignores, -1 for none.
+ * The class of score (p, j): ignored when col_lab < 0 or j == own[p]; else genuine when col_lab == row_lab[p];
+ * else impostor.  The order is fpm_rank_topk's key (score descending, ties to the lower column, NaN after
+ * every number, -0 below +0).  Grid (slices of 4096 columns, rows), 256 threads, 16 columns a thread.  Only
+ * integer atomics (a 64-bit max, 32- and 64-bit adds): one answer whatever the schedule.  No scratch.
+ *
+ * fpm_mate_rank: per row, mate_col = the genuine column with the greatest key (-1: the row has none),
+ * mate_score = that column's bits (0x7FC00000 if none), mate_rank = the number of impostor columns whose key
+ * is above the mate's (-1 if none).  Two launches: the largest genuine key per row (one 64-bit atomic max per
+ * workgroup and row), then the count (one integer add).  ws: fpm_mate_rank_ws_bytes(P) bytes of device
+ * scratch, owned by the call until the stream has run it (the entry point clears it on the stream). */
+long fpm_mate_rank_ws_bytes(int P);
+int fpm_mate_rank(const float* scores, long ld, int P, int G, const int* row_lab, const int* col_lab, long lab_ld,
+                  const int* own, int* mate_col, float* mate_score, int* mate_rank, void* ws, long ws_bytes,
+                  void* stream);
+/* fpm_score_census: the histogram of the genuine and of the impostor scores of the whole matrix over T edges
+ * (device fp32, finite, strictly ascending -- the caller's to check --, 1 <= T <= 4095): bin(s) = the number of
+ * edges <= s, so a score equal to an edge falls in the upper bin, -inf in bin 0, +inf in bin T.  gen, imp:
+ * T + 1 int64 counts each; skipped: 3 int64 counts -- NaN genuine, NaN impostor, ignored (device; the entry point
+ * clears all three on the stream).  gen + imp + skipped sum to P * G.  One launch: 32-bit histograms in LDS,
+ * the edges beside them (sized by T, at most 48 KB a workgroup; the bin by a binary search of fixed length), one
+ * 64-bit atomic add per non-empty bin and workgroup. */
+int fpm_score_census(const float* scores, long ld, int P, int G, const int* row_lab, const int* col_lab, long lab_ld,
+                     const int* own, const float* edges, int T, long* gen, long* imp, long* skipped, void* stream);
+/* fpm_score_select: *value (host) = the k-th largest (k >= 1) non-NaN score of class cls (1 genuine, 2 impostor)
+ * over the whole matrix, exact bits; *count (host) = the class's number of non-NaN scores; k > *count gives
+ * 0x7FC00000.  Three radix passes over the order-preserving score bits (11, 11, 10 bits), one launch each over
+ * the scores that match the prefix found so far; the entry point reads each histogram back and synchronises the
+ * stream (an offline tool).  ws: fpm_score_select_ws_bytes() bytes of device scratch. */
+long fpm_score_select_ws_bytes(void);
+int fpm_score_select(const float* scores, long ld, int P, int G, const int* row_lab, const int* col_lab, long lab_ld,
+                     const int* own, int cls, long k, float* value, long* count, void* ws, long ws_bytes, void* stream);
+
 /* ---- coarse 1:N score (the first pass of a shortlisted identification) ---------------------------
  * One scalar per (probe, enrolled entry) pair, one workgroup per pair, B pairs per launch:
  *   a = bf16(yp o coef[b]) (one fp32 multiply, round to nearest even), b = bf16(y rows of idx[b]),
