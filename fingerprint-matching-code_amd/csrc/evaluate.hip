@@ -5,8 +5,8 @@
 //
 // Classes of a score (p, j): ignored when col_lab < 0 or j == own[p]; genuine when col_lab == row_lab[p];
 // impostor otherwise.  col_lab is read at col_lab + p * lab_ld (lab_ld 0: one row of labels for all probes).
-// Ordering: rank.hip's key, (order-preserving score bits) << 32 | (0xFFFFFFFF - column): score descending,
-// ties to the lower column, NaN after every number, -0 below +0.
+// Ordering: the ranking key of rank_key.h over (score, column): score descending, ties to the lower column,
+// NaN after every number, -0 below +0.
 //
 // Grid (slices of EV_SLICE columns, rows): 256 threads, thread t of slice s holds the columns
 // s * 4096 + t + 256 i, i < 16 (coalesced, 16 loads in flight), and walks the rows blockIdx.y, + gridDim.y, ...
@@ -21,10 +21,11 @@
 //               compare and a select), one 64-bit atomic add per non-empty bin; LDS by T, at most 48 KB
 //   tally<1>    radix pass: the same over a digit of the score bits, for the scores of one class that match the
 //               prefix found so far; three passes (11, 11, 10 bits), the histogram read on the host in between
-#include "fpm_common.h"
+#include "rank_key.h"
 #include "fpm.h"
 
 namespace {
+using namespace fpm;
 constexpr int EV_THREADS = 256;
 constexpr int EV_PER = 16;
 constexpr int EV_SLICE = EV_THREADS * EV_PER;      // 4096 columns per workgroup
@@ -32,20 +33,6 @@ constexpr int EV_TMAX = 4095;                      // edges of a census
 constexpr int EV_ROWS_MAX = 1 << 19;               // rows per workgroup: 2^19 * 4096 = 2^31 fits an LDS counter
 constexpr int EV_TALLY_BLOCKS = 1024;              // workgroups of a tally launch (about four per CU)
 constexpr int EV_RADIX_BINS = 2048;
-typedef unsigned long long u64;
-
-// as rank.hip's rank_bits
-__device__ __forceinline__ uint32_t ev_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ u64 ev_key(float f, int j) { return ((u64)ev_bits(f) << 32) | (0xFFFFFFFFu - (uint32_t)j); }
-
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
-    return ((u64)hi << 32) | lo;
-}
 
 struct EvalIn {
     const float* scores;
@@ -104,19 +91,15 @@ __device__ __forceinline__ void ev_walk(const EvalIn& in, Begin&& begin, Elem&& 
 __global__ __launch_bounds__(EV_THREADS) void mate_max_kernel(EvalIn in, u64* __restrict__ best) {
     __shared__ u64 part[EV_THREADS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 b = 0ull;                                  // below every key: a key's column field is >= 2^31
+    u64 b = 0ull;                                  // below every key
     ev_walk(
         in, [&](long) { b = 0ull; },
         [&](long, int, int j, float x, int c) {
-            const u64 key = ev_key(x, j);
+            const u64 key = rank_key(x, (uint32_t)j);
             if (c == 1 && key > b) b = key;
         },
         [&](long p) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const u64 o = shfl_xor_u64(b, m);
-                b = o > b ? o : b;
-            }
+            b = team_max_u64<64>(b);
             if (lane == 0) part[wave] = b;
             __syncthreads();
             if (threadIdx.x == 0) {
@@ -143,7 +126,7 @@ __global__ __launch_bounds__(EV_THREADS) void mate_count_kernel(EvalIn in, const
             T = best[p];
             cnt = 0;
         },
-        [&](long, int, int j, float x, int c) { cnt += (c == 2 && T != 0ull && ev_key(x, j) > T) ? 1 : 0; },
+        [&](long, int, int j, float x, int c) { cnt += (c == 2 && T != 0ull && rank_key(x, (uint32_t)j) > T) ? 1 : 0; },
         [&](long p) {
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
@@ -157,10 +140,10 @@ __global__ __launch_bounds__(EV_THREADS) void mate_count_kernel(EvalIn in, const
                 if (blockIdx.x == 0) {
                     if (T == 0ull) {                                // no mate: no workgroup adds to this row
                         mate_col[p] = -1;
-                        mate_score[p] = __uint_as_float(0x7FC00000u);
+                        mate_score[p] = qnan();
                         mate_rank[p] = -1;
                     } else {
-                        const int col = (int)(0xFFFFFFFFu - (uint32_t)T);
+                        const int col = (int)rank_index(T);
                         mate_col[p] = col;
                         mate_score[p] = in.scores[p * in.ld + col];
                     }
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(EV_THREADS) void tally_kernel(EvalIn in, TallyArgs 
     for (int b = threadIdx.x; b < nb; b += EV_THREADS) hist[b] = 0u;
     if (MODE == 0)                                 // the edges, padded with NaN (never <= a score) to 2 top - 1
         for (int t = threadIdx.x; t < 2 * a.top - 1; t += EV_THREADS)
-            ev_lds[nb + t] = t < a.T ? __float_as_uint(a.edges[t]) : 0x7FC00000u;
+            ev_lds[nb + t] = t < a.T ? __float_as_uint(a.edges[t]) : QNAN_BITS;
     if (threadIdx.x < 3) skip[threadIdx.x] = 0u;
     __syncthreads();
     uint32_t nan_gen = 0u, nan_imp = 0u, ignored = 0u;
@@ -211,7 +194,7 @@ __global__ __launch_bounds__(EV_THREADS) void tally_kernel(EvalIn in, TallyArgs 
                 xs[i] = x;
                 cs[i] = c;
             } else if (c == a.want && x == x) {
-                const uint32_t bits = ev_bits(x);
+                const uint32_t bits = rank_bits(x);
                 if ((uint32_t)((u64)bits >> a.hi_shift) == a.prefix) atomicAdd(&hist[(bits >> a.shift) & mask], 1u);
             }
         },
@@ -337,9 +320,8 @@ extern "C" int fpm_score_select(const float* scores, long ld, int P, int G, cons
     FPM_CHECK_ARG(value && count, "score_select: value and count (host) are required");
     FPM_CHECK_ARG(ws && ws_bytes >= fpm_score_select_ws_bytes(), "score_select: workspace of %ld bytes, %ld needed",
                   ws_bytes, fpm_score_select_ws_bytes());
-    const uint32_t qnan = 0x7FC00000u;
     *count = 0;
-    __builtin_memcpy(value, &qnan, 4);
+    __builtin_memcpy(value, &QNAN_BITS, 4);
     if (P == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const EvalIn in{scores, ld, P, G, row_lab, col_lab, lab_ld, own};

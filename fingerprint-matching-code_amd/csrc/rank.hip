@@ -2,59 +2,40 @@
 // best gallery entries in descending score order, ties to the lower index, NaN after every number
 // (NaNs among themselves by index).
 //
-// Every element gets a 64-bit key, (order-preserving bits of the score) << 32 | (0xFFFFFFFF - index),
-// unique per element, so the ranking is "the k largest keys" with no tie logic: round j takes the
-// largest key below round j-1's.  One workgroup per row streams the row once per round (k <= 128; the
-// row of one probe is a few KB and stays in L2); wave max-reduce on __shfl_xor, the four waves join
-// through LDS.  Deterministic: a max over unique keys has one answer.
-#include "fpm_common.h"
+// Every element gets its ranking key (rank_key.h), unique per element, so the ranking is "the k
+// largest keys" with no tie logic: round j takes the largest key below round j-1's.  One workgroup
+// per row streams the row once per round (k <= 128; the row of one probe is a few KB and stays in
+// L2); wave max-reduce on __shfl_xor, the four waves join through LDS.  Deterministic: a max over
+// unique keys has one answer.
+#include "rank_key.h"
 #include "fpm.h"
 
 namespace {
+using namespace fpm;
 constexpr int RANK_THREADS = 256;
-
-// fp32 bits -> unsigned, monotone in the value: negatives below positives (-0 below +0), NaN -> 0
-// (below -inf, which maps to 0x007FFFFF)
-__device__ __forceinline__ uint32_t rank_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(RANK_THREADS) void rank_topk_kernel(const float* __restrict__ scores, long ld, int G, int k,
                                                                  int* __restrict__ top_idx,
                                                                  float* __restrict__ top_score) {
-    __shared__ unsigned long long part[2][RANK_THREADS / 64];
+    __shared__ u64 part[2][RANK_THREADS / 64];
     const float* row = scores + (long)blockIdx.x * ld;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // every key is below 2^64 - 1: rank_bits never returns 0xFFFFFFFF (that would be the positive NaN
-    // pattern 0x7FFFFFFF, which maps to 0)
-    unsigned long long prev = ~0ull;
+    u64 prev = ~0ull;                          // above every key
     for (int j = 0; j < k; ++j) {
-        unsigned long long best = 0ull;        // below every key: a key's index field is >= 1 (G is an int)
+        u64 best = 0ull;                       // below every key
         for (int i = threadIdx.x; i < G; i += RANK_THREADS) {
-            const unsigned long long key = ((unsigned long long)rank_bits(row[i]) << 32) | (0xFFFFFFFFu - (uint32_t)i);
+            const u64 key = rank_key(row[i], (uint32_t)i);
             if (key < prev && key > best) best = key;
         }
-        best = wave_max_u64(best);
+        best = team_max_u64<64>(best);
         if (lane == 0) part[j & 1][wave] = best;
         __syncthreads();                       // part[] alternates, so one barrier per round suffices
-        unsigned long long m = part[j & 1][0];
+        u64 m = part[j & 1][0];
 #pragma unroll
         for (int w = 1; w < RANK_THREADS / 64; ++w) m = part[j & 1][w] > m ? part[j & 1][w] : m;
         prev = m;
         if (threadIdx.x == 0) {
-            const int i = (int)(0xFFFFFFFFu - (uint32_t)m);
+            const int i = (int)rank_index(m);
             top_idx[(long)blockIdx.x * k + j] = i;
             top_score[(long)blockIdx.x * k + j] = row[i];
         }

@@ -1,8 +1,8 @@
 // Merge of sorted candidate lists (a gallery spread over several devices: every shard's shortlist, carried
 // to one device, merged into the global shortlist).  Row p holds L = list_off[S] candidates, a score and an
-// id each; list t is the columns [list_off[t], list_off[t + 1]).  key(c) = rs_bits(score) << 32 |
-// (0xFFFFFFFF - id): rank_select.hip's key with the candidate's id (a global entry number) in place of its
-// column, so a tie between lists goes to the lower id wherever the two candidates sit in the row.
+// id each; list t is the columns [list_off[t], list_off[t + 1]).  key(c) = rank_key(score, id): the
+// ranking key of rank_key.h with the candidate's id (a global entry number) in place of its column, so a
+// tie between lists goes to the lower id wherever the two candidates sit in the row.
 //
 // Precondition (what fpm_rank_select over a shard plus an ascending id table gives): every list is strictly
 // descending by key, and the ids of a row are distinct, so keys are unique.
@@ -21,23 +21,16 @@
 //
 // For data that breaks the precondition the kernel still ends and stays inside its buffers: a search is
 // bounded by its list, and a slot is used only below k.  Slots may then be written twice or not at all.
-#include "fpm_common.h"
+#include "rank_key.h"
 #include "fpm.h"
 
 namespace {
+using namespace fpm;
 constexpr int MG_THREADS = 1024;
-typedef unsigned long long u64;
 
 struct MergeLists {
     int off[FPM_TOPK_MERGE_SMAX + 1];
 };
-
-// as rank_select.hip's rs_bits
-__device__ __forceinline__ uint32_t mg_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __global__ __launch_bounds__(MG_THREADS) void topk_merge_kernel(const float* __restrict__ score,
                                                                 const int* __restrict__ id, long ld, MergeLists lists,
@@ -56,7 +49,7 @@ __global__ __launch_bounds__(MG_THREADS) void topk_merge_kernel(const float* __r
     for (int w = threadIdx.x; w < items; w += MG_THREADS) {
         const int t = w / k, j = w - t * k;
         const int c = off[t] + j;
-        if (c < off[t + 1]) keys[c] = ((u64)mg_bits(rs[c]) << 32) | (0xFFFFFFFFu - (uint32_t)ri[c]);
+        if (c < off[t + 1]) keys[c] = rank_key(rs[c], (uint32_t)ri[c]);
     }
     __syncthreads();
     for (int w = threadIdx.x; w < items; w += MG_THREADS) {

@@ -7,22 +7,17 @@
 // __builtin_sqrtf are the correctly rounded ones under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt.
 //
 // ---- group_topr: the mean of a group's r best entries ------------------------------------------------------
-// Groups as rank_group.hip takes them (CSR tables, shared or per row).  For a group of c >= 1 entries
+// The groups, their walk and gbest as rank_groups.h defines them.  For a group of c >= 1 entries
 // x[0..c) (x[j] = scores[p][pos[off + j]]):
-//   gbest   as fpm_group_scores: the position with the largest ranking key (score bits << 32 |
-//           0xFFFFFFFF - position): the best score, ties to the lower position, NaN below every number.
 //   gscore  r' = min(r, c); the r' entries that rank first by (score descending, NaN last), x1 .. x_r';
 //           s = +0.0, s = s + x1, ..., s = s + x_r' (fp32, in that order); s / fp32(r'); NaN as 0x7FC00000.
 //           Entries that tie have the same value, so their order among themselves changes no bit.
 //   empty   0x7FC00000, -1.
 // Selection: r rounds; in each, every lane of the group's team scans its strided entries for the largest
-// selection key (score bits << 32 | 0xFFFFFFFF - j, j the entry's place in the group: unique even if a
+// selection key (the ranking key over (score, j), j the entry's place in the group: unique even if a
 // position repeats) strictly below the previous round's winner, an xor butterfly over (key, value) finds
 // the team's, and every lane adds the winner's value.  All 64 lanes of a wave run all r rounds and reach
 // every shuffle, whatever their teams' counts: an exhausted team carries key 0 and adds nothing.
-// Layout of group_scores_kernel: grid (tiles of 64 groups, P rows), 256 threads = 16 teams of 16 lanes for
-// groups of at most 1024 entries, a whole wave for larger ones; no LDS, no atomics, nothing shared between
-// workgroups.
 //
 // ---- cohort_decide: z-scores of a ranked row against its own tail ------------------------------------------
 // top (P, K) fp32 contiguous, a row as fpm_rank_select returns it (descending, NaN last).  Row p's cohort:
@@ -36,76 +31,49 @@
 // One wave per row, four rows per workgroup of 256 threads; the wave compacts the window's non-NaN values
 // into its 4 KB of LDS (at most 16 rounds of 64 columns: ballot and prefix count), so that the statement's
 // order holds for any row, sorted or not.  Plain vector stores.
-#include "fpm_common.h"
+#include "rank_groups.h"
 #include "fpm.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int GRP_THREADS = 256;
-constexpr int GRP_TEAM = 16;
-constexpr int GRP_TILE = 64;                       // groups per workgroup
-constexpr int GRP_WIDE = 1024;                     // counts above this take a whole wave
+using namespace fpm;
 constexpr int COH_ROWS = 4;                        // rows (waves) per workgroup
 constexpr int COH_WINDOW = 1024;                   // skip + cohort at most: 16 rounds of 64 columns
-typedef unsigned long long u64;
 
 __device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
 __device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
 __device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
 __device__ __forceinline__ float div_rn(float a, float b) { return a / b; }
 __device__ __forceinline__ float sqrt_rn(float a) { return __builtin_sqrtf(a); }
-__device__ __forceinline__ float qnan() { return __uint_as_float(0x7FC00000u); }
 // Store v with every NaN as 0x7FC00000.  On the bits, through an integer store: a select between floats
 // ("v != v ? qnan : v") may be folded away, since the compiler is free to assume which NaN an operation returned
 // (it was, for the square root: sigma came out as 0xFFC00000).
 __device__ __forceinline__ void store_canon(float* __restrict__ at, float v) {
     const uint32_t u = __float_as_uint(v);
-    *reinterpret_cast<uint32_t*>(at) = (u & 0x7FFFFFFFu) > 0x7F800000u ? 0x7FC00000u : u;
-}
-
-// as rank.hip's rank_bits
-__device__ __forceinline__ uint32_t open_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
-    return ((u64)hi << 32) | lo;
+    *reinterpret_cast<uint32_t*>(at) = (u & 0x7FFFFFFFu) > 0x7F800000u ? QNAN_BITS : u;
 }
 
 // One group of c entries at pos[0..c) by a team of W lanes (t: the lane's number in its team), r rounds.
 // Every lane of the team leaves with the same sum, count of entries taken and best position key (0: none).
-// A position outside [0, G) (the host wrapper refuses them) is read as NaN and never is gbest.
 template <int W>
 __device__ __forceinline__ void group_select(const float* __restrict__ row, int G, const int* __restrict__ pos, int c,
                                              int t, int r, float& sum, int& taken, u64& best) {
-    auto read = [&](int q) { return (unsigned)q < (unsigned)G ? row[q] : qnan(); };
-    u64 pb = 0ull;                                 // gbest: below every key (a key's position field is >= 2^31)
+    u64 pb = 0ull;                                 // gbest: below every key
     for (int j = t; j < c; j += W) {
         const int q = pos[j];
-        if ((unsigned)q < (unsigned)G) {
-            const u64 key = ((u64)open_bits(row[q]) << 32) | (0xFFFFFFFFu - (uint32_t)q);
-            pb = key > pb ? key : pb;
-        }
+        pb = group_best(pb, G, q, group_read(row, G, q));
     }
-#pragma unroll
-    for (int m = W / 2; m >= 1; m >>= 1) {
-        const u64 o = shfl_xor_u64(pb, m);
-        pb = o > pb ? o : pb;
-    }
-    best = pb;
+    best = team_max_u64<W>(pb);
     float s = 0.f;
     int n = 0;
     u64 prev = ~0ull;                              // above every key
     for (int round = 0; round < r; ++round) {      // r is uniform over the launch
-        u64 b = 0ull;                              // below every selection key (its place field is >= 2^31)
+        u64 b = 0ull;                              // below every selection key
         float bx = 0.f;
         for (int j = t; j < c; j += W) {
-            const float x = read(pos[j]);
-            const u64 key = ((u64)open_bits(x) << 32) | (0xFFFFFFFFu - (uint32_t)j);
+            const float x = group_read(row, G, pos[j]);
+            const u64 key = rank_key(x, (uint32_t)j);
             if (key < prev && key > b) {
                 b = key;
                 bx = x;
@@ -137,51 +105,30 @@ __device__ __forceinline__ void topr_write(float sum, int taken, u64 best, float
         *gbest = -1;
         return;
     }
-    *gbest = (int)(0xFFFFFFFFu - (uint32_t)best);
+    *gbest = (int)rank_index(best);
     store_canon(gscore, div_rn(sum, (float)taken));
 }
+
+struct ToprGroup {
+    int r;
+    template <int W>
+    __device__ __forceinline__ void group(const float* __restrict__ row, int G, const int* __restrict__ pos, int c, int t,
+                                          bool write, int, float* __restrict__ gscore, int* __restrict__ gbest,
+                                          long g) const {
+        float sum;
+        int taken;
+        u64 best;
+        group_select<W>(row, G, pos, c, t, r, sum, taken, best);
+        if (write && t == 0) topr_write(sum, taken, best, gscore + g, gbest + g);
+    }
+};
 
 __global__ __launch_bounds__(GRP_THREADS) void group_topr_kernel(const float* __restrict__ scores, long ld, int G,
                                                                  const int* __restrict__ grp_off, long off_ld,
                                                                  const int* __restrict__ grp_pos, long pos_ld, int S,
                                                                  int r, float* __restrict__ gscore,
                                                                  int* __restrict__ gbest) {
-    const long p = blockIdx.y;
-    const float* row = scores + p * ld;
-    const int* off = grp_off + p * off_ld;
-    const int* pos = grp_pos + p * pos_ld;
-    float* os = gscore + p * (long)S;
-    int* ob = gbest + p * (long)S;
-    const long g0 = (long)blockIdx.x * GRP_TILE;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int team = threadIdx.x / GRP_TEAM, t = threadIdx.x % GRP_TEAM;
-    // pass 1: a team of 16 per group of at most GRP_WIDE entries (the trip count is the same for every lane)
-    for (int i = 0; i < GRP_TILE / (GRP_THREADS / GRP_TEAM); ++i) {
-        const long g = g0 + team + (long)i * (GRP_THREADS / GRP_TEAM);
-        int o0 = 0, c = 0;
-        if (g < S) {
-            o0 = off[g];
-            c = off[g + 1] - o0;
-        }
-        const bool mine = g < S && c <= GRP_WIDE;
-        float sum;
-        int taken;
-        u64 best;
-        group_select<GRP_TEAM>(row, G, pos + o0, mine && c > 0 && o0 >= 0 ? c : 0, t, r, sum, taken, best);
-        if (mine && t == 0) topr_write(sum, taken, best, os + g, ob + g);
-    }
-    // pass 2: a whole wave per larger group (the branch is uniform over the wave)
-    for (int i = wave; i < GRP_TILE; i += GRP_THREADS / 64) {
-        const long g = g0 + i;
-        if (g >= S) break;
-        const int o0 = off[g], c = off[g + 1] - o0;
-        if (c <= GRP_WIDE || o0 < 0) continue;
-        float sum;
-        int taken;
-        u64 best;
-        group_select<64>(row, G, pos + o0, c, lane, r, sum, taken, best);
-        if (lane == 0) topr_write(sum, taken, best, os + g, ob + g);
-    }
+    group_walk(scores, ld, G, grp_off, off_ld, grp_pos, pos_ld, S, gscore, gbest, ToprGroup{r});
 }
 
 // L(v) over the n values in LDS mapped by f: lane-strided adds, then the xor butterfly
@@ -251,22 +198,13 @@ __global__ __launch_bounds__(COH_ROWS * 64) void cohort_decide_kernel(const floa
 
 extern "C" int fpm_group_topr(const float* scores, long ld, int P, int G, const int* grp_off, long off_ld,
                               const int* grp_pos, long pos_ld, int S, int r, float* gscore, int* gbest, void* stream) {
-    FPM_CHECK_ARG(P >= 0 && G >= 1 && ld >= G, "group_topr: bad sizes (P %d, G %d, ld %ld)", P, G, ld);
-    FPM_CHECK_ARG(S >= 0, "group_topr: S = %d groups", S);
-    FPM_CHECK_ARG(r >= 1 && r <= FPM_TOPR_MAX, "group_topr: r = %d outside [1, %d]", r, FPM_TOPR_MAX);
-    FPM_CHECK_ARG(off_ld == 0 || off_ld >= (long)S + 1,
-                  "group_topr: off_ld = %ld (0: one structure for all rows; else at least S + 1 = %ld)", off_ld,
-                  (long)S + 1);
-    FPM_CHECK_ARG(pos_ld >= 0 && (off_ld == 0) == (pos_ld == 0),
-                  "group_topr: pos_ld = %ld with off_ld = %ld (both 0, or one structure per row)", pos_ld, off_ld);
-    FPM_CHECK_ARG(scores && grp_off && grp_pos && gscore && gbest,
-                  "group_topr: scores, grp_off, grp_pos, gscore and gbest are required");
-    FPM_CHECK_ARG(P <= 65535, "group_topr: at most 65535 rows per call (P %d)", P);
-    if (P == 0 || S == 0) return 0;
-    const unsigned tiles = (unsigned)(((long)S + GRP_TILE - 1) / GRP_TILE);
-    hipLaunchKernelGGL(group_topr_kernel, dim3(tiles, (unsigned)P), dim3(GRP_THREADS), 0, (hipStream_t)stream, scores,
-                       ld, G, grp_off, off_ld, grp_pos, pos_ld, S, r, gscore, gbest);
-    return fpm::check_launch("fpm_group_topr");
+    return group_launch(
+        "fpm_group_topr", group_topr_kernel,
+        [&] {
+            FPM_CHECK_ARG(r >= 1 && r <= FPM_TOPR_MAX, "group_topr: r = %d outside [1, %d]", r, FPM_TOPR_MAX);
+            return 0;
+        },
+        scores, ld, P, G, grp_off, off_ld, grp_pos, pos_ld, S, r, gscore, gbest, stream);
 }
 
 extern "C" int fpm_cohort_decide(const float* top, int P, int K, int k, int skip, int cohort, float sigma_floor,

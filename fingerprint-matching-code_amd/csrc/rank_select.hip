@@ -1,6 +1,6 @@
 // Per-probe top-k for k up to 1024 (the shortlist of a 1:N identification): the ranking of
-// rank.hip (64-bit key = order-preserving score bits << 32 | (0xFFFFFFFF - index), unique per
-// element; descending, ties to the lower index, NaN after every number) without k passes over the row.
+// rank.hip (by the ranking key of rank_key.h, unique per element: descending, ties to the lower
+// index, NaN after every number) without k passes over the row.
 //
 //   1. Radix search for the k-th largest key T: six digit passes over the key's 64 bits from the top
 //      (five of 11 bits, one of 9).  A pass is one launch of several workgroups per row; each builds
@@ -16,16 +16,16 @@
 // fpm_rank_keep (the prescreen of a 1:N identification) takes step 1 as it is (rs_search) for any k <= G and
 // replaces steps 2 and 3 by an ordered compaction: the columns whose key is >= T, in ascending column order,
 // with no slot handed out by an atomic (below).
-#include "fpm_common.h"
+#include "rank_key.h"
 #include "fpm.h"
 
 namespace {
+using namespace fpm;
 constexpr int RS_THREADS = 256;
 constexpr int RS_KMAX = FPM_RANK_SELECT_KMAX;
 constexpr int RS_PASSES = 6;
 constexpr int RS_BINS = 2048;
 constexpr int RS_ITEMS = 16;                       // elements per thread and slice pass
-typedef unsigned long long u64;
 
 __device__ __host__ constexpr int rs_width(int d) { return d < 5 ? 11 : 9; }
 __device__ __host__ constexpr int rs_shift(int d) { return d < 5 ? 53 - 11 * d : 0; }
@@ -39,16 +39,6 @@ struct RsRow {
     unsigned pad;
     u64 cand[RS_KMAX];
 };
-
-// as rank.hip's rank_bits
-__device__ __forceinline__ uint32_t rs_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ u64 rs_key(float f, int i) {
-    return ((u64)rs_bits(f) << 32) | (0xFFFFFFFFu - (uint32_t)i);
-}
 
 // prefix / remaining rank of pass d (1 <= d <= 6) from pass d - 1's state and finished histogram;
 // every thread of the workgroup returns with the same pair.  sh: RS_THREADS + 2 words of LDS.
@@ -116,7 +106,7 @@ __global__ __launch_bounds__(RS_THREADS) void rank_select_hist_kernel(const floa
         for (int q = 0; q < RS_ITEMS; ++q) {
             const long i = base + q * RS_THREADS + threadIdx.x;
             if (i < G) {
-                const u64 key = rs_key(row[i], (int)i);
+                const u64 key = rank_key(row[i], (uint32_t)i);
                 if (d == 0 || (key >> (sh_d + wd)) == prefix)
                     atomicAdd(&lh[(unsigned)(key >> sh_d) & ((1u << wd) - 1u)], 1u);
             }
@@ -140,7 +130,7 @@ __global__ __launch_bounds__(RS_THREADS) void rank_select_compact_kernel(const f
         for (int q = 0; q < RS_ITEMS; ++q) {
             const long i = base + q * RS_THREADS + threadIdx.x;
             if (i < G) {
-                const u64 key = rs_key(row[i], (int)i);
+                const u64 key = rank_key(row[i], (uint32_t)i);
                 if (key >= T) {
                     const unsigned slot = atomicAdd(&w->count, 1u);
                     if (slot < (unsigned)k) w->cand[slot] = key;     // exactly k keys pass; the guard bounds the write
@@ -175,10 +165,10 @@ __global__ __launch_bounds__(RS_THREADS) void rank_select_sort_kernel(const floa
             __syncthreads();
         }
     for (int j = threadIdx.x; j < k; j += RS_THREADS) {
-        const uint32_t i = 0xFFFFFFFFu - (uint32_t)key[j];
+        const uint32_t i = rank_index(key[j]);
         const bool ok = i < (uint32_t)G;             // always, with k <= G keys in the list; never read outside the row
         top_idx[(long)blockIdx.x * k + j] = ok ? (int)i : -1;
-        top_score[(long)blockIdx.x * k + j] = ok ? row[i] : __uint_as_float(0x7FC00000u);
+        top_score[(long)blockIdx.x * k + j] = ok ? row[i] : qnan();
     }
 }
 
@@ -229,7 +219,7 @@ __global__ __launch_bounds__(RS_THREADS) void rank_keep_count_kernel(const float
     rs_derive(w, RS_PASSES, (unsigned)k, sh, T, krem);
     const long c0 = (long)blockIdx.x * len, c1 = c0 + len < G ? c0 + len : G;
     unsigned c = 0;
-    for (long i = c0 + threadIdx.x; i < c1; i += RS_THREADS) c += rs_key(row[i], (int)i) >= T ? 1u : 0u;
+    for (long i = c0 + threadIdx.x; i < c1; i += RS_THREADS) c += rank_key(row[i], (uint32_t)i) >= T ? 1u : 0u;
     c = rk_block_sum(c, sh);
     if (threadIdx.x == 0) cnt[(long)blockIdx.y * gridDim.x + blockIdx.x] = c;
 }
@@ -254,7 +244,7 @@ __global__ __launch_bounds__(RS_THREADS) void rank_keep_write_kernel(const float
     const long c0 = (long)blockIdx.x * len, c1 = c0 + len < G ? c0 + len : G;
     for (long b = c0; b < c1; b += RK_CHUNK) {               // the trip count is the workgroup's
         const long i = b + tid;
-        const bool in = i < c1 && rs_key(row[i < c1 ? i : c0], (int)i) >= T;
+        const bool in = i < c1 && rank_key(row[i < c1 ? i : c0], (uint32_t)i) >= T;
         const u64 m = __ballot(in);
         if (lane == 0) wc[wv] = (unsigned)__popcll(m);
         __syncthreads();

@@ -335,18 +335,11 @@ def rows_gather_scale(y, row_off, idx, nmax, coef=None, out_f=None, out_t=None, 
     for name, t, dt in (("idx", idx, torch.int32), ("row_off", row_off, torch.int64)):
         _check_index_tensors("rows_gather_scale", ((name, t, dt),))
         _check_on_device_of("rows_gather_scale", y, ((name, t),))
-    if y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != 768 or not y.is_contiguous():
-        raise _lib.FpmError("rows_gather_scale: y must be contiguous fp32 rows of 768 channels")
+    _check_row_store("rows_gather_scale", "y", y)
     G, B, nmax = int(row_off.numel()) - 1, int(idx.numel()), int(nmax)
     if G < 1 or nmax < 0:
         raise _lib.FpmError("rows_gather_scale: empty gallery or negative nmax")
-    ih, oh = _host_copy(idx_host, idx), _host_copy(row_off_host, row_off)
-    if ih.numel() != B or oh.numel() != G + 1:
-        raise _lib.FpmError("rows_gather_scale: host copies of idx / row_off do not match the device tensors")
-    if not _offsets_rise(oh, y):
-        raise _lib.FpmError("rows_gather_scale: row_off must rise from 0 to the %d rows of y" % y.shape[0])
-    if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
-        raise _lib.FpmError("rows_gather_scale: idx value outside [0, %d)" % G)
+    ih, oh = _check_selection("rows_gather_scale", idx, row_off, y, "y", idx_host, row_off_host)
     if B and int((oh[ih + 1] - oh[ih]).max()) > nmax:
         raise _lib.FpmError("rows_gather_scale: a selected graph has n_g = %d > nmax = %d"
                             % (int((oh[ih + 1] - oh[ih]).max()), nmax))
@@ -383,10 +376,8 @@ def rows_fetch(src, row_off, idx, out, out_off, idx_host=None, row_off_host=None
     the copy."""
     _check_index_tensors("rows_fetch", (("idx", idx, torch.int32), ("row_off", row_off, torch.int64),
                                         ("out_off", out_off, torch.int64)))
-    for name, t in (("src", src), ("out", out)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
-                or not t.is_contiguous():
-            raise _lib.FpmError("rows_fetch: %s must be contiguous fp32 rows of 768 channels" % name)
+    _check_row_store("rows_fetch", "src", src)
+    _check_row_store("rows_fetch", "out", out)
     for name, t in (("row_off", row_off), ("idx", idx), ("out_off", out_off)):
         if t.device != out.device:
             raise _lib.FpmError("rows_fetch: %s is on %s, out on %s" % (name, t.device, out.device))
@@ -398,13 +389,7 @@ def rows_fetch(src, row_off, idx, out, out_off, idx_host=None, row_off_host=None
         raise _lib.FpmError("rows_fetch: empty gallery")
     if out_off.numel() != M + 1:
         raise _lib.FpmError("rows_fetch: out_off must hold %d offsets (got %d)" % (M + 1, out_off.numel()))
-    ih, oh = _host_copy(idx_host, idx), _host_copy(row_off_host, row_off)
-    if ih.numel() != M or oh.numel() != G + 1:
-        raise _lib.FpmError("rows_fetch: host copies of idx / row_off do not match the device tensors")
-    if not _offsets_rise(oh, src):
-        raise _lib.FpmError("rows_fetch: row_off must rise from 0 to the %d rows of src" % src.shape[0])
-    if M and (int(ih.min()) < 0 or int(ih.max()) >= G):
-        raise _lib.FpmError("rows_fetch: idx value outside [0, %d)" % G)
+    ih, oh = _check_selection("rows_fetch", idx, row_off, src, "src", idx_host, row_off_host)
     if M > 65535:
         raise _lib.FpmError("rows_fetch: at most 65535 entries per call")
     ng = oh[ih + 1] - oh[ih]
@@ -441,12 +426,8 @@ def rows_pack(src, n, nmax, out_off, out32=None, out16=None, n_host=None, out_of
     if out32 is None and out16 is None:
         raise _lib.FpmError("rows_pack: give out32, out16 or both")
     for name, t, dt in (("src", src, torch.float32), ("out32", out32, torch.float32), ("out16", out16, torch.bfloat16)):
-        if t is None and name != "src":
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 768 \
-                or not t.is_contiguous():
-            raise _lib.FpmError("rows_pack: %s must be contiguous %s rows of 768 channels"
-                                % (name, "bf16" if dt == torch.bfloat16 else "fp32"))
+        if t is not None or name == "src":
+            _check_row_store("rows_pack", name, t, dt)
     for name, t in (("n", n), ("out_off", out_off), ("out32", out32), ("out16", out16)):
         if t is not None and t.device != src.device:
             raise _lib.FpmError("rows_pack: %s is on %s, src on %s" % (name, t.device, src.device))
@@ -524,16 +505,13 @@ def rows_move(src_off, dst_off, cnt, src32=None, dst32=None, src16=None, dst16=N
         raise _lib.FpmError("rows_move: the fp8 rows go as src8, dst8, srcs and dsts together, without other rows")
     if src32 is None and src16 is None and not fp8:
         raise _lib.FpmError("rows_move: give the fp32 rows (src32, dst32), the bf16 rows (src16, dst16) or both")
-    pairs = [(s, d, dt) for s, d, dt in ((src32, dst32, torch.float32), (src16, dst16, torch.bfloat16),
-                                         (src8, dst8, torch.float8_e4m3fn)) if s is not None]
-    for s, d, dt in pairs:
-        for name, t in (("src", s), ("dst", d)):
-            name += {torch.float32: "32", torch.bfloat16: "16", torch.float8_e4m3fn: "8"}[dt]
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 768 \
-                    or not t.is_contiguous():
-                raise _lib.FpmError("rows_move: %s must be contiguous %s rows of 768 channels"
-                                    % (name, {torch.float32: "fp32", torch.bfloat16: "bf16",
-                                              torch.float8_e4m3fn: "float8_e4m3fn"}[dt]))
+    pairs = []
+    for bits, s, d, dt in (("32", src32, dst32, torch.float32), ("16", src16, dst16, torch.bfloat16),
+                           ("8", src8, dst8, torch.float8_e4m3fn)):
+        if s is not None:
+            _check_row_store("rows_move", "src" + bits, s, dt)
+            _check_row_store("rows_move", "dst" + bits, d, dt)
+            pairs.append((s, d, dt))
     if fp8:
         for name, t, rows in (("srcs", srcs, src8), ("dsts", dsts, dst8)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() \
@@ -632,9 +610,7 @@ def rows_quant8(y, y8=None, s8=None):
     Everything lives on one device.  Checked on the host before anything is launched: dtypes, contiguity,
     devices, sizes and 16-byte alignment.  ``rows`` = 0 launches nothing.  CPU tensors take the torch
     statement of the definition."""
-    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != 768 \
-            or not y.is_contiguous():
-        raise _lib.FpmError("rows_quant8: y must be contiguous fp32 rows of 768 channels")
+    _check_row_store("rows_quant8", "y", y)
     rows = int(y.shape[0])
     if y8 is None:
         y8 = torch.empty(rows, 768, device=y.device, dtype=torch.float8_e4m3fn)
@@ -662,10 +638,10 @@ def rows_quant8(y, y8=None, s8=None):
 
 
 def rank_key(scores, ids=None):
-    """The 64-bit ranking key of fpm_rank_topk for a (P, G) fp32 tensor, as int64 whose signed order
-    is the key's unsigned order shifted by 2^63: (order-preserving bits of the score) << 32 |
-    (0xFFFFFFFF - index); NaN maps below -inf, -0 below +0.  ``ids`` (integers of scores' shape, each in
-    [0, 2^32)): taken in place of the column number (``topk_merge``'s key)."""
+    """The 64-bit ranking key (the host statement of csrc/rank_key.h) for a (P, G) fp32 tensor, as int64
+    whose signed order is the key's unsigned order shifted by 2^63: (order-preserving bits of the score)
+    << 32 | (0xFFFFFFFF - index); NaN maps below -inf, -0 below +0.  ``ids`` (integers of scores' shape,
+    each in [0, 2^32)): taken in place of the column number (``topk_merge``'s key)."""
     s = scores.detach().to(torch.float32)
     u = s.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
     neg = u >= 0x80000000
@@ -678,35 +654,28 @@ def rank_key(scores, ids=None):
     return ((bits - 0x80000000) << 32) | (0xFFFFFFFF - i)
 
 
+def _top_outputs(op, scores, k, top_idx, top_score):
+    """``rank_topk``'s and ``rank_select``'s outputs on the device path, the caller's or new ones."""
+    _dev(top_idx, top_score)
+    shape, msg = (int(scores.shape[0]), k), "top_idx must be contiguous int32, top_score contiguous fp32"
+    return (_out_tensor(op, "top_idx", top_idx, shape, torch.int32, scores.device, msg),
+            _out_tensor(op, "top_score", top_score, shape, torch.float32, scores.device, msg))
+
+
 def rank_topk(scores, k, top_idx=None, top_score=None):
     """Per-row top-k of scores (P, G) fp32 (any row stride) -> (top_idx (P, k) int32, top_score (P, k)
     fp32): descending score, ties to the lower index, NaN after every number (NaNs by index).
     Device tensors run fpm_rank_topk; CPU tensors take the host path below (a stable sort on the same
     key), which states the semantics."""
-    if scores.dim() != 2 or scores.dtype != torch.float32:
-        raise _lib.FpmError("rank_topk: scores must be a (P, G) fp32 tensor")
-    P, G = int(scores.shape[0]), int(scores.shape[1])
+    P, G = _check_scores("rank_topk", scores)
     k = int(k)
     if not 1 <= k <= min(G, 128):
         raise _lib.FpmError("rank_topk: k = %d outside [1, min(G, 128) = %d]" % (k, min(G, 128)))
     if not scores.is_cuda:
-        order = torch.argsort(rank_key(scores), dim=1, descending=True, stable=True)[:, :k]
+        order = _rank_order(scores, k)
         return order.to(torch.int32), torch.gather(scores, 1, order)
-    if G > 1 and scores.stride(1) != 1:
-        scores = scores.contiguous()
-    ld = int(scores.stride(0)) if P > 1 else G
-    if ld < G:
-        scores, ld = scores.contiguous(), G
-    if top_idx is None:
-        top_idx = torch.empty(P, k, device=scores.device, dtype=torch.int32)
-    if top_score is None:
-        top_score = torch.empty(P, k, device=scores.device, dtype=torch.float32)
-    _shape(top_idx, (P, k), "rank_topk top_idx")
-    _shape(top_score, (P, k), "rank_topk top_score")
-    if top_idx.dtype != torch.int32 or top_score.dtype != torch.float32 or not top_idx.is_contiguous() \
-            or not top_score.is_contiguous():
-        raise _lib.FpmError("rank_topk: top_idx must be contiguous int32, top_score contiguous fp32")
-    _dev(top_idx, top_score)
+    scores, ld = _dense_rows(scores)
+    top_idx, top_score = _top_outputs("rank_topk", scores, k, top_idx, top_score)
     _lib.call("fpm_rank_topk", _p(scores), ld, P, G, k, _p(top_idx), _p(top_score), _stream(scores))
     return top_idx, top_score
 
@@ -721,38 +690,21 @@ def rank_select(scores, k, top_idx=None, top_score=None):
     search for the k-th largest key over several workgroups per row, a compaction, a sort of the k in
     LDS); CPU tensors take the same stable sort as ``rank_topk``'s host path.  Keys are unique, so
     the two agree bit for bit, and with ``rank_topk`` for k <= 128."""
-    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
-        raise _lib.FpmError("rank_select: scores must be a (P, G) fp32 tensor")
-    P, G = int(scores.shape[0]), int(scores.shape[1])
+    P, G = _check_scores("rank_select", scores)
     k = int(k)
     if not 1 <= k <= min(G, RANK_SELECT_KMAX):
         raise _lib.FpmError("rank_select: k = %d outside [1, min(G, %d) = %d]"
                             % (k, RANK_SELECT_KMAX, min(G, RANK_SELECT_KMAX)))
     if not scores.is_cuda:
-        order = torch.argsort(rank_key(scores), dim=1, descending=True, stable=True)[:, :k]
+        order = _rank_order(scores, k)
         return order.to(torch.int32), torch.gather(scores, 1, order)
     if P > 65535:
         raise _lib.FpmError("rank_select: at most 65535 rows per call")
-    if G > 1 and scores.stride(1) != 1:
-        scores = scores.contiguous()
-    ld = int(scores.stride(0)) if P > 1 else G
-    if ld < G:
-        scores, ld = scores.contiguous(), G
-    if top_idx is None:
-        top_idx = torch.empty(P, k, device=scores.device, dtype=torch.int32)
-    if top_score is None:
-        top_score = torch.empty(P, k, device=scores.device, dtype=torch.float32)
-    _shape(top_idx, (P, k), "rank_select top_idx")
-    _shape(top_score, (P, k), "rank_select top_score")
-    if top_idx.dtype != torch.int32 or top_score.dtype != torch.float32 or not top_idx.is_contiguous() \
-            or not top_score.is_contiguous():
-        raise _lib.FpmError("rank_select: top_idx must be contiguous int32, top_score contiguous fp32")
-    _dev(top_idx, top_score)
+    scores, ld = _dense_rows(scores)
+    top_idx, top_score = _top_outputs("rank_select", scores, k, top_idx, top_score)
     if P == 0:
         return top_idx, top_score
-    # scratch of this call alone, allocated on the caller's stream (histograms, prefix states, the k keys)
-    wsb = int(_lib.load().fpm_rank_select_ws_bytes(P))
-    ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
+    ws, wsb = _scratch("fpm_rank_select_ws_bytes", scores.device, P)     # histograms, prefix states, the k keys
     _lib.call("fpm_rank_select", _p(scores), ld, P, G, k, _p(top_idx), _p(top_score), _p(ws), wsb, _stream(scores))
     return top_idx, top_score
 
@@ -765,35 +717,20 @@ def rank_keep(scores, k, keep=None):
     (``rank_select``'s radix search for the k-th key, then an ordered compaction: counts per slice, their
     prefix, ballots; no atomics hand out a slot); CPU tensors take the statement: a stable descending sort on the
     key, the first k, sorted by column.  Keys are unique, so the two agree bit for bit."""
-    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
-        raise _lib.FpmError("rank_keep: scores must be a (P, G) fp32 tensor")
-    P, G = int(scores.shape[0]), int(scores.shape[1])
+    P, G = _check_scores("rank_keep", scores)
     k = int(k)
     if not 1 <= k <= G:
         raise _lib.FpmError("rank_keep: k = %d outside [1, G = %d]" % (k, G))
     if P > 65535:
         raise _lib.FpmError("rank_keep: at most 65535 rows per call")
-    if keep is not None:
-        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.int32 or not keep.is_contiguous() \
-                or keep.device != scores.device:
-            raise _lib.FpmError("rank_keep: keep must be contiguous int32 on the scores' device")
-        _shape(keep, (P, k), "rank_keep keep")
+    keep = _out_tensor("rank_keep", "keep", keep, (P, k), torch.int32, scores.device,
+                       "keep must be contiguous int32 on the scores' device")
     if not scores.is_cuda:
-        order = torch.argsort(rank_key(scores), dim=1, descending=True, stable=True)[:, :k]
-        res = torch.sort(order, dim=1).values.to(torch.int32)
-        return res if keep is None else keep.copy_(res)
-    if G > 1 and scores.stride(1) != 1:
-        scores = scores.contiguous()
-    ld = int(scores.stride(0)) if P > 1 else G
-    if ld < G:
-        scores, ld = scores.contiguous(), G
-    if keep is None:
-        keep = torch.empty(P, k, device=scores.device, dtype=torch.int32)
+        return keep.copy_(torch.sort(_rank_order(scores, k), dim=1).values)
     if P == 0:
         return keep
-    # scratch of this call alone, allocated on the caller's stream (histograms, prefix states, the slices' counts)
-    wsb = int(_lib.load().fpm_rank_keep_ws_bytes(P, G))
-    ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
+    scores, ld = _dense_rows(scores)
+    ws, wsb = _scratch("fpm_rank_keep_ws_bytes", scores.device, P, G)    # histograms, prefix states, slice counts
     _lib.call("fpm_rank_keep", _p(scores), ld, P, G, k, _p(keep), _p(ws), wsb, _stream(scores))
     return keep
 
@@ -806,9 +743,7 @@ SCORE_CLASSES = ("genuine", "impostor")
 def _eval_args(op, scores, row_lab, col_lab, own):
     """The common inputs of ``mate_rank``, ``score_census`` and ``score_select``, checked on the host before
     anything is launched -> (scores with dense columns, its row stride, P, G, the labels' leading dimension)."""
-    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
-        raise _lib.FpmError("%s: scores must be a (P, G) fp32 tensor" % op)
-    P, G = int(scores.shape[0]), int(scores.shape[1])
+    P, G = _check_scores(op, scores)
     if G < 1:
         raise _lib.FpmError("%s: scores must have at least one column" % op)
     for name, t in (("row_lab", row_lab), ("col_lab", col_lab), ("own", own)):
@@ -825,11 +760,7 @@ def _eval_args(op, scores, row_lab, col_lab, own):
         raise _lib.FpmError("%s: col_lab of shape %s where (G,) = %s or (P, G) = %s is required"
                             % (op, tuple(col_lab.shape), (G,), (P, G)))
     lab_ld = G if col_lab.dim() == 2 else 0
-    if G > 1 and scores.stride(1) != 1:
-        scores = scores.contiguous()
-    ld = int(scores.stride(0)) if P > 1 else G
-    if ld < G:
-        scores, ld = scores.contiguous(), G
+    scores, ld = _dense_rows(scores)
     return scores, ld, P, G, lab_ld
 
 
@@ -879,8 +810,7 @@ def mate_rank(scores, row_lab, col_lab, own=None):
     mrank = torch.empty(P, device=dev, dtype=torch.int32)
     if P == 0:
         return mcol, msc, mrank
-    wsb = int(_lib.load().fpm_mate_rank_ws_bytes(P))
-    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+    ws, wsb = _scratch("fpm_mate_rank_ws_bytes", dev, P)
     _lib.call("fpm_mate_rank", _p(scores), ld, P, G, _p(row_lab), _p(col_lab), lab_ld, _p(own), _p(mcol), _p(msc),
               _p(mrank), _p(ws), wsb, _stream(scores))
     return mcol, msc, mrank
@@ -951,8 +881,7 @@ def score_select(scores, row_lab, col_lab, cls, k, own=None):
         at = torch.argsort(key, descending=True, stable=True)[k - 1]
         return scores[m][at].clone(), n
     value, count = ctypes.c_float(), ctypes.c_long()
-    wsb = int(_lib.load().fpm_score_select_ws_bytes())
-    ws = torch.empty(wsb, device=scores.device, dtype=torch.uint8)
+    ws, wsb = _scratch("fpm_score_select_ws_bytes", scores.device)
     _lib.call("fpm_score_select", _p(scores), ld, P, G, _p(row_lab), _p(col_lab), lab_ld, _p(own),
               1 + SCORE_CLASSES.index(cls), k, ctypes.byref(value), ctypes.byref(count), _p(ws), wsb, _stream(scores))
     bits = ctypes.c_int32.from_buffer_copy(value).value
@@ -1005,9 +934,7 @@ def rows_pool(y, row_off, lo=0, hi=None, out=None, row_off_host=None):
     the host before anything is launched: dtypes, contiguity, devices, 0 <= lo <= hi <= G and offsets that rise
     from 0 to R (``row_off_host``: a host copy, so the check needs no device synchronisation)."""
     op = "rows_pool"
-    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != DESC_DIM \
-            or not y.is_contiguous():
-        raise _lib.FpmError("%s: y must be contiguous fp32 rows of 768 channels" % op)
+    _check_row_store(op, "y", y)
     _check_index_tensors(op, (("row_off", row_off, torch.int64),))
     _check_on_device_of(op, y, (("row_off", row_off), ("out", out)))
     G = int(row_off.numel()) - 1
@@ -1020,11 +947,8 @@ def rows_pool(y, row_off, lo=0, hi=None, out=None, row_off_host=None):
     oh = _host_copy(row_off_host, row_off)
     if oh.numel() != G + 1 or not _offsets_rise(oh, y):
         raise _lib.FpmError("%s: row_off must rise from 0 to the %d rows of y" % (op, y.shape[0]))
-    if out is None:
-        out = torch.empty(hi - lo, DESC_DIM, device=y.device, dtype=torch.bfloat16)
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.bfloat16 or not out.is_contiguous():
-        raise _lib.FpmError("%s: out must be a contiguous bfloat16 tensor" % op)
-    _shape(out, (hi - lo, DESC_DIM), "%s out" % op)
+    out = _out_tensor(op, "out", out, (hi - lo, DESC_DIM), torch.bfloat16, y.device,
+                      "out must be a contiguous bfloat16 tensor")
     if hi == lo:
         return out
     if y.data_ptr() & 15 or out.data_ptr() & 7:
@@ -1083,11 +1007,7 @@ def desc_score(dq, dg, idx=None, out=None, idx_host=None, dtype=None):
         return out.copy_(res)
     if dtype is not None:
         raise _lib.FpmError("%s: dtype selects the host statement's arithmetic; the kernel is fp32" % op)
-    if out is None:
-        out = torch.empty(Q, B, device=dq.device, dtype=torch.float32)
-    _shape(out, (Q, B), "%s out" % op)
-    if out.dtype != torch.float32 or not out.is_contiguous():
-        raise _lib.FpmError("%s: out must be contiguous fp32" % op)
+    out = _out_tensor(op, "out", out, (Q, B), torch.float32, dq.device, "out must be contiguous fp32")
     if Q == 0 or B == 0:
         return out
     if (dq.data_ptr() | dg.data_ptr()) & 15:
@@ -1114,8 +1034,7 @@ def topk_merge(score, ids, list_off, k, top_id=None, top_score=None, top_col=Non
     and a violation raises.  Device tensors run the kernel, which equals the statement bit for bit and does
     not check the precondition (it stays inside its buffers whatever the data)."""
     op = "topk_merge"
-    if not isinstance(score, torch.Tensor) or score.dim() != 2 or score.dtype != torch.float32:
-        raise _lib.FpmError("%s: score must be a (P, L) fp32 tensor" % op)
+    P, L = _check_scores(op, score, "score", "(P, L)")
     if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or tuple(ids.shape) != tuple(score.shape):
         raise _lib.FpmError("%s: ids must be an int32 tensor of score's shape %s" % (op, tuple(score.shape)))
     if ids.device != score.device:
@@ -1132,7 +1051,6 @@ def topk_merge(score, ids, list_off, k, top_id=None, top_score=None, top_col=Non
         raise _lib.FpmError("%s: list_off must start at 0 and must not fall" % op)
     if int(length.max()) > RANK_SELECT_KMAX:
         raise _lib.FpmError("%s: a list of %d candidates, at most %d" % (op, int(length.max()), RANK_SELECT_KMAX))
-    P, L = int(score.shape[0]), int(score.shape[1])
     if int(off[-1]) != L:
         raise _lib.FpmError("%s: list_off ends at %d, a row holds %d candidates" % (op, int(off[-1]), L))
     k = int(k)
@@ -1158,17 +1076,10 @@ def topk_merge(score, ids, list_off, k, top_id=None, top_score=None, top_col=Non
     ld = int(score.stride(0)) if P > 1 else L
     if ld < L or (P > 1 and int(ids.stride(0)) != ld):
         score, ids, ld = score.contiguous(), ids.contiguous(), L
-    dev = score.device
-    outs = []
-    for name, t, dt in (("top_id", top_id, torch.int32), ("top_score", top_score, torch.float32),
-                        ("top_col", top_col, torch.int32)):
-        if t is None:
-            t = torch.empty(P, k, device=dev, dtype=dt)
-        _shape(t, (P, k), "%s %s" % (op, name))
-        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
-            raise _lib.FpmError("%s: %s must be contiguous %s on score's device" % (op, name, dt))
-        outs.append(t)
-    top_id, top_score, top_col = outs
+    top_id, top_score, top_col = (
+        _out_tensor(op, name, t, (P, k), dt, score.device, "%s must be contiguous %s on score's device" % (name, dt))
+        for name, t, dt in (("top_id", top_id, torch.int32), ("top_score", top_score, torch.float32),
+                            ("top_col", top_col, torch.int32)))
     if P == 0:
         return top_id, top_score, top_col
     offs = (ctypes.c_int * (S + 1))(*off.tolist())
@@ -1178,6 +1089,7 @@ def topk_merge(score, ids, list_off, k, top_id=None, top_score=None, top_col=Non
 
 
 GROUP_FUSE = ("max", "mean")
+# GRP_TEAM and GRP_WIDE of csrc/rank_groups.h: the host statements sum in the order these fix
 GROUP_TEAM = 16                 # lanes that sum a group of at most GROUP_WIDE entries
 GROUP_WIDE = 1024               # larger groups are summed by 64 lanes
 
@@ -1253,9 +1165,7 @@ def _group_op(op, entry, arg, scores, off, pos, gscore, gbest, off_host, pos_hos
     """The checks and the CPU / GPU dispatch shared by ``group_scores`` and ``group_topr``: ``entry`` is the
     C-ABI function, ``arg`` its one integer besides the structures (the fuse, or r), ``rows_host(scores (R, G),
     off, pos, gscore, gbest)`` the statement for rows that share one structure."""
-    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
-        raise _lib.FpmError("%s: scores must be a (P, G) fp32 tensor" % op)
-    P, G = int(scores.shape[0]), int(scores.shape[1])
+    P, G = _check_scores(op, scores)
     if G < 1:
         raise _lib.FpmError("%s: scores has no columns" % op)
     for name, t in (("off", off), ("pos", pos)):
@@ -1286,15 +1196,9 @@ def _group_op(op, entry, arg, scores, off, pos, gscore, gbest, off_host, pos_hos
     used = torch.arange(L).view(1, -1) < oh2[:, -1:]
     if bool((used & ((ph2 < 0) | (ph2 >= G))).any()):
         raise _lib.FpmError("%s: a position outside [0, %d)" % (op, G))
-    if gscore is None:
-        gscore = torch.empty(P, S, device=scores.device, dtype=torch.float32)
-    if gbest is None:
-        gbest = torch.empty(P, S, device=scores.device, dtype=torch.int32)
-    _shape(gscore, (P, S), "%s gscore" % op)
-    _shape(gbest, (P, S), "%s gbest" % op)
-    if gscore.dtype != torch.float32 or gbest.dtype != torch.int32 or not gscore.is_contiguous() \
-            or not gbest.is_contiguous() or gscore.device != scores.device or gbest.device != scores.device:
-        raise _lib.FpmError("%s: gscore must be contiguous fp32, gbest contiguous int32, on the scores' device" % op)
+    msg = "gscore must be contiguous fp32, gbest contiguous int32, on the scores' device"
+    gscore = _out_tensor(op, "gscore", gscore, (P, S), torch.float32, scores.device, msg)
+    gbest = _out_tensor(op, "gbest", gbest, (P, S), torch.int32, scores.device, msg)
     if P == 0 or S == 0:
         return gscore, gbest
     if L == 0:                                   # no positions at all: every group is empty
@@ -1308,11 +1212,7 @@ def _group_op(op, entry, arg, scores, off, pos, gscore, gbest, off_host, pos_hos
         else:
             rows_host(scores, oh2[0], ph2[0], gscore, gbest)
         return gscore, gbest
-    if G > 1 and scores.stride(1) != 1:
-        scores = scores.contiguous()
-    ld = int(scores.stride(0)) if P > 1 else G
-    if ld < G:
-        scores, ld = scores.contiguous(), G
+    scores, ld = _dense_rows(scores)
     _lib.call(entry, _p(scores), ld, P, G, _p(off), S + 1 if per_row else 0, _p(pos), L if per_row else 0, S,
               int(arg), _p(gscore), _p(gbest), _stream(scores))
     return gscore, gbest
@@ -1536,15 +1436,14 @@ def _coarse_call(kernel, pairs, y, args, B, n0max, ngmax):
     rows = {torch.float32: "", torch.bfloat16: "_rows16", torch.float8_e4m3fn: "_rows8"}[y.dtype]
     ws = ()
     if nws:
-        wsb = int(getattr(_lib.load(), one + "_ws_bytes")(*(B, n0max, ngmax)[:nws]))
-        buf = torch.empty(wsb, device=y.device, dtype=torch.uint8)
+        buf, wsb = _scratch(one + "_ws_bytes", y.device, *(B, n0max, ngmax)[:nws])
         ws = (_p(buf), wsb)
     _lib.call((many if pairs else one) + rows, *args, *ws, _stream(y))
 
 
-# The checks that ``coarse_score*``, ``coarse_pairs`` and the ``rows_*`` wrappers make alike; ``op`` names the
-# caller in the message.  (The row and device checks of ``rows_fetch`` / ``rows_pack`` word theirs after other
-# tensors -- "out on", "src on" -- and stay with them.)
+# The checks and prologues that the ranking, ``coarse_score*``, ``coarse_pairs`` and ``rows_*`` wrappers make
+# alike; ``op`` names the caller in the message.  (The device checks of ``rows_fetch`` / ``rows_pack`` word theirs
+# after other tensors -- "out on", "src on" -- and stay with them.)
 def _check_index_tensors(op, named):
     for name, t, dt in named:
         if not isinstance(t, torch.Tensor) or t.dtype != dt:
@@ -1558,7 +1457,7 @@ def _check_coarse_rows(op, y, named, row_scale=None):
     # y: the index's fp32 rows, their bf16 copy (an index's y16: the rounding already done) or their fp8 form
     # with ``row_scale`` (an index's y8 and s8: ``rows_quant8``)
     if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.bfloat16, torch.float8_e4m3fn) \
-            or y.dim() != 2 or y.shape[1] != 768 or not y.is_contiguous():
+            or y.dim() != 2 or y.shape[1] != DESC_DIM or not y.is_contiguous():
         raise _lib.FpmError("%s: y must be contiguous fp32 or bf16 rows of 768 channels (or float8_e4m3fn rows with "
                             "row_scale=)" % op)
     if (y.dtype == torch.float8_e4m3fn) != (row_scale is not None):
@@ -1573,9 +1472,7 @@ def _check_coarse_rows(op, y, named, row_scale=None):
         if row_scale.device != y.device:
             raise _lib.FpmError("%s: row_scale is on %s, y on %s" % (op, row_scale.device, y.device))
     for name, t in named:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 768 \
-                or not t.is_contiguous():
-            raise _lib.FpmError("%s: %s must be contiguous fp32 rows of 768 channels" % (op, name))
+        _check_row_store(op, name, t)
 
 
 def _check_on_device_of(op, y, named):
@@ -1591,6 +1488,74 @@ def _host_copy(host, t):
 def _offsets_rise(off, rows):
     """Host offsets ``off`` rise from 0 to the row count of ``rows``."""
     return int(off[0]) == 0 and int(off[-1]) == rows.shape[0] and not bool((off[1:] < off[:-1]).any())
+
+
+def _check_selection(op, idx, row_off, rows, rows_name, idx_host, row_off_host):
+    """A selection ``idx`` of the entries of a ragged row store, on host copies (given, or copied back): the copies
+    match the tensors, ``row_off`` rises from 0 to the rows of ``rows``, every idx is in [0, G) -> (idx, row_off)
+    as host int64."""
+    G, B = int(row_off.numel()) - 1, int(idx.numel())
+    ih, oh = _host_copy(idx_host, idx), _host_copy(row_off_host, row_off)
+    if ih.numel() != B or oh.numel() != G + 1:
+        raise _lib.FpmError("%s: host copies of idx / row_off do not match the device tensors" % op)
+    if not _offsets_rise(oh, rows):
+        raise _lib.FpmError("%s: row_off must rise from 0 to the %d rows of %s" % (op, rows.shape[0], rows_name))
+    if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
+        raise _lib.FpmError("%s: idx value outside [0, %d)" % (op, G))
+    return ih, oh
+
+
+_ROW_DTYPES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float8_e4m3fn: "float8_e4m3fn"}
+
+
+def _check_row_store(op, name, t, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 2 or t.shape[1] != DESC_DIM \
+            or not t.is_contiguous():
+        raise _lib.FpmError("%s: %s must be contiguous %s rows of %d channels" % (op, name, _ROW_DTYPES[dtype], DESC_DIM))
+
+
+def _check_scores(op, scores, name="scores", shape="(P, G)"):
+    """A score matrix -> its (P, G)."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
+        raise _lib.FpmError("%s: %s must be a %s fp32 tensor" % (op, name, shape))
+    return int(scores.shape[0]), int(scores.shape[1])
+
+
+def _dense_rows(scores):
+    """What a kernel reads a (P, G) matrix of any strides through -> (the matrix with dense columns, its row
+    stride ld >= G); copied only where the strides ask for it."""
+    P, G = int(scores.shape[0]), int(scores.shape[1])
+    if G > 1 and scores.stride(1) != 1:
+        scores = scores.contiguous()
+    ld = int(scores.stride(0)) if P > 1 else G
+    if ld < G:
+        scores, ld = scores.contiguous(), G
+    return scores, ld
+
+
+def _rank_order(scores, k):
+    """The host ranking: every row's first k columns by ``rank_key``, descending (keys are unique)."""
+    return torch.argsort(rank_key(scores), dim=1, descending=True, stable=True)[:, :k]
+
+
+def _out_tensor(op, name, t, shape, dtype, device, msg):
+    """An output: a new tensor, or the caller's ``t`` checked -- its shape, then dtype, contiguity and device,
+    which the caller words (``msg``)."""
+    if t is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if not isinstance(t, torch.Tensor):
+        raise _lib.FpmError("%s: %s" % (op, msg))
+    _shape(t, shape, "%s %s" % (op, name))
+    if t.dtype != dtype or not t.is_contiguous() or t.device != device:
+        raise _lib.FpmError("%s: %s" % (op, msg))
+    return t
+
+
+def _scratch(sym, device, *args):
+    """Scratch of one call alone, sized by the library's ``sym(*args)`` and allocated on the caller's stream
+    -> (uint8 buffer, its size)."""
+    wsb = int(getattr(_lib.load(), sym)(*args))
+    return torch.empty(wsb, device=device, dtype=torch.uint8), wsb
 
 
 def _check_iters_tau(op, iters, tau):
@@ -1622,12 +1587,7 @@ def _coarse_out(op, y, B, out, dtype, res=None):
         return out.copy_(res)
     if dtype is not None:
         raise _lib.FpmError("%s: dtype selects the host statement's arithmetic; the kernel is fp32" % op)
-    if out is None:
-        out = torch.empty(B, device=y.device, dtype=torch.float32)
-    _shape(out, (B,), "%s out" % op)
-    if out.dtype != torch.float32 or not out.is_contiguous():
-        raise _lib.FpmError("%s: out must be contiguous fp32" % op)
-    return out
+    return _out_tensor(op, "out", out, (B,), torch.float32, y.device, "out must be contiguous fp32")
 
 
 def _coarse_score_op(kernel, y, row_off, idx, yp, coef, iters, tau, out, idx_host, row_off_host, dtype,
@@ -1644,13 +1604,7 @@ def _coarse_score_op(kernel, y, row_off, idx, yp, coef, iters, tau, out, idx_hos
     if G < 1:
         raise _lib.FpmError("%s: empty gallery" % op)
     _shape(coef, (B, 768), "%s coef" % op)
-    ih, oh = _host_copy(idx_host, idx), _host_copy(row_off_host, row_off)
-    if ih.numel() != B or oh.numel() != G + 1:
-        raise _lib.FpmError("%s: host copies of idx / row_off do not match the device tensors" % op)
-    if not _offsets_rise(oh, y):
-        raise _lib.FpmError("%s: row_off must rise from 0 to the %d rows of y" % (op, y.shape[0]))
-    if B and (int(ih.min()) < 0 or int(ih.max()) >= G):
-        raise _lib.FpmError("%s: idx value outside [0, %d)" % (op, G))
+    ih, oh = _check_selection(op, idx, row_off, y, "y", idx_host, row_off_host)
     if not 1 <= n0 <= nmax:
         raise _lib.FpmError("%s: a probe of %d keypoints; the coarse pass takes 1 to %s = %d" % (op, n0, bound, nmax))
     if B:

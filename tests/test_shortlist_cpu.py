@@ -158,3 +158,5 @@ def test_rank_select_bad_arguments():
         ops.rank_select(torch.zeros(1, 9), 10)
     with pytest.raises(_lib.FpmError, match="fp32"):
         ops.rank_select(s.double(), 2)
+    with pytest.raises(_lib.FpmError, match=r"rank_topk: scores must be a \(P, G\) fp32 tensor"):
+        ops.rank_topk([[1.0, 2.0]], 1)
